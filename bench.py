@@ -9,7 +9,12 @@ system: preconditioner build (rebuilt every solve like prec->create()/free())
 and right-hand side are assembled on the GPU before the timed region
 (`ISPH: computePoisson`, reported separately as assemble_ms).
 
+A plain run sets up, warms up, times --steps steps and prints the record; --full adds everything measured beside the
+headline (roofline and SpMV profile passes, CPU baseline, other preconditioners, atom orders, drop-in and time-step
+legs, the self-validation of an N > 1 record).  --dump-outputs DIR writes what the last timed step computed.
+
   python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -161,7 +166,34 @@ def parse():
                          "not a performance figure")
     ap.add_argument("--force-rccl", action="store_true",
                     help="1 GPU only: route the periodic images through the RCCL halo path (send/recv to self)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: steady-state assembly split, SpMV profile passes and roofline, the "
+                         "self-validation of an N > 1 record, the jacobi / sa-amg lines, the drop-in legs, the CPU baseline, the "
+                         "atom-order table and the time-step leg (each still subject to its --no-* switch).  Off: set up, warm "
+                         "up, time --steps steps, write --dump-outputs, print the record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64; at most "
+                         "64 MB in all, a fixed seeded sample of rows beyond that).  solve: x (rank 0's rows) and solve_info "
+                         "(iterations, restarts, converged, implicit relative residual); step: the particles' x, v and p")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Writes {name: array} as path/<name>.npy in float64.  When the arrays together exceed DUMP_LIMIT_BYTES, every array
+    keeps a fixed, seeded sample of its rows (in row order), sized so that the files together fit."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)                   # room for the .npy headers
+    for name, a in arrays.items():
+        if total > budget and a.ndim > 0 and len(a) > 1:
+            keep = max(1, int(len(a) * (budget / total)))
+            rows = np.sort(np.random.default_rng(20251015).choice(len(a), size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 METRIC_NAME = {
@@ -477,6 +509,8 @@ def step_workload(args, json_fd=None, ctx=None, steps=None, warmup=None, quiet=F
         "host_lammps_side_ms_per_step": {"neighbour_list_and_ghosts": acc["neighbour_host"] / K * 1e3, "upload": acc["upload"] / K * 1e3,
                                          "note": "what LAMMPS does between compute() calls; not in `value`"},
     }
+    if json_fd is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": x.cpu().numpy(), "v": v.cpu().numpy(), "p": pr.cpu().numpy()})
     if json_fd is not None:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if own_ctx:
@@ -516,11 +550,11 @@ def self_launch(args):
 
 
 class Case:
-    """The resident system of one run: this rank's particles in one atom order, the assembled matrix (twice: the first
-    pass pays the one-time device allocations, the second is the steady state a time step sees), and step() = one pass of
-    `ISPH: solvePoisson` (preconditioner build + FGMRES + projections)."""
+    """The resident system of one run: this rank's particles in one atom order, the assembled matrix (with `full` twice:
+    the first pass pays the one-time device allocations, the second is the steady state a time step sees; else once), and
+    step() = one pass of `ISPH: solvePoisson` (preconditioner build + FGMRES + projections)."""
 
-    def __init__(self, env, order, lib_order):
+    def __init__(self, env, order, lib_order, full=True):
         import torch
         from isph_amd import hip, dist
         self.env, self.order, self.lib_order = env, order, lib_order
@@ -563,14 +597,16 @@ class Case:
         self.A, self.b = self.assemble()
         torch.cuda.synchronize()
         self.assemble_first_ms = (time.perf_counter() - t0) * 1e3
-        self.A.close()
-        t0 = time.perf_counter()
-        self.A, self.b = self.assemble()
-        torch.cuda.synchronize()
-        self.assemble_ms = (time.perf_counter() - t0) * 1e3
-        # the same once more with a synchronisation between computePre's volumes and the matrix assembly, for the split
-        self.A.close()
-        self.A, self.b = self.assemble(split=True)
+        self.assemble_ms = self.assemble_split_ms = None
+        if full:
+            self.A.close()
+            t0 = time.perf_counter()
+            self.A, self.b = self.assemble()
+            torch.cuda.synchronize()
+            self.assemble_ms = (time.perf_counter() - t0) * 1e3
+            # the same once more with a synchronisation between computePre's volumes and the matrix assembly, for the split
+            self.A.close()
+            self.A, self.b = self.assemble(split=True)
         self.x = torch.zeros(nlocal, dtype=torch.float64, device=dev)
         self.bwork = torch.empty_like(self.b)
         self.prm = hip.SolverParams()
@@ -746,7 +782,7 @@ def main():
         lib_order = False                                 # the extended matrix is built from the exported rows (caller's numbering)
     ctx.set_ordering("bricks" if lib_order else "caller")
     env = dict(ctx=ctx, dev=dev, args=args, td=td, world=world, rank=rank)
-    case = Case(env, args.order, lib_order)
+    case = Case(env, args.order, lib_order, full=args.full)
     spec, parts, plan, nlocal, brick, bptr = case.spec, case.parts, case.plan, case.nlocal, case.brick, case.bptr
     brows = brick[0] * brick[1] * brick[2]
     n = args.ncell
@@ -770,51 +806,55 @@ def main():
         inf = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    # the per-launch SpMV duration (HIP events on the library's stream around every in-solve SpMV) is taken in
-    # separate, untimed passes so that the event records do not sit inside the timed steps
-    ctx.set_profile(True)
-    spmv_ms, spmv_calls = 0.0, 0
-    nprof = 2
-    for _ in range(nprof):
-        infp = step()
-        spmv_ms += infp.spmv_ms
-        spmv_calls += infp.spmv_calls
-    barrier()
-    prof = ctx.profile_read()          # {class: (ms, launches)} over the nprof untimed passes (set-up + solve)
-    halo_prof = ctx.halo_profile_read() if world > 1 else None
-    x_headline = x.clone()             # the headline configuration's solution (the alt runs below reuse x)
+    if args.dump_outputs:
+        x_last = x.cpu().numpy()                # what the last timed step returned to its caller
+        info_last = np.array([inf.iters, inf.restarts, inf.converged, inf.rel_res_implicit], dtype=np.float64)
     if td is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.share_gpu else dev)
         td.all_reduce(t, op=td.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.full:
+        # the per-launch SpMV duration (HIP events on the library's stream around every in-solve SpMV) is taken in
+        # separate, untimed passes so that the event records do not sit inside the timed steps
+        ctx.set_profile(True)
+        spmv_ms, spmv_calls = 0.0, 0
+        nprof = 2
+        for _ in range(nprof):
+            infp = step()
+            spmv_ms += infp.spmv_ms
+            spmv_calls += infp.spmv_calls
+        barrier()
+        prof = ctx.profile_read()          # {class: (ms, launches)} over the nprof untimed passes (set-up + solve)
+        halo_prof = ctx.halo_profile_read() if world > 1 else None
+        x_headline = x.clone()             # the headline configuration's solution (the alt runs below reuse x)
 
-    # isolated SpMV (no halo, back-to-back launches) for reference
-    ctx.set_profile(False)
-    xin = torch.randn(plan.ncol, dtype=torch.float64, device=dev)
-    yout = torch.empty(nlocal, dtype=torch.float64, device=dev)
-    iso_ms = A.spmv_time(xin, yout, reps=args.spmv_reps) if (world == 1 and not args.force_rccl) else None
+        # isolated SpMV (no halo, back-to-back launches) for reference
+        ctx.set_profile(False)
+        xin = torch.randn(plan.ncol, dtype=torch.float64, device=dev)
+        yout = torch.empty(nlocal, dtype=torch.float64, device=dev)
+        iso_ms = A.spmv_time(xin, yout, reps=args.spmv_reps) if (world == 1 and not args.force_rccl) else None
 
-    alg_bytes = spmv_algorithmic_bytes(info_m["nrow"], info_m["nnz"])
-    # HBM traffic of the SpMV kernel from the PMC passes committed under profiles/ (rocprofv3
-    # cannot run inside this process); only quoted when it was taken on this very matrix.
-    traffic = None
-    import glob
-    tsrc = None
-    for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_spmv_traffic.json")), reverse=True):  # newest round first
-        tj = json.load(open(tpath))
-        if tj.get("nrow") == info_m["nrow"] and tj.get("nnz") == info_m["nnz"]:
-            traffic, tsrc = tj["traffic_bytes_per_launch"], os.path.relpath(tpath, ROOT)
-            break
-    avg_ms = spmv_ms / max(spmv_calls, 1)
-    achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-    # what the production kernel (16-bit window columns) is built to move: 10 B per STORED entry (padding included),
-    # the per-slice window table, x once, y once
-    nslices = (info_m["nrow"] + 63) // 64
-    moved_model = 10 * info_m["stored"] + 64 * 4 * nslices + 16 * info_m["nrow"]
+        alg_bytes = spmv_algorithmic_bytes(info_m["nrow"], info_m["nnz"])
+        # HBM traffic of the SpMV kernel from the PMC passes committed under profiles/ (rocprofv3
+        # cannot run inside this process); only quoted when it was taken on this very matrix.
+        traffic = None
+        import glob
+        tsrc = None
+        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_spmv_traffic.json")), reverse=True):  # newest round first
+            tj = json.load(open(tpath))
+            if tj.get("nrow") == info_m["nrow"] and tj.get("nnz") == info_m["nnz"]:
+                traffic, tsrc = tj["traffic_bytes_per_launch"], os.path.relpath(tpath, ROOT)
+                break
+        avg_ms = spmv_ms / max(spmv_calls, 1)
+        achieved = alg_bytes / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+        # what the production kernel (16-bit window columns) is built to move: 10 B per STORED entry (padding included),
+        # the per-slice window table, x once, y once
+        nslices = (info_m["nrow"] + 63) // 64
+        moved_model = 10 * info_m["stored"] + 64 * 4 * nslices + 16 * info_m["nrow"]
 
     # ---- N > 1: a record that validates itself (every rank takes part; rank 0 prints)
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         ctx.set_profile(False)
         cpu_side = args.share_gpu                      # gloo reduces host tensors
         red = lambda t, op: (td.all_reduce(t, op=op), t)[1]
@@ -883,19 +923,20 @@ def main():
                                       ("host-staged halo + all-reduce over gloo, ALL RANKS ON ONE GPU (rehearsal, not a performance figure)"
                                        if args.share_gpu else "RCCL halo + all-reduce"),
                        "iterations": inf.iters, "restarts": inf.restarts, "converged": inf.converged,
-                       "rel_res": inf.rel_res_implicit, "assemble_ms": assemble_ms, "assemble_first_call_ms": assemble_first_ms,
-                       "assemble_split_ms": case.assemble_split_ms,
-                       "spmv_isolated_ms": iso_ms, ("amg" if args.prec == "sa-amg" else "ilu"): pinfo},
-            "roofline": {"bound": "hbm", "kernel": "k_sell_spmv16<8,false> (SELL-64, 16-bit window columns)",
-                         "achieved": achieved, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "bytes_moved_model": moved_model,
-                         "achieved_moved_model_GBs": moved_model / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
-                         "traffic_source": (tsrc + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)") if traffic else None,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": avg_ms, "launches": spmv_calls},
+                       "rel_res": inf.rel_res_implicit, "assemble_first_call_ms": assemble_first_ms,
+                       ("amg" if args.prec == "sa-amg" else "ilu"): pinfo},
         }
-        out["roofline"].update(solve_roofline(info_m, pinfo, inf, prm, nprof, prof, elapsed / args.steps, args.prec))
-        if world == 1 and not args.no_alt and args.prec == "bjacobi-ilu0":
+        if args.full:
+            out["config"].update(assemble_ms=assemble_ms, assemble_split_ms=case.assemble_split_ms, spmv_isolated_ms=iso_ms)
+            out["roofline"] = {"bound": "hbm", "kernel": "k_sell_spmv16<8,false> (SELL-64, 16-bit window columns)",
+                               "achieved": achieved, "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                               "bytes_moved_model": moved_model,
+                               "achieved_moved_model_GBs": moved_model / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0,
+                               "traffic_source": (tsrc + " (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes)") if traffic else None,
+                               "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": avg_ms, "launches": spmv_calls}
+            out["roofline"].update(solve_roofline(info_m, pinfo, inf, prm, nprof, prof, elapsed / args.steps, args.prec))
+        if args.full and world == 1 and not args.no_alt and args.prec == "bjacobi-ilu0":
             # the two other preconditioners of the C ABI on the SAME resident system, measured in this run (same step(): the
             # preconditioner is rebuilt every solve): point Jacobi and SA-AMG (PrecondWrapper_ML's stand-in)
             alt = {}
@@ -910,7 +951,7 @@ def main():
                 alt[name] = {"ms_per_solve": (time.perf_counter() - t0) / 3 * 1e3, "iterations": ia.iters, "converged": ia.converged,
                              "rel_res": ia.rel_res_implicit}
             out["alt"] = alt
-        if world == 1 and not args.no_dropin and not args.force_rccl and args.prec == "bjacobi-ilu0" and (args.block == 512 or bptr is not None):
+        if args.full and world == 1 and not args.no_dropin and not args.force_rccl and args.prec == "bjacobi-ilu0" and (args.block == 512 or bptr is not None):
             # the unchanged SolverLin drop-in (host CSR in, host x out) beside the device-resident figure above
             # with the three-line adapter call that hands the wrapper the coordinates (the library numbers the rows), and
             # without it (pair_isph.cpp unchanged: the rows keep the atom order, 512 consecutive rows per subdomain)
@@ -928,7 +969,7 @@ def main():
                     out[key] = rec
                 else:
                     out[key] = d
-        if world == 1 and not args.no_cpu_baseline and args.prec in ("none", "jacobi", "bjacobi-ilu0", "bjacobi-ilu1", "bjacobi-ilu2", "sa-amg"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.prec in ("none", "jacobi", "bjacobi-ilu0", "bjacobi-ilu1", "bjacobi-ilu2", "sa-amg"):
             rp, ci, val = A.export_csr()                                           # the caller's numbering
             bh = b.cpu().numpy()
             o = A.ordering()
@@ -965,7 +1006,7 @@ def main():
         if multi is not None:
             out["multi_gpu"] = multi
         extra = {}
-        if world == 1 and not args.no_orders and args.prec == "bjacobi-ilu0" and not args.force_rccl:
+        if args.full and world == 1 and not args.no_orders and args.prec == "bjacobi-ilu0" and not args.force_rccl:
             # the same particles handed over in the other atom orders, with the library's own row numbering and without:
             # the headline must not depend on the order the caller's atoms happen to be in
             table = {}
@@ -985,7 +1026,7 @@ def main():
             ctx.set_ordering("bricks" if lib_order else "caller")
             extra["atom_orders"] = dict(note="<atom order handed over>/<who numbers the matrix rows>; 3 timed solves after 2, same "
                                              "particles, preconditioner rebuilt every solve", cases=table)
-        if world == 1 and not args.no_step and args.prec == "bjacobi-ilu0" and not args.force_rccl and args.kernel == "wendland":
+        if args.full and world == 1 and not args.no_step and args.prec == "bjacobi-ilu0" and not args.force_rccl and args.kernel == "wendland":
             # the reference's own protocol beside the solve: 3 ISPH time steps, everything rebuilt per step
             st = step_workload(args, None, ctx=ctx, steps=3, warmup=1, quiet=True)
             extra["step"] = dict(metric=st["metric"], steps_per_s=st["value"], ms_per_step=st["ms_per_step"], split=st["split"],
@@ -994,6 +1035,8 @@ def main():
                                  host_lammps_side_ms_per_step=st["host_lammps_side_ms_per_step"])
         if extra:
             out["extra"] = extra
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"x": x_last, "solve_info": info_last})
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if td is not None:

@@ -111,8 +111,8 @@ def build_cpp_mpi(force=False):
     flags = ["-O2", "-std=c++17", "-DISPH_HAVE_MPI", "-I", MPI_INC, "-I", INC, "-I", host]
     # conda's lib directory also holds an older libstdc++ that must not shadow the system's (libisph_hip / ROCm need the
     # newer one): link libmpi by path and let the loader find it and its two conda-only dependencies through a private
-    # directory of symlinks
-    mpilib = os.path.join(ROOT, "tests", "cpp", "mpilib")
+    # directory of symlinks (a build product: kept out of tests/, whose files are the suite's)
+    mpilib = os.path.join(ROOT, "build", "mpilib")
     os.makedirs(mpilib, exist_ok=True)
     for so in ("libmpi.so.12", "libgfortran.so.4", "libquadmath.so.0"):
         link = os.path.join(mpilib, so)

@@ -78,3 +78,25 @@ def test_cloud_builder_reproduces_the_generators_neighbourhoods():
         L = 2 * np.pi
         dxo = c["x"][nl:] - c["x"][c["owner_index"][nl:]]
         assert np.allclose(dxo / L, np.round(dxo / L), atol=1e-12) and np.all(np.abs(dxo).max(axis=1) > 1.0)
+
+
+def test_dump_outputs_writes_float64_whole_or_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: arrays below the limit are written whole in float64; above it every array keeps a seeded sample of
+    its rows, in row order, the same from call to call, and the files together stay within the limit"""
+    import numpy as np
+    x = np.arange(1000.0)
+    y = np.arange(3000, dtype=np.float32).reshape(1000, 3)
+    bench.dump_outputs(str(tmp_path / "whole"), {"x": x, "y": y})
+    xw, yw = np.load(tmp_path / "whole" / "x.npy"), np.load(tmp_path / "whole" / "y.npy")
+    assert xw.dtype == np.float64 and yw.dtype == np.float64
+    assert np.array_equal(xw, x) and np.array_equal(yw, y)
+    limit = 2 * 4096 + 16000
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "y": y})
+        assert sum(os.path.getsize(tmp_path / d / f) for f in ("x.npy", "y.npy")) <= limit
+    xa, ya = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "y.npy")
+    assert 0 < len(xa) < 1000 and 0 < len(ya) < 1000
+    assert np.all(np.diff(xa) > 0) and np.all(np.isin(xa, x))          # rows of x, in row order
+    assert np.all(ya[:, 1] - ya[:, 0] == 1.0) and np.all(np.diff(ya[:, 0]) > 0)
+    assert np.array_equal(xa, np.load(tmp_path / "b" / "x.npy")) and np.array_equal(ya, np.load(tmp_path / "b" / "y.npy"))

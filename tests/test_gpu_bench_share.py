@@ -18,7 +18,7 @@ def test_bench_two_process_ranks_sharing_the_gpu():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--ncell", "20", "--steps", "1", "--warmup", "0",
-           "--no-cpu-baseline", "--no-dropin", "--no-alt"]
+           "--full", "--no-cpu-baseline", "--no-dropin", "--no-alt"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -47,7 +47,7 @@ def test_bench_four_process_ranks_validate_their_own_record():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-gpu", "--ncell", "40", "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--no-dropin", "--no-alt"]
+           "--full", "--no-cpu-baseline", "--no-dropin", "--no-alt"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     rec = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])

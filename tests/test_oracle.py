@@ -516,59 +516,55 @@ def test_amg_with_null_vector_masked_to_the_fluid_rows():
     assert ia.converged == 1 and ii.converged == 1 and ia.iters < ii.iters
 
 
-def test_oracle_kernels_equal_the_reference_kernel_classes():
-    """oracle/_ref/libisph_refkernels.so = the reference's OWN KernelFuncWendland / Quintic / Cubic (kernel*.h, the only
-    sources of the path that build without Trilinos and LAMMPS), compiled where they lie by oracle/build.py.  The oracle's
-    W and dW/dr must be those functions: same value to the last bit or two over the whole support, both dimensions,
-    including the breakpoints and the cut radius."""
-    import ctypes
+def _ref_tables():
+    """tests/golden/ref_kernel_tables.npz (made by tests/golden/make_ref_kernel_tables.py) and that script's input builders"""
     import importlib.util
     import os
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    spec = importlib.util.spec_from_file_location("_oracle_build", os.path.join(ROOT, "oracle", "build.py"))
-    ob = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ob)
-    path = ob.build_ref()
-    if not (path and os.path.exists(path)):
-        pytest.skip("no /root/reference here and no prebuilt oracle/_ref")
-    ref = ctypes.CDLL(path)
-    ref.ref_kernel_table.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
-                                     ctypes.c_void_p, ctypes.c_void_p]
+    gdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_ref_kernel_tables", os.path.join(gdir, "make_ref_kernel_tables.py"))
+    mk = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mk)
+    return mk, np.load(os.path.join(gdir, "ref_kernel_tables.npz"))
+
+
+def test_oracle_kernels_equal_the_reference_kernel_classes():
+    """The reference's OWN KernelFuncWendland / Quintic / Cubic (kernel*.h, the only sources of the path that build without
+    Trilinos and LAMMPS), compiled where they lie by oracle/build.py into oracle/_ref/libisph_refkernels.so; what they
+    return on this test's inputs is stored in tests/golden/ref_kernel_tables.npz.  The oracle's W and dW/dr must be those
+    functions: same value to the last bit or two over the whole support, both dimensions, including the breakpoints and
+    the cut radius."""
+    import ctypes
+    mk, g = _ref_tables()
     # the particle-kind filter of every functor (filter.h:33-57) over all kinds of pair_isph.h:113-138 and all filters in use
-    kinds = [99, 12, 127, 1, 2, 4, 8, 32, 64]
-    for fi in (99, 12, 127):
-        for ik in kinds:
-            assert ref.ref_filter_yes1(fi, ik) == orc.lib().orc_filter_yes1(fi, ik)
-            for fj in (99, 12, 127):
-                for jk in kinds:
-                    assert ref.ref_filter_yes2(fi, fj, ik, jk) == orc.lib().orc_filter_yes2(fi, fj, ik, jk)
+    kinds = mk.KINDS
+    for a, fi in enumerate(mk.FILTERS):
+        for i, ik in enumerate(kinds):
+            assert g["filter_yes1"][a, i] == orc.lib().orc_filter_yes1(fi, ik)
+            for b, fj in enumerate(mk.FILTERS):
+                for j, jk in enumerate(kinds):
+                    assert g["filter_yes2"][a, b, i, j] == orc.lib().orc_filter_yes2(fi, fj, ik, jk)
     # FilterMatchBinary (filter.h:83-104) of the solute-transport / applied-potential functors: (Fluid, Fluid - BufferNeumann), (Fluid, Fluid)
-    for fi in (99, 12):
-        for ik in kinds:
-            assert ref.ref_filter_match_yes1(fi, ik) == orc.lib().orc_filter_yes1(fi | orc.FILTER_MATCH, ik)
-            for fj in (99, 99 - 64, 127):
-                for jk in kinds:
-                    assert ref.ref_filter_match_yes2(fi, fj, ik, jk) == orc.lib().orc_filter_yes2(fi | orc.FILTER_MATCH, fj, ik, jk)
+    for a, fi in enumerate(mk.MATCH_FI):
+        for i, ik in enumerate(kinds):
+            assert g["filter_match_yes1"][a, i] == orc.lib().orc_filter_yes1(fi | orc.FILTER_MATCH, ik)
+            for b, fj in enumerate(mk.MATCH_FJ):
+                for j, jk in enumerate(kinds):
+                    assert g["filter_match_yes2"][a, b, i, j] == orc.lib().orc_filter_yes2(fi | orc.FILTER_MATCH, fj, ik, jk)
     # the pair operator of every gradient / divergence / Laplacian functor (functor.h:9-20) and MirrorNothing (mirror.h:19)
-    ref.ref_sph_operator.restype = ctypes.c_double
-    ref.ref_sph_operator.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double]
-    ref.ref_mirror_nothing.restype = ctypes.c_double
-    ref.ref_mirror_nothing.argtypes = [ctypes.c_double]
     orc.lib().orc_sph_operator.restype = ctypes.c_double
     orc.lib().orc_sph_operator.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double]
-    for fi, fj in ((1.5, -0.25), (0.0, 3.0), (-2.0, -2.0), (1e-300, 1e300)):
+    for k, (fi, fj) in enumerate(mk.OPERATOR_ARGS):
         for a in (0, 1):
-            assert ref.ref_sph_operator(a, fi, fj) == orc.lib().orc_sph_operator(a, fi, fj)
-    assert ref.ref_mirror_nothing(0.3) == 1.0
-    rng = np.random.default_rng(1)
-    for kernel, name, support in ((0, "wendland", 2.0), (1, "quintic", 3.0), (2, "cubic", 2.0)):
+            assert g["sph_operator"][k, a] == orc.lib().orc_sph_operator(a, fi, fj)
+    assert float(g["mirror_nothing_0.3"]) == 1.0
+    radii = mk.oracle_radii()
+    for kernel, name, support in mk.KERNELS:
         for dim in (2, 3):
-            for h in (1.5 * 2 * np.pi / 100, 0.037, 1.0):
-                s = np.concatenate([rng.uniform(0.0, support + 0.3, 400), np.arange(0.0, support + 0.51, 0.5),
-                                    np.nextafter(np.arange(1.0, support + 0.1, 1.0), 0.0)])
-                r = np.ascontiguousarray(s * h)
-                w, dw = np.zeros_like(r), np.zeros_like(r)
-                ref.ref_kernel_table(kernel, dim, h, len(r), r.ctypes.data, w.ctypes.data, dw.ctypes.data)
+            for hi, h in enumerate(mk.ORACLE_H):
+                key = "oracle_%d_%d_%d" % (kernel, dim, hi)
+                r = radii[(kernel, dim, hi)]
+                assert np.array_equal(r, g[key + "_r"]), key        # the stored outputs belong to these inputs
+                w, dw = g[key + "_w"], g[key + "_dw"]
                 wo = np.array([orc.kernel_val(name, dim, float(x), h) for x in r])
                 dwo = np.array([orc.kernel_dval(name, dim, float(x), h) for x in r])
                 scale_w, scale_d = np.abs(w).max(), np.abs(dw).max()
