@@ -27,7 +27,8 @@ int sell_sort_rows(isph_ctx *ctx, Sell &S);         // isph_capi.hip
 int sell_set_wmax(isph_ctx *ctx, Sell &S);          // isph_capi.hip
 
 constexpr double kEps = 1.0e-24;  // ISPH_EPSILON, ref: macrodef.h:6
-enum { KIND_FLUID = 99, KIND_SOLID = 12, KIND_BUFFER_DIRICHLET = 32, KIND_BUFFER_NEUMANN = 64, KIND_ALL = 127 };  // pair_isph.h:113-124
+enum { KIND_FLUID = 99, KIND_SOLID = 12, KIND_BOUNDARY = 16, KIND_BUFFER_DIRICHLET = 32, KIND_BUFFER_NEUMANN = 64,
+       KIND_ALL = 127 };  // pair_isph.h:113-124
 
 struct AsmTables {  // small per-type tables, device resident
   const int *kind;      // [ntypes+1]
@@ -797,7 +798,10 @@ __global__ __launch_bounds__(kBlock) void k_asm_poisson(AsmTables T, PoissonArgs
 //     (Fluid, Fluid - BufferNeumann) -- rows of kind == Fluid only --, w = (1-theta) A c, A <- -theta A,
 //     diag = 1 + A_ii on Fluid rows and 1 on Solid / Buffer rows, b = c (+ w on Fluid rows);
 //   MODE 2, applied electric potential (ref: functor_applied_electric_potential.h:36-98): Laplacian(-1, sigma),
-//     FilterMatchBinary (Fluid, Fluid), no theta scaling, diag = 1 on Solid / Buffer rows, b = phi on Buffer rows, else 0.
+//     FilterMatchBinary (Fluid, Fluid), no theta scaling, diag = 1 on Solid / Buffer rows, b = phi on Buffer rows, else 0;
+//   MODE 3, the Laplacian part of the Poisson-Boltzmann Jacobian (ref: functor_poisson_boltzmann_jacobian.h:47-68):
+//     Laplacian(-1, eps), FilterBinary (Fluid, All) -- every row whose kind shares a bit with Fluid --, no theta scaling,
+//     diag = -1 and zero off-diagonal values on the other (Solid / Boundary) rows (:81-84), no b.
 // The scalar field (c or phi) travels in r2.y, the material (1 or sigma) in r2.x; dt holds the Laplacian's alpha.
 struct HelmholtzArgs {
   int nlocal, antisym, incremental, lda, morris;
@@ -830,11 +834,12 @@ __global__ void k_pack_particles_scalar(int nall, const double *__restrict__ x, 
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= nall) return;
   r1[j] = make_double4(x[3 * (size_t)j], x[3 * (size_t)j + 1], x[3 * (size_t)j + 2], vfrac[j]);
-  r2[j] = make_double4(material ? material[j] : 1.0, field[j], 0.0, 0.0);
+  r2[j] = make_double4(material ? material[j] : 1.0, field ? field[j] : 0.0, 0.0, 0.0);
   r3[j] = make_int2(type[j], colmap[j]);
 }
 
-// DIMT / FAM as in k_asm_poisson; MODE: 0 velocity Helmholtz, 1 solute transport, 2 applied electric potential
+// DIMT / FAM as in k_asm_poisson; MODE: 0 velocity Helmholtz, 1 solute transport, 2 applied electric potential,
+// 3 Poisson-Boltzmann Laplacian
 template <int DIMT, int FAM, int MODE = 0>
 __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, HelmholtzArgs a,
                                                           const long long *__restrict__ slice_off,
@@ -859,12 +864,12 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
   const long long off = sval ? slice_off[i >> 6] : 0;
   const int w = sval ? (int)((slice_off[(i >> 6) + 1] - off) >> 6) : 0;
   const int filt_i = MODE ? a.filt_i : KIND_FLUID, filt_j = MODE ? a.filt_j : KIND_ALL;
-  const bool row_ok = MODE ? (ikind == filt_i) : ((ikind & filt_i) != 0);   // FilterMatchBinary | FilterBinary
+  const bool row_ok = (MODE == 1 || MODE == 2) ? (ikind == filt_i) : ((ikind & filt_i) != 0);   // FilterMatchBinary | FilterBinary
   const int nf = MODE ? 1 : dim;                                            // right-hand-side columns
   const double alpha = a.dt;
   const double invrho = MODE ? 1.0 : 1.0 / a.rho[i];
   const double mi = MODE ? a.r2[i].x : a.nu[i] * a.rho[i];
-  const double vscale = MODE == 2 ? 1.0 : -a.theta;                         // what multiplies the Laplacian in A
+  const double vscale = MODE >= 2 ? 1.0 : -a.theta;                         // what multiplies the Laplacian in A
   const int jb = 0, je = T.nlen[i];
   int cnt = 0, pdiag = -1;
   const int ci_own = a.colmap[i];
@@ -882,7 +887,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
         if (sval) { scol[p] = cj; sval[p] = 0.0; }
       }
     }
-    diag_final = 1.0;  // solid rows: unit diagonal, b unchanged (:114-117)
+    diag_final = MODE == 3 ? -1.0 : 1.0;  // solid rows: unit diagonal, b unchanged (:114-117); PB: minus unit row
   } else {
     double G[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, L[6] = {1, 0, 1, 0, 0, 1};
     if (dim == 2) { G[0] = 1; G[1] = 0; G[2] = 0; G[3] = 1; L[0] = 1; L[1] = 0; L[2] = 1; }
@@ -1006,7 +1011,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
     const double dval = ((diag1 + diag2) * alpha) * invrho;
     if (MODE) wv[0] += dval * a.r2[i].y;
     else for (int k = 0; k < dim; ++k) wv[k] += dval * a.v[3 * (size_t)i + k];
-    diag_final = MODE == 2 ? dval : 1.0 + dval * (-a.theta);
+    diag_final = MODE >= 2 ? dval : 1.0 + dval * (-a.theta);
   }
   {
     if (pdiag < 0) pdiag = cnt++;
@@ -1023,7 +1028,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
     b[i] = bk;
   } else if (MODE == 2) {  // b = phi on the buffers, 0 elsewhere, functor_applied_electric_potential.h:76-90
     b[i] = (ikind == KIND_BUFFER_DIRICHLET || ikind == KIND_BUFFER_NEUMANN) ? a.r2[i].y : 0.0;
-  } else {
+  } else if (MODE == 0) {
     for (int k = 0; k < dim; ++k) {
       double bk = a.v[3 * (size_t)i + k];
       if (ikind & filt_i) {
@@ -1457,8 +1462,9 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
                               const double *gvec, int incremental, const double *vel, int ncol, isph_mat **A_out,
                               double *b_out, int lda, int on_device, int mode = 0, const double *field = nullptr,
                               const double *material = nullptr) {
-  // mode 1 / 2: the scalar callers (HelmholtzArgs); dt then carries the Laplacian's alpha, field = c or phi [nall]
-  ISPH_REQUIRE(mode == 0 || (field && A_out), "scalar assembly needs the field and a matrix handle");
+  // mode 1 / 2: the scalar callers (HelmholtzArgs); dt then carries the Laplacian's alpha, field = c or phi [nall];
+  // mode 3: the Poisson-Boltzmann Laplacian (no field, no b: b_out may be NULL)
+  ISPH_REQUIRE(mode == 0 || ((field || mode == 3) && A_out), "scalar assembly needs the field and a matrix handle");
   ISPH_REQUIRE(P->dim == 2 || P->dim == 3, "dim must be 2 or 3");
   ISPH_REQUIRE(P->x && P->type && (P->neigh_ptr || P->neigh_ptr64) && P->neigh_idx && P->colmap, "particle arrays missing");
   ISPH_REQUIRE(antisym || (P->Gc && P->Lc), "Symmetric family needs Gc and Lc");
@@ -1513,15 +1519,18 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
   if (rc == ISPH_SUCCESS)
     for (int t = 1; t <= P->ntypes; ++t)
       if (P->kind[t] != KIND_FLUID && P->kind[t] != KIND_SOLID &&
-          !(mode != 0 && (P->kind[t] == KIND_BUFFER_DIRICHLET || P->kind[t] == KIND_BUFFER_NEUMANN)))
-        rc = fail(mode ? "only fluid/solid/buffer particle kinds are supported" : "only fluid/solid particle kinds are supported", __FILE__, __LINE__);
+          !(mode != 0 && (P->kind[t] == KIND_BUFFER_DIRICHLET || P->kind[t] == KIND_BUFFER_NEUMANN)) &&
+          !(mode == 3 && P->kind[t] == KIND_BOUNDARY))
+        rc = fail(mode == 3 ? "only fluid/solid/boundary/buffer particle kinds are supported"
+                  : mode ? "only fluid/solid/buffer particle kinds are supported" : "only fluid/solid particle kinds are supported", __FILE__, __LINE__);
   Sell &M = A->S;
   M.nrow = n; M.ncol = ncol; M.nslices = (n + kSlice - 1) / kSlice;
   if (rc == ISPH_SUCCESS) rc = M.rowlen.reserve((size_t)(n > 0 ? n : 1));
   if (rc == ISPH_SUCCESS) rc = M.slice_off.reserve((size_t)M.nslices + 1);
-  double *db = b_out;
+  const bool no_b = mode == 3;
+  double *db = no_b ? nullptr : b_out;
   const int nrhs = mode ? 1 : dim;
-  if (rc == ISPH_SUCCESS && !on_device) { rc = bdev.reserve((size_t)lda * nrhs); db = bdev.p; }
+  if (rc == ISPH_SUCCESS && !on_device && !no_b) { rc = bdev.reserve((size_t)lda * nrhs); db = bdev.p; }
   if (rc == ISPH_SUCCESS && n > 0) {
     const int grid = (n + kBlock - 1) / kBlock;
     if (!rhs_only) {
@@ -1545,8 +1554,10 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
                            P->nall, a.x, a.vfrac, a.nu, a.v, a.type, a.colmap, pk1.p, pk2.p, pk3.p);
         a.r1 = pk1.p; a.r2 = pk2.p; a.r3 = pk3.p;
         a.filt_i = KIND_FLUID;
-        a.filt_j = mode == 1 ? KIND_FLUID - KIND_BUFFER_NEUMANN : KIND_FLUID;
-        if (mode == 1)
+        a.filt_j = mode == 1 ? KIND_FLUID - KIND_BUFFER_NEUMANN : mode == 3 ? KIND_ALL : KIND_FLUID;
+        if (mode == 3)
+          hipLaunchKernelGGL((k_asm_helmholtz<0, -1, 3>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, M.col.p, M.val.p, db);
+        else if (mode == 1)
           hipLaunchKernelGGL((k_asm_helmholtz<0, -1, 1>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, M.col.p, M.val.p, db);
         else
           hipLaunchKernelGGL((k_asm_helmholtz<0, -1, 2>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, M.col.p, M.val.p, db);
@@ -1574,7 +1585,7 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
       }
       // rows come out column-sorted when the neighbour lists were ordered; merged duplicates break that order
       if (rc == ISPH_SUCCESS && !rhs_only) rc = (T.sorted && n > 32768) ? sell_set_wmax(ctx, M) : sell_sort_rows(ctx, M);
-      if (rc == ISPH_SUCCESS && !on_device &&
+      if (rc == ISPH_SUCCESS && !on_device && !no_b &&
           hipMemcpyAsync(b_out, db, sizeof(double) * (size_t)lda * nrhs, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = fail("copy failed", __FILE__, __LINE__);
       if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)

@@ -127,6 +127,9 @@ struct isph_halo {
   int n_int = 0, n_bnd = 0;
 };
 
+struct isph_pb_rows;  // poisson_boltzmann.hpp
+namespace isph { void pb_rows_destroy(isph_pb_rows *R); }
+
 struct isph_mat {
   isph::Sell S;
   isph_halo halo;
@@ -135,6 +138,9 @@ struct isph_mat {
   isph::RowOrderPtr order;
   bool local = false;  // rectangular operator on rank-local vectors (AMG transfer operators): no ghost columns
   bool aux = false;    // a level operator of the AMG hierarchy with its own halo plan: not in the caller's SpMV statistics
+  // a Poisson-Boltzmann Jacobian (isph_assemble_poisson_boltzmann): row classes, Dirichlet values, diagonal positions in
+  // S.val, the Laplacian's diagonal, the current shift J_ii - L_ii and the Newton workspaces, all in the matrix' rows
+  isph_pb_rows *pb = nullptr;
 };
 
 struct isph_ilu;  // ilu.hpp

@@ -1095,6 +1095,7 @@ int isph_mat_export_csr(isph_ctx *ctx, const isph_mat *A, int *rowptr, int *coli
 
 void isph_mat_destroy(isph_mat *A) {
   if (!A) return;
+  pb_rows_destroy(A->pb);
   A->S.release();
   A->halo.send_idx.release();
   A->halo.list_int.release();
@@ -2013,3 +2014,6 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 }
 
 }  // extern "C"
+
+// the Poisson-Boltzmann Newton solve (isph_assemble_poisson_boltzmann, isph_pb_*, isph_solve_poisson_boltzmann)
+#include "poisson_boltzmann.hpp"

@@ -26,6 +26,7 @@ EXPORTS = [
     "isph_solve_block", "isph_assemble_block_helmholtz", "isph_amg_params_default", "isph_prec_create_amg", "isph_prec_amg_levels", "isph_prec_amg_info",
     "isph_prec_amg_export", "isph_prec_amg_aggregates",
     "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
+    "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
 ]
 
 
@@ -52,6 +53,33 @@ class SolverParams(C.Structure):
                  ortho=0, verbose=0, num_recycled=50):
         """solver_type 0 "Block GMRES", 1 "Block CG", 2 "Recycling GMRES" (GCRO-DR(num_blocks, num_recycled))"""
         super().__init__(solver_type, flexible, num_blocks, max_iters, max_restarts, tol, ortho, verbose, num_recycled)
+
+
+class PBParams(C.Structure):
+    """Mirror of isph_pb_params: the Poisson-Boltzmann physics (kappa^2 = 2 ezcb / psiref, gamma, linearized) and the
+    NOX list of SolverNOX_Stratimikos (solver_nox_impl.h:78-145, solver_nox_stratimikos.h:84-122).  Keyword arguments
+    override the defaults of isph_pb_params_default; `amg` / `linear` may be given as AmgParams / SolverParams or as a
+    dict of fields to change."""
+    _fields_ = [("kappasq", C.c_double), ("gamma", C.c_double), ("linearized", C.c_int), ("max_iters", C.c_int),
+                ("f_tol", C.c_double), ("update_tol", C.c_double), ("prec_max_age", C.c_int), ("prec_kind", C.c_int),
+                ("amg", AmgParams), ("linear", SolverParams)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().isph_pb_params_default(C.byref(self))
+        for k, v in kw.items():
+            if k in ("amg", "linear") and isinstance(v, dict):
+                sub = getattr(self, k)
+                for k2, v2 in v.items():
+                    setattr(sub, k2, v2)
+            else:
+                setattr(self, k, v)
+
+
+class PBInfo(C.Structure):
+    """isph_pb_info: status 1 converged, 0 MaxIters, -1 non-finite ||F||"""
+    _fields_ = [("status", C.c_int), ("newton_iters", C.c_int), ("linear_iters", C.c_int), ("prec_builds", C.c_int),
+                ("norm_f", C.c_double), ("norm_update", C.c_double), ("ms", C.c_double)]
 
 
 class SolveInfo(C.Structure):
@@ -207,6 +235,14 @@ def lib():
                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_assemble_applied_potential.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_pb_params_default.argtypes = [C.c_void_p]
+        L.isph_pb_params_default.restype = None
+        L.isph_assemble_poisson_boltzmann.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_int]
+        L.isph_pb_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_pb_jacobian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_solve_poisson_boltzmann.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_int]
         _lib = L
     return _lib
 
@@ -908,6 +944,64 @@ def assemble_applied_potential(ctx, parts, colmap, sigma, phi, antisym=True, nco
     _check(lib().isph_assemble_applied_potential(ctx.h, C.byref(pv), int(antisym), _ptr(sg), _ptr(phi),
                                                  nlocal if ncol is None else ncol, C.byref(A.h), _ptr(b_out), dev))
     return A, b_out
+
+
+def assemble_poisson_boltzmann(ctx, parts, colmap, eps=None, psi0=None, antisym=True, ncol=None, vfrac=None, Gc=None,
+                               Lc=None, kernel="wendland", kinds=None, pnd=None, morris_safe_coeff=0.43301):
+    """isph_assemble_poisson_boltzmann == the Laplacian part of FunctorOuterPoissonBoltzmannJacobian (the reference's
+    A.is_filled pass).  eps, psi0: [nall] or None (1 / 0).  pnd given: the MorrisHolmes mirror.  Returns the Jacobian
+    Matrix, which pb_residual / pb_jacobian / solve_poisson_boltzmann take."""
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, Gc=Gc, Lc=Lc, keep=keep, kinds=kinds,
+                                   pnd=pnd, morris_safe_coeff=morris_safe_coeff)
+    eps = None if eps is None else _f64(eps)
+    psi0 = None if psi0 is None else _f64(psi0)
+    nlocal, na = int(parts["nlocal"]), int(parts["nall"])
+    _need(eps, na, "eps [nall]"); _need(psi0, na, "psi0 [nall]")
+    J = Matrix(ctx)
+    _check(lib().isph_assemble_poisson_boltzmann(ctx.h, C.byref(pv), int(antisym), _ptr(eps), _ptr(psi0),
+                                                 nlocal if ncol is None else ncol, C.byref(J.h), dev))
+    return J
+
+
+def pb_residual(ctx, J, psi, f=None, params=None):
+    """isph_pb_residual == computeF: F [nlocal] at psi [nlocal] (f: the Extra F [nlocal] or None)"""
+    prm = params or PBParams()
+    n = J.info()["nrow"]
+    psi = _f64(psi)
+    f = None if f is None else _f64(f)
+    _need(psi, n, "psi [nlocal]"); _need(f, n, "f [nlocal]")
+    dev = _on_device(psi, f)
+    if dev:
+        import torch
+        F = torch.empty(n, dtype=torch.float64, device=psi.device)
+    else:
+        F = np.zeros(n)
+    _check(lib().isph_pb_residual(ctx.h, J.h, C.byref(prm), _ptr(psi), _ptr(f), _ptr(F), dev))
+    return F
+
+
+def pb_jacobian(ctx, J, psi, params=None):
+    """isph_pb_jacobian == computeJacobian: J's diagonal at psi [nlocal], in place"""
+    prm = params or PBParams()
+    psi = _f64(psi)
+    _need(psi, J.info()["nrow"], "psi [nlocal]")
+    _check(lib().isph_pb_jacobian(ctx.h, J.h, C.byref(prm), _ptr(psi), _on_device(psi)))
+
+
+def solve_poisson_boltzmann(ctx, J, psi, f=None, params=None):
+    """isph_solve_poisson_boltzmann == solveProblem: Newton from psi [nlocal] (updated in place: a contiguous float64
+    numpy array or CUDA tensor); returns PBInfo"""
+    prm = params or PBParams()
+    info = PBInfo()
+    n = J.info()["nrow"]
+    f = None if f is None else _f64(f)
+    _need(psi, n, "psi [nlocal]"); _need(f, n, "f [nlocal]")
+    if _f64(psi) is not psi:
+        raise ValueError("psi is updated in place: pass a contiguous float64 array")
+    _check(lib().isph_solve_poisson_boltzmann(ctx.h, J.h, C.byref(prm), _ptr(f), _ptr(psi), C.byref(info),
+                                              _on_device(psi, f)))
+    return info
 
 
 def assemble_block_helmholtz(ctx, parts, colmap, dt, theta, beta, nu, rho, pres, force, g, vel, normal=None, antisym=True,

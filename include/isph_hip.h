@@ -557,6 +557,58 @@ int isph_prec_amg_info(isph_ctx *ctx, const isph_prec *M, int level, long long i
 int isph_prec_amg_export(isph_ctx *ctx, const isph_prec *M, int level, int what, int *rowptr, int *colidx, double *val);
 int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *agg);
 
+/* ---- nonlinear Poisson-Boltzmann: PairISPH::computePoissonBoltzmann (ref: pair_isph.cpp:573-600, every step when
+ * enabled, :1312-1313) and the NOX solve it drives through SolverNOX_Stratimikos (pair_isph.h:78).
+ *   F_i = (-div(eps grad psi))_i + kappa^2 g(psi_i) + f_i  on the rows of kind Fluid, BufferDirichlet, BufferNeumann
+ *         (exact kind match, functor_poisson_boltzmann_f.h:40-86, pair_isph_corrected.cpp:439-484); the Laplacian is the
+ *         corrected (antisym = 0) or AntiSymmetric family with FilterBinary(Fluid, All), the MorrisHolmes mirror when
+ *         P->morris_holmes is set (FunctorPoissonBoltzmannF_MorrisHolmes);
+ *   F_i = psi0_i - psi_i                                  on the rows of kind Solid and Boundary;
+ *   g(psi) = sinh(psi) / (1 + 2 gamma sinh^2(psi/2)), linearized: psi / (1 + 2 gamma (psi/2)^2);
+ *   f = the per-particle "Extra F" (functor_poisson_boltzmann_extra_f.h), added on every row whose kind has no bit of
+ *       Solid (:79-81) -- Boundary rows included.  Any other row kind is an error.
+ * J (functor_poisson_boltzmann_jacobian.h:38-108) = the Laplacian built once by isph_assemble_poisson_boltzmann (the
+ * reference's A.is_filled), whose diagonal isph_pb_jacobian replaces: L_ii + kappa^2 g'(psi_i) on the Fluid-like rows
+ * (the closed forms of :86-97), -1 on the Solid / Boundary rows, which hold no other (nonzero) entry.
+ * Vectors cross this boundary in the caller's numbering with nlocal entries, as in isph_solve; ghost values of psi come
+ * from the matrix' halo inside the SpMV.  The forward comm of psi after the solve (pair_isph.cpp:595-597) stays with
+ * the caller (isph_halo_forward).  Non-convergence is reported in info, never an error.  With more than one rank the
+ * residual, the solve and the preconditioner set-up are COLLECTIVE. */
+typedef struct {
+  double kappasq;           /* 2 ezcb / psiref (pair_isph.cpp:1680-1698; default 1)                         */
+  double gamma;             /* steric "gamma" (0)                                                           */
+  int linearized;           /* "linearized" (0)                                                             */
+  int max_iters;            /* NOX::StatusTest::MaxIters (100)                                              */
+  double f_tol;             /* NOX::StatusTest::NormF, unscaled 2-norm (1e-8)                               */
+  double update_tol;        /* NOX::StatusTest::NormUpdate, unscaled 2-norm (1e-5); not met before step 1    */
+  int prec_max_age;         /* "Preconditioner Reuse Policy" Reuse, "Max Age Of Prec" (10); 1 = every step   */
+  int prec_kind;            /* 0 SA-AMG (ML in the reference's list), 1 block-Jacobi ILU(0)                 */
+  isph_amg_params amg;      /* isph_amg_params_default                                                      */
+  isph_solver_params linear;/* Block GMRES (flexible, right preconditioning), tol 1e-6, 80 iterations       */
+} isph_pb_params;
+void isph_pb_params_default(isph_pb_params *p);
+typedef struct {
+  int status;               /* 1 converged, 0 MaxIters, -1 non-finite ||F|| (NOX FiniteValue)               */
+  int newton_iters, linear_iters, prec_builds;
+  double norm_f, norm_update, ms;
+} isph_pb_info;
+/* The Laplacian part of J, Laplacian(-1, eps) (FunctorOuterPoissonBoltzmannJacobian::enterFor, :47-68), -1 unit rows on
+ * Solid / Boundary particles; psi0 [nall] the Dirichlet values (NULL: 0), eps [nall] the dielectric coefficient (NULL:
+ * 1).  The matrix keeps its row classes, psi0, the positions of its diagonal entries and L_ii. */
+int isph_assemble_poisson_boltzmann(isph_ctx *ctx, const isph_particles *P, int antisym, const double *eps /*[h|d]*/,
+                                    const double *psi0 /*[h|d]*/, int ncol, isph_mat **J_out, int on_device);
+/* computeF: F_out [nlocal] at psi [nlocal]; f [nlocal] or NULL.  Independent of the diagonal J holds. */
+int isph_pb_residual(isph_ctx *ctx, const isph_mat *J, const isph_pb_params *prm, const double *psi, const double *f,
+                     double *F_out, int on_device);
+/* computeJacobian: J's diagonal at psi [nlocal], written in place */
+int isph_pb_jacobian(isph_ctx *ctx, isph_mat *J, const isph_pb_params *prm, const double *psi, int on_device);
+/* solveProblem: Newton from the caller's psi [nlocal] (the initial guess; updated in place), full step, constant forcing
+ * term, FGMRES from x0 = 0 on J delta = -F with the preconditioner of prec_kind rebuilt when its age reaches
+ * prec_max_age; stop on FiniteValue OR MaxIters OR (NormF AND NormUpdate) (solver_nox_impl.h:78-145,
+ * solver_nox_stratimikos.h:84-122).  prm NULL: isph_pb_params_default. */
+int isph_solve_poisson_boltzmann(isph_ctx *ctx, isph_mat *J, const isph_pb_params *prm, const double *f, double *psi,
+                                 isph_pb_info *info, int on_device);
+
 /* Particle shifting (fix isph/shift -> PairISPH_Corrected::shiftParticles, pair_isph_corrected.cpp:1203-1262).
  * isph_compute_shift replaces FunctorOuterComputeShift (functor_compute_shift.h:48-113): dr[nlocal][3] for the fluid
  * particles, pairs inside min(cutsq, shiftcut^2), alpha = shift*dt*vmax.
