@@ -138,20 +138,25 @@ __global__ void k_order_soa_to_aos(int n, const double *__restrict__ x, const do
   out[3 * (size_t)i + 2] = z ? z[i] : 0.0;
 }
 
-// per-workgroup bounding box of x[0..n)[0..3): part[block][0..3) = min, [3..6) = max
+// min / max that keep a NaN: fmin / fmax drop it, and a NaN coordinate would then pass the host's finiteness check of the
+// box and land in cell 0
+__device__ inline double order_nanmin(double a, double b) { return (isnan(a) || isnan(b)) ? a + b : fmin(a, b); }
+__device__ inline double order_nanmax(double a, double b) { return (isnan(a) || isnan(b)) ? a + b : fmax(a, b); }
+
+// per-workgroup bounding box of x[0..n)[0..3): part[block][0..3) = min, [3..6) = max (NaN when a coordinate is NaN)
 __global__ __launch_bounds__(kBlock) void k_order_bbox(int n, OrderGeom g, const double *__restrict__ x, double *__restrict__ part) {
   __shared__ double red[kBlock / 64][6];
   double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
     for (int a = 0; a < 3; ++a) {
       const double v = order_coord(g, a, x[3 * (size_t)i + a]);
-      mn[a] = fmin(mn[a], v);
-      mx[a] = fmax(mx[a], v);
+      mn[a] = order_nanmin(mn[a], v);
+      mx[a] = order_nanmax(mx[a], v);
     }
   for (int a = 0; a < 3; ++a)
     for (int o = 32; o > 0; o >>= 1) {
-      mn[a] = fmin(mn[a], __shfl_xor(mn[a], o, 64));
-      mx[a] = fmax(mx[a], __shfl_xor(mx[a], o, 64));
+      mn[a] = order_nanmin(mn[a], __shfl_xor(mn[a], o, 64));
+      mx[a] = order_nanmax(mx[a], __shfl_xor(mx[a], o, 64));
     }
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0)
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(kBlock) void k_order_bbox(int n, OrderGeom g, const
   __syncthreads();
   if (threadIdx.x < 6) {
     double v = red[0][threadIdx.x];
-    for (int w = 1; w < kBlock / 64; ++w) v = threadIdx.x < 3 ? fmin(v, red[w][threadIdx.x]) : fmax(v, red[w][threadIdx.x]);
+    for (int w = 1; w < kBlock / 64; ++w) v = threadIdx.x < 3 ? order_nanmin(v, red[w][threadIdx.x]) : order_nanmax(v, red[w][threadIdx.x]);
     part[(size_t)blockIdx.x * 6 + threadIdx.x] = v;
   }
 }
@@ -395,9 +400,9 @@ inline int order_build(hipStream_t st, int dim, int n, const double *x, RowOrder
   ISPH_CHECK_HIP(hipMemcpyAsync(hp.data(), part.p, sizeof(double) * hp.size(), hipMemcpyDeviceToHost, st));
   ISPH_CHECK_HIP(hipStreamSynchronize(st));
   double mn[3] = {1e300, 1e300, 1e300}, mx[3] = {-1e300, -1e300, -1e300};
+  for (size_t k = 0; k < hp.size(); ++k) ISPH_REQUIRE(std::isfinite(hp[k]), "particle positions are not finite");   // std::min drops a NaN
   for (int b = 0; b < gb; ++b)
     for (int a = 0; a < 3; ++a) { mn[a] = std::min(mn[a], hp[(size_t)b * 6 + a]); mx[a] = std::max(mx[a], hp[(size_t)b * 6 + 3 + a]); }
-  for (int a = 0; a < 3; ++a) ISPH_REQUIRE(std::isfinite(mn[a]) && std::isfinite(mx[a]), "particle positions are not finite");
   order_geometry(dim, n, mn, mx, O->g);
   // 1b. cell faces = quantiles of the coordinates, from one histogram per axis
   {

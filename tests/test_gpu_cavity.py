@@ -2,6 +2,8 @@
 closed box, solid walls with normals, moving lid; block Helmholtz (functor_incomp_navier_stokes_block_helmholtz.h) ->
 solveBlockProblem, then the pressure Poisson system with wall Neumann rows and the null-space mask.
 Oracle parity at 16^3 sites, size-independent properties at the configuration's 2 M particles."""
+import time
+
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -152,6 +154,8 @@ def test_wall_bounded_poisson_every_singular_mode_and_preconditioner(gpu_ctx, si
 def test_cavity_config3_full_size_properties(gpu_ctx):
     """126^3 = 2 000 376 particles (114^3 fluid + 6 wall layers, the .m script's nn = 6): the 3x3 block Helmholtz system
     and the pressure Poisson system of one time step, assembled and solved on the device with torch-resident arrays.
+    Entries: 16 804 rows (fluid, wall and lid) of all nine blocks, of b and of a Poisson system with the wall Neumann rows
+    against the oracle's row window (tests/row_window.py), values 1e-12.
     Properties: all nine blocks exist on the scalar pattern, block residual <= 2e-8 re-computed
     block by block with independent SpMV calls, the lid drags the fluid (+x velocity under the lid), solid rows keep
     their velocity; Poisson: converged, residual <= 2e-8, pressure orthogonal to the masked null vector."""
@@ -177,6 +181,30 @@ def test_cavity_config3_full_size_properties(gpu_ctx):
     blocks, b = hip.assemble_block_helmholtz(gpu_ctx, dp, colmap, p["dt"], THETA, BETA, nu, rho, pres, force, np.zeros(3),
                                              vel, normal=nrm, vfrac=vfrac, Gc=Gc, kinds=p["kinds"])
     assert all(blocks[i][j] is not None for i in range(3) for j in range(3))
+    # ---- entries: 256 runs of 64 rows of all nine blocks and of b against the oracle's row window (tests/row_window.py)
+    import row_window as rw
+    typ_h = p["type"][:n]
+    rng = np.random.default_rng(12)
+    lid = np.flatnonzero(typ_h == 3)
+    wall_n = np.flatnonzero((typ_h == 2) & (np.abs(p["normal"][:n]).sum(axis=1) > 0))
+    rows = rw.runs(n, 240, 64, seed=3, starts=np.r_[rng.choice(lid, 8), rng.choice(wall_n, 8), rng.choice(np.flatnonzero(typ_h == 1), 8)])
+    assert len(rows) >= 16384 and all(np.any(typ_h[rows] == t) for t in (1, 2, 3))
+    zeros_h = np.zeros((nall, 3))
+    t0 = time.perf_counter()
+    win, Pw, (wrp, wci, wvals, wb) = rw.block_helmholtz(p, colmap_h, rows, p["dt"], THETA, BETA, p["nu"], p["rho"],
+                                                         np.zeros(nall), zeros_h, np.zeros(3), p["v"], normal=p["normal"],
+                                                         kinds=p["kinds"])
+    t_orc = time.perf_counter() - t0
+    k = win.nrows
+    assert np.max(np.abs(vf.cpu().numpy()[rows] - Pw.vfrac[:k]) / Pw.vfrac[:k]) < 1e-13
+    scale = np.abs(wvals).max()
+    errs = [rw.assert_rows_match(rw.device_rows(blocks[ib][jb], rows), (wrp, wci, wvals[ib * dim + jb]), 1e-12, scale)
+            for ib in range(dim) for jb in range(dim)]
+    bh = b.cpu().numpy().reshape(dim, n)[:, rows]
+    db = np.max(np.abs(bh - wb)) / np.abs(wb).max()
+    print("config3 block Helmholtz, %d window rows: oracle %.1f s, max|dval|/max|val| %.3g, max|db|/max|b| %.3g"
+          % (k, t_orc, max(errs), db))
+    assert db <= 1e-12
     x = vel[:n].t().contiguous().reshape(-1).clone()
     M = hip.Precond(gpu_ctx, blocks[0][0], "bjacobi-ilu0", 512)
     bw = b.clone()
@@ -228,3 +256,23 @@ def test_cavity_config3_full_size_properties(gpu_ctx):
         r -= (r @ q) * q
     assert float(r.norm() / bpw.norm()) < 2e-8
     assert abs(float(xp @ nvec)) < 1e-10 * float(xp.abs().max())
+    del A, bp, bpw, xp, M, blocks
+    torch.cuda.empty_cache()
+    # ---- entries of the pressure system with the wall Neumann rows, for a velocity defined on the host (the oracle gets
+    # nothing the device computed)
+    vs_h = np.zeros((nall, 3))
+    vs_h[:n] = 0.1 * np.random.default_rng(13).standard_normal((n, 3)) * (typ_h[:, None] == 1)
+    vs_h = np.ascontiguousarray(vs_h[colmap_h])
+    A2, b2 = hip.assemble_poisson(gpu_ctx, dp, colmap, p["dt"], rho, t(vs_h), vfrac=vfrac, Gc=Gc, kinds=p["kinds"],
+                                  normal=nrm)
+    t0 = time.perf_counter()
+    win, Pw, (wrp, wci, wv, wb) = rw.poisson(p, colmap_h, rows, p["dt"], p["rho"], vs_h, kinds=p["kinds"], normal=p["normal"])
+    t_orc = time.perf_counter() - t0
+    skip = rows != int(np.flatnonzero(typ_h == 1)[0])                  # the first fluid row (rank0 edit)
+    dval = rw.assert_rows_match(rw.rows_of(*rw.device_rows(A2, rows), np.flatnonzero(skip)),
+                                rw.rows_of(wrp, wci, wv, np.flatnonzero(skip)), 1e-12)
+    db = np.max(np.abs(b2.cpu().numpy()[rows] - wb)[skip]) / np.abs(wb).max()
+    print("config3 Poisson + wall Neumann rows, %d window rows: oracle %.1f s, max|dval|/max|val| %.3g, max|db|/max|b| %.3g"
+          % (win.nrows, t_orc, dval, db))
+    assert db <= 1e-12
+    A2.close()

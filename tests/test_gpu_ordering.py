@@ -446,3 +446,21 @@ def test_cpp_mirror_with_coordinates(gpu_ctx, tmp_path):
     assert abs(its[0] - io.iters) <= 1, (its, io.iters)
     assert np.linalg.norm(x - xo) / np.linalg.norm(xo) <= 1e-6
     assert "library's bricks" in r.stdout
+
+
+def test_nan_position_is_refused_by_the_brick_ordering(octx):
+    """A NaN coordinate must not pass the ordering's bounding-box guard: fmin / fmax drop NaN, so the box stayed finite,
+    the particle was binned into cell 0 and the assembly succeeded with NaN entries.  The reduction now keeps NaN and the
+    assembly is refused with an error that names the positions (a host-side check of the reduced box)."""
+    pr = Problem(tgv_spec(dim=3, n=12, mode=workload.JITTER))
+    p = dict(pr.parts)
+    x = p["x"].copy()
+    x[pr.n // 2, 1] = np.nan                                    # one owned particle, the middle of the list
+    p["x"] = x
+    with pytest.raises(hip.IsphError, match="positions"):
+        hip.assemble_poisson(octx, p, pr.colmap, pr.spec.dt, p["rho"], np.ascontiguousarray(p["v"]), vfrac=pr.P.vfrac)
+    # the same particles with finite positions still assemble
+    A, _ = hip.assemble_poisson(octx, pr.parts, pr.colmap, pr.spec.dt, pr.parts["rho"], np.ascontiguousarray(pr.parts["v"]),
+                                vfrac=pr.P.vfrac)
+    assert A.info()["nrow"] == pr.n
+    A.close()

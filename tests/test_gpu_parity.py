@@ -1,6 +1,8 @@
 """-m gpu: parity of the HIP path (through the C ABI) against the CPU oracle on
 seeded TGV problems.  Tolerances are stated per test; integer/index work
 (sparsity pattern) must match exactly."""
+import time
+
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -263,8 +265,9 @@ def test_full_size_properties(gpu_ctx):
 def test_config1_full_size_100cubed(gpu_ctx_bricks):
     """BASELINE configs[1] at its full size and in bench.py's own configuration: 3-D TGV, 100^3 = 1 M particles handed over
     in lexicographic atom order (create_atoms on the lattice), the library numbering the rows itself (its 10 x 10 x 5
-    bricks = the block-Jacobi subdomains), FGMRES(50) + block ILU(0) rebuilt per solve -- against the ORACLE on the same
-    system (solver_lin_belos.h:130-222): the oracle is handed the library's permutation and subdomain table, factors and
+    bricks = the block-Jacobi subdomains), FGMRES(50) + block ILU(0) rebuilt per solve.  Every entry of the exported
+    matrix, b and the volumes against the oracle's own assembly of the whole system (pattern exact, values 1e-12).  Then,
+    against the ORACLE on the same system (solver_lin_belos.h:130-222): the oracle is handed the library's permutation and subdomain table, factors and
     solves P A P^T (1-2 s on the host cores): iterations +-1, ||x_gpu - x_cpu|| / ||x_cpu|| <= 1e-6, the ILU factor of
     200 sampled subdomains <= 1e-10 with the pattern exact.  Kept from the earlier rounds, the size-independent properties:
     zero row sums, b orthogonal to the null vector after projection, x . n = 0, the residual re-computed on the host with
@@ -284,6 +287,19 @@ def test_config1_full_size_100cubed(gpu_ctx_bricks):
     assert info_m["nrow"] == n and 100 < info_m["nnz"] / n < 108
     rp, ci, v = A.export_csr()                                          # the caller's numbering
     assert np.max(np.abs(A.spmv(np.ones(n)))) < 1e-11 * np.abs(v).max()
+    # ---- every entry against the oracle's own assembly of the whole system (volumes included)
+    t0 = time.perf_counter()
+    P = orc.Particles(p, colmap)
+    P.precompute(corrections=False)
+    rpo, cio, vo, bo = P.poisson(sp.dt, p["rho"], np.ascontiguousarray(p["v"]))
+    t_orc = time.perf_counter() - t0
+    assert np.max(np.abs(vf - P.vfrac[:n]) / P.vfrac[:n]) < 1e-13
+    assert np.array_equal(rp, rpo) and np.array_equal(ci, cio)          # pattern: exact
+    dval = np.max(np.abs(v - vo)) / np.abs(vo).max()
+    db = np.max(np.abs(b - bo)) / max(np.abs(bo).max(), sp.umax / sp.h)
+    print("config1 AntiSymmetric, all %d rows: oracle %.1f s, max|dval|/max|val| %.3g, max|db|/scale %.3g" % (n, t_orc, dval, db))
+    assert dval <= 1e-12 and db <= 1e-12
+    del P, rpo, cio, vo, bo
     o = A.ordering()
     sizes = np.diff(o["block_ptr"])
     assert len(sizes) == 2000 and sizes.min() == sizes.max() == 500     # 10 x 10 x 5 bricks tile the lattice
@@ -323,6 +339,45 @@ def test_config1_full_size_100cubed(gpu_ctx_bricks):
     assert ij.converged == 1
     assert np.linalg.norm(x - xj) / np.linalg.norm(xj) < 1e-6
     A.close()
+
+
+def test_config1_symmetric_rows_match_the_oracle_window(gpu_ctx_bricks):
+    """configs[1] at 100^3 with the Symmetric (corrected) operator family, the whole chain on the device: volumes, G_i and
+    L_i, then the Poisson rows and right-hand side, in the library's own row numbering.  At least 2^16 rows -- 1040 runs
+    of 64 consecutive rows spread over the lattice plus the first and last 512 -- against the oracle's row window
+    (tests/row_window.py), which assembles exactly those rows bit for bit as the whole system would.  Tolerances of the
+    small Symmetric chain (test_gpu_corrections_match_oracle_and_feed_assembly): V 1e-13, G 1e-11, L 1e-9 (6x6 LU pivot
+    order), values 1e-9 (they carry L); b 1e-12 of max(|b|, umax/h) (it carries G only)."""
+    import row_window as rw
+    ctx = gpu_ctx_bricks
+    sp = workload.TGVSpec(dim=3, ncell=(100, 100, 100), brick=(100, 100, 100), mode=workload.ADVECT)
+    p = workload.make_tgv(sp)
+    colmap = workload.single_rank_colmap(p)
+    n = p["nlocal"]
+    own = p["owner_index"]
+    vf = hip.compute_volumes(ctx, p, colmap)
+    vfrac = np.ascontiguousarray(vf[own])
+    G, L = hip.compute_corrections(ctx, p, colmap, vfrac)
+    A, b = hip.assemble_poisson(ctx, p, colmap, sp.dt, p["rho"], np.ascontiguousarray(p["v"]), antisym=False, vfrac=vfrac,
+                                Gc=np.ascontiguousarray(G[own]), Lc=np.ascontiguousarray(L[own]))
+    rp, ci, v = A.export_csr()
+    A.close()
+    rows = np.unique(np.r_[rw.runs(n, 1040, 64, seed=1), np.arange(512), np.arange(n - 512, n)])
+    assert len(rows) >= 2 ** 16
+    t0 = time.perf_counter()
+    win, P, (wrp, wci, wv, wb) = rw.poisson(p, colmap, rows, sp.dt, p["rho"], p["v"], antisym=False)
+    t_orc = time.perf_counter() - t0
+    k = win.nrows
+    assert np.max(np.abs(vf[rows] - P.vfrac[:k]) / P.vfrac[:k]) < 1e-13
+    assert np.max(np.abs(G[rows] - P.Gc[:k])) < 1e-11 * np.abs(P.Gc[:k]).max()
+    assert np.max(np.abs(L[rows] - P.Lc[:k])) < 1e-9 * np.abs(P.Lc[:k]).max()
+    skip = rows != 0                                                    # row 0: the first fluid row (rank0 edit)
+    dev = rw.rows_of(rp, ci, v, rows[skip])
+    dval = rw.assert_rows_match(dev, rw.rows_of(wrp, wci, wv, np.flatnonzero(skip)), 1e-9)
+    db = np.max(np.abs(b[rows] - wb)[skip]) / max(np.abs(wb).max(), sp.umax / sp.h)
+    print("config1 Symmetric, %d window rows (%d window particles): oracle %.1f s, max|dval|/max|val| %.3g, "
+          "max|db|/scale %.3g" % (k, win.parts["nlocal"], t_orc, dval, db))
+    assert db <= 1e-12
 
 
 def test_neigh_ptr64_gives_the_same_system(gpu_ctx):

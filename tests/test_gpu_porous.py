@@ -1,8 +1,10 @@
 """-m gpu: BASELINE configs[4] -- pore-scale flow through a bead pack in a cylinder (sph-script/pore-scale-flow-3d.lmp,
 compute_isph_cylinder_porous.cpp:195-224): bcc lattice, Quintic kernel cut 3h (749 entries per row), MorrisHolmes
 boundary, NotSingular Poisson, SA-AMG preconditioner.  Oracle parity on a 43 904-particle cylinder, size-independent
-properties on 1.02 M particles (767 M matrix entries), on 2.96 M particles (2.22e9 entries: 64-bit offsets) and at the
+properties and oracle row windows on 1.02 M particles (767 M matrix entries), on 2.96 M particles (2.22e9 entries: 64-bit offsets) and at the
 configuration's own size, 4.0 M particles (3.0e9 entries, 36 GB of sliced-ELL on one GPU)."""
+import time
+
 import numpy as np
 import pytest
 import scipy.sparse as sps
@@ -62,7 +64,8 @@ def test_porous_config4_properties_at_size(gpu_ctx, nc, reference_beads):
     nc = 112 with the reference's own bead pack (tests/golden/pore_scale_flow_bead_centeroids_3d.npz = the script's
     pore-scale-flow-bead-centeroids-3d.dat: 3807 beads in the middle half of a cylinder of aspect ratio 1.634):
     2 x 112 x 168 x 112 = 4 214 784 particles, 3.16e9 entries -- BASELINE configs[4] at its own size on ONE GPU.
-    Assembled on the device from torch-resident arrays and solved with FGMRES + SA-AMG.  Properties: row length of the
+    Assembled on the device from torch-resident arrays and solved with FGMRES + SA-AMG.  Entries: 4 224 rows, b and
+    volumes against the oracle's row window (tests/row_window.py).  Properties: row length of the
     bcc/Quintic stencil, solid rows are identity rows, the solve converges, residual <= 2e-8 re-computed with an
     independent SpMV, zero pressure on the solid rows."""
     import torch
@@ -88,6 +91,43 @@ def test_porous_config4_properties_at_size(gpu_ctx, nc, reference_beads):
     vf = hip.compute_volumes(gpu_ctx, dp, colmap, kernel="quintic")
     vfrac = vf[own].contiguous()
     pnd = (1.0 / vfrac).contiguous()
+    # ---- entries: 4 096 rows (64 runs of 64, the last 512 rows among them) against the oracle's row window
+    # (tests/row_window.py; pnd = 1/V from the oracle's own volumes).  With 64-bit list offsets at least half of the rows
+    # lie where neigh_ptr >= 2^31: their list entries and sliced-ELL offsets are beyond 2^31.  The right-hand side is
+    # checked for a seeded random velocity: the smooth divergence-free field of the solve below gives interior rows that
+    # are round-off of cancelling O(umax/h) terms, where one-ulp differences of the two sides' own volumes reach 1e-12 of
+    # max|b| at nc = 114; a random field has no such cancellation, and a wrong neighbour moves b at O(1).
+    import row_window as rw
+    nptr = p["neigh_ptr"]
+    wide = nptr.dtype == np.int64
+    hi = int(np.searchsorted(nptr, 2 ** 31)) if wide else n
+    rows = rw.runs(n, 26 if wide else 58, 64, seed=nc, starts=n - np.arange(64, 513, 64))
+    if wide:
+        assert hi < n - 4096
+        rows = np.union1d(rows, hi + rw.runs(n - hi, 32, 64, seed=nc + 1))
+        assert np.mean(nptr[rows] >= 2 ** 31) >= 0.5
+    assert len(rows) >= 4096 and np.all(np.isin(np.arange(n - 512, n), rows))
+    vr = np.zeros((nall, 3))
+    vr[:n] = 1e-3 * np.random.default_rng(nc).standard_normal((n, 3)) * (p["type"][:n, None] <= 2)
+    vr = np.ascontiguousarray(vr[colmap_h])
+    Ar, br = hip.assemble_poisson(gpu_ctx, dp, colmap, p["dt"], rho, torch.from_numpy(vr).to(dev), singular=hip.NOT_SINGULAR,
+                                  vfrac=vfrac, kernel="quintic", kinds=p["kinds"], pnd=pnd)
+    t0 = time.perf_counter()
+    win, Pw, (wrp, wci, wv, wb) = rw.poisson(p, colmap_h, rows, p["dt"], p["rho"], vr, kernel="quintic", kinds=p["kinds"],
+                                             singular=orc.NOT_SINGULAR, morris=1, pnd_from_volumes=True)
+    t_orc = time.perf_counter() - t0
+    k = win.nrows
+    rows_d = torch.from_numpy(rows).to(dev)
+    dvf = np.max(np.abs(vf[rows_d].cpu().numpy() - Pw.vfrac[:k]) / Pw.vfrac[:k])
+    dval = rw.assert_rows_match(rw.device_rows(Ar, rows), (wrp, wci, wv), 1e-12)
+    db = np.max(np.abs(br[rows_d].cpu().numpy() - wb)) / np.abs(wb).max()
+    print("config4 nc=%d, %d window rows (%d past 2^31 list offsets, %d window particles): oracle %.1f s, "
+          "max|dval|/max|val| %.3g, max|db|/max|b| %.3g, max|dV|/V %.3g" % (nc, k, int(np.sum(nptr[rows] >= 2 ** 31)),
+                                                                         win.parts["nlocal"], t_orc, dval, db, dvf))
+    assert dvf < 1e-13 and db <= 1e-12
+    Ar.close()
+    del win, Pw, wrp, wci, wv, wb, Ar, br
+    torch.cuda.empty_cache()
     x = dp["x"]
     fluid = (dp["type"] <= 2).to(torch.float64)
     vstar = torch.zeros((nall, 3), dtype=torch.float64, device=dev)
