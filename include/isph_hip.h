@@ -296,7 +296,8 @@ typedef struct {
   double spmv_ms;           /* sum of SpMV kernel times (profile mode only) */
   int spmv_calls;
   int reorth;               /* Gram-Schmidt steps whose second pass was applied (DGKS: when the norm dropped below
-                               1/sqrt(2) of its value before the first pass; ICGS: every step) */
+                               1/sqrt(2) of its value before the first pass; ICGS: every step), summed over the
+                               right-hand sides.  IMGS always sweeps twice and is not counted: 0, as for CG */
 } isph_solve_info;
 
 /* Replaces SolverLin_Belos::solveProblem (ref: solver_lin_belos.h:130-222):
