@@ -12,6 +12,7 @@ import scipy.sparse as sps
 from isph_amd import hip, workload
 import oracle as orc
 
+from amg_levels import compare_levels
 from sampled_check import assert_spmv_matches_host_on_sampled_rows
 
 pytestmark = pytest.mark.gpu
@@ -48,7 +49,11 @@ def test_porous_small_matches_oracle(gpu_ctx):
     prm = hip.AmgParams(block=512, coarse_max=128)
     M = hip.PrecondAMG(gpu_ctx, A, params=prm)
     G = orc.AMG(rp, ci, val, block=512, coarse_max=128)
-    assert M.levels == G.levels
+    assert M.levels == G.levels >= 2
+    compare_levels(M, G)                                              # the whole hierarchy entry by entry, then one V cycle
+    r = np.random.default_rng(28).standard_normal(n)
+    zo, zg = G.apply(r), M.apply(r)
+    assert np.linalg.norm(zg - zo) <= 1e-9 * np.linalg.norm(zo)
     x = np.zeros(n)
     info = hip.solve(gpu_ctx, A, bg.copy(), x, prec=M, singular=False)
     xo, io, _ = orc.solve(rp, ci, val, b, singular=False, prec="amg", amg=G)
