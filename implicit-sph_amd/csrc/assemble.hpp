@@ -304,6 +304,56 @@ __global__ void k_pnd(AsmTables T, int nlocal, const double *__restrict__ x, con
   pnd[i] = w + kernel_val(T.kernel, 0.0, T.hinv[it * nt1 + it], T.knorm[it * nt1 + it]);
 }
 
+// The whole of FunctorOuterNormal (functor_normal.h:57-133) in the same neighbour sweep: the neighbours k_pnd leaves out
+// -- those of the opposite kind -- are exactly the ones that build the wall normal,
+//   n_i = orient_i sum_j (G_i^T r_ij) W'/r V_j,   orient = -1 on Fluid / buffer particles, +1 on Solid ones
+// (pair_isph_corrected.cpp:381-386), divided by its length unless that is exactly 0.  The reference runs the functor
+// twice, filters (Fluid, Solid) and (Solid, Fluid); a pass returns before its store for a particle whose kind fails the
+// filter, so the two passes write disjoint particles and are one sweep here.  The pnd sum is k_pnd's, add for add.
+template <int DIM>
+__global__ __launch_bounds__(kBlock) void k_normals(AsmTables T, int nlocal, const double *__restrict__ x,
+                                                    const int *__restrict__ type, const double *__restrict__ vfrac,
+                                                    const double *__restrict__ Gc, double *__restrict__ normal,
+                                                    double *__restrict__ pnd) {
+  const int i = xcd_block() * blockDim.x + threadIdx.x;
+  if (i >= nlocal) return;
+  const int it = type[i], nt1 = T.ntypes + 1, ikind = T.kind[it];
+  double nrm[3] = {0, 0, 0}, w = 0.0;
+  if (ikind & (KIND_FLUID | KIND_SOLID)) {
+    const int opposite = (ikind & KIND_SOLID) ? KIND_FLUID : KIND_SOLID;
+    const double orient = (ikind & KIND_SOLID) ? 1.0 : -1.0;
+    double G[DIM * DIM];
+    for (int k = 0; k < DIM * DIM; ++k) G[k] = Gc[(size_t)i * DIM * DIM + k];
+    for (int jj = 0, nn_i = T.nlen[i]; jj < nn_i; ++jj) {
+      const int j = neigh_at(T, i, jj);
+      const int jt = type[j];
+      double rij[3];
+      const double rsq = pair_rsq(DIM, x, i, j, rij);
+      if (!(rsq < T.cutsq[it * nt1 + jt])) continue;
+      const double r = sqrt(rsq) + kEps;
+      if (T.kind[jt] & opposite) {
+        const double dwdr = kernel_dval(T.kernel, r, T.hinv[it * nt1 + jt], T.kdnorm[it * nt1 + jt]);
+        const double vjtmp = orient * dwdr / r * vfrac[j];
+        for (int k2 = 0; k2 < DIM; ++k2) {
+          double gitmp = 0.0;
+          for (int k1 = 0; k1 < DIM; ++k1) gitmp += G[k2 * DIM + k1] * rij[k1];
+          nrm[k2] += gitmp * vjtmp;
+        }
+      } else {
+        w += kernel_val(T.kernel, r, T.hinv[it * nt1 + jt], T.knorm[it * nt1 + jt]);
+      }
+    }
+    w += kernel_val(T.kernel, 0.0, T.hinv[it * nt1 + it], T.knorm[it * nt1 + it]);
+    double len = 0.0;
+    for (int k = 0; k < DIM; ++k) len += nrm[k] * nrm[k];
+    len = sqrt(len);
+    if (len != 0.0)
+      for (int k = 0; k < DIM; ++k) nrm[k] /= len;
+  }
+  for (int k = 0; k < 3; ++k) normal[3 * (size_t)i + k] = nrm[k];
+  if (pnd) pnd[i] = w;
+}
+
 
 // ---------------------------------------------------------------------------
 // computePre tensors of the Symmetric (consistent) family, one lane per particle.

@@ -2017,3 +2017,7 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 
 // the Poisson-Boltzmann Newton solve (isph_assemble_poisson_boltzmann, isph_pb_*, isph_solve_poisson_boltzmann)
 #include "poisson_boltzmann.hpp"
+
+// wall normals, continuum surface force, pairwise force (isph_compute_normals, isph_csf_*, isph_surface_tension_csf,
+// isph_pairwise_force)
+#include "surface_tension.hpp"

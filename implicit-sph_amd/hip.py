@@ -27,6 +27,7 @@ EXPORTS = [
     "isph_prec_amg_export", "isph_prec_amg_aggregates",
     "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
+    "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
 ]
 
 
@@ -243,12 +244,26 @@ def lib():
         L.isph_pb_jacobian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_solve_poisson_boltzmann.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_int]
+        L.isph_compute_normals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_csf_params_default.argtypes = [C.c_void_p]
+        L.isph_csf_params_default.restype = None
+        L.isph_csf_phase_normal.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int]
+        L.isph_csf_force.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_surface_tension_csf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_pairwise_force.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
 
 class IsphError(RuntimeError):
     pass
+
+
+class OperandError(IsphError, ValueError):
+    """an operand shorter than what the C ABI reads: refused by the binding before any library call"""
 
 
 def _check(rc):
@@ -817,7 +832,7 @@ def _need(a, count, what):
         return
     have = int(a.numel()) if _is_torch(a) else int(np.asarray(a).size)
     if have < count:
-        raise ValueError("%s: %d elements given, %d needed" % (what, have, count))
+        raise OperandError("%s: %d elements given, %d needed" % (what, have, count))
 
 
 def particles_view(parts, colmap, kernel="wendland", kinds=None, vfrac=None, Gc=None, Lc=None, keep=None,
@@ -1202,3 +1217,120 @@ def shift_particles(ctx, parts, colmap, shift, shiftcut, nonfluidweight, dt, x, 
     _check(lib().isph_shift_particles(ctx.h, C.byref(pv), int(antisym), _ptr(fx), float(shift), float(shiftcut),
                                       float(nonfluidweight), float(dt), _ptr(x), _ptr(v), _ptr(p), C.byref(vmax), dev))
     return vmax.value
+
+
+# ---- two-phase flow: wall normals and surface tension --------------------------------------------------------------
+
+CSF_COLORS = {"corrected": 0, "adami": 1}
+PAIRWISE_MODELS = {"tartakovsky-meakin": 0, "tartakovsky-panchenko-var1": 1, "tartakovsky-panchenko-var2": 2}
+
+
+class _CsfParams(C.Structure):
+    _fields_ = [("color", C.c_int), ("alpha", C.c_double), ("theta", C.c_double), ("epsilon", C.c_double),
+                ("kappa", C.c_double), ("phase", C.c_void_p)]
+
+
+class CsfParams:
+    """isph_csf_params == st.csf of the reference (pair_isph.cpp:1583-1586): color "corrected" | "adami", alpha, theta,
+    epsilon, kappa (defaults 1, 0, 0.01, 100) and phase, the phase of every particle type (phase[t - 1] for type t;
+    solids 0)."""
+
+    def __init__(self, phase, color="corrected", alpha=1.0, theta=0.0, epsilon=0.01, kappa=100.0):
+        self.phase = np.ascontiguousarray([0] + [int(q) for q in phase], dtype=np.int32)
+        self.color = CSF_COLORS[color] if isinstance(color, str) else int(color)
+        self.alpha, self.theta, self.epsilon, self.kappa = float(alpha), float(theta), float(epsilon), float(kappa)
+
+    def c_struct(self, ntypes):
+        """the C view; the phase table must cover the particle view's types"""
+        _need(self.phase, ntypes + 1, "phase [ntypes+1]")
+        return _CsfParams(self.color, self.alpha, self.theta, self.epsilon, self.kappa, _ptr(self.phase))
+
+
+def compute_normals(ctx, parts, colmap, vfrac, Gc, kernel="wendland", kinds=None, with_pnd=True):
+    """isph_compute_normals == PairISPH_Corrected::computeNormals (Solid walls): (normal [nlocal, 3], pnd [nlocal]) or
+    the normals alone with with_pnd=False."""
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, Gc=Gc, keep=keep, kinds=kinds)
+    if Gc is None or vfrac is None:
+        raise IsphError("compute_normals needs vfrac and Gc")
+    n = int(parts["nlocal"])
+    nrm = _out_like(dev, parts["x"], (n, 3))
+    pnd = _out_like(dev, parts["x"], (n,)) if with_pnd else None
+    _check(lib().isph_compute_normals(ctx.h, C.byref(pv), _ptr(nrm), _ptr(pnd), dev))
+    return (nrm, pnd) if with_pnd else nrm
+
+
+def _csf_view(parts, colmap, prm, vfrac, Gc, kernel, kinds, pnd, rho, wall_normal):
+    if Gc is None or vfrac is None:
+        raise IsphError("the continuum surface force needs vfrac and Gc")
+    if wall_normal is not None and pnd is None:
+        raise IsphError("the contact-angle correction needs pnd")
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, Gc=Gc, keep=keep, kinds=kinds, pnd=pnd)
+    rho = None if rho is None else _f64(rho)
+    wall_normal = None if wall_normal is None else _f64(wall_normal)
+    _same_side(dev, rho, wall_normal)
+    _need(rho, int(parts["nall"]), "rho [nall]")
+    _need(wall_normal, 3 * int(parts["nlocal"]), "wall_normal [nlocal][3]")
+    cp = prm.c_struct(pv.ntypes)
+    keep += [prm, cp, rho, wall_normal]
+    return pv, dev, keep, cp, rho, wall_normal
+
+
+def csf_phase_normal(ctx, parts, colmap, prm, vfrac, Gc, rho=None, wall_normal=None, pnd=None, kernel="wendland",
+                     kinds=None, with_grad=True):
+    """isph_csf_phase_normal: (grad [nlocal, 3] or None, nmag [nlocal, 4] = unit phase normal and |grad c|)."""
+    pv, dev, keep, cp, rho, wall_normal = _csf_view(parts, colmap, prm, vfrac, Gc, kernel, kinds, pnd, rho, wall_normal)
+    n = int(parts["nlocal"])
+    grad = _out_like(dev, parts["x"], (n, 3)) if with_grad else None
+    nmag = _out_like(dev, parts["x"], (n, 4))
+    _check(lib().isph_csf_phase_normal(ctx.h, C.byref(pv), C.byref(cp), _ptr(rho), _ptr(wall_normal), _ptr(grad),
+                                       _ptr(nmag), dev))
+    return grad, nmag
+
+
+def csf_force(ctx, parts, colmap, prm, vfrac, Gc, nmag, f, kernel="wendland", kinds=None, with_kappa=True):
+    """isph_csf_force: f [nlocal, 3] is incremented in place; nmag [nall, 4] with the ghost records filled.  Returns the
+    curvature [nlocal] (None with with_kappa=False)."""
+    pv, dev, keep, cp, _, _ = _csf_view(parts, colmap, prm, vfrac, Gc, kernel, kinds, None, None, None)
+    nmag = _f64(nmag)
+    _same_side(dev, nmag, f)
+    n = int(parts["nlocal"])
+    _need(nmag, 4 * int(parts["nall"]), "nmag [nall][4]"); _need(f, 3 * n, "f [nlocal][3]")
+    kap = _out_like(dev, parts["x"], (n,)) if with_kappa else None
+    _check(lib().isph_csf_force(ctx.h, C.byref(pv), C.byref(cp), _ptr(nmag), _ptr(f), _ptr(kap), dev))
+    return kap
+
+
+def surface_tension_csf(ctx, parts, colmap, prm, vfrac, Gc, f, rho=None, wall_normal=None, pnd=None, plan=None,
+                        kernel="wendland", kinds=None, with_nmag=False):
+    """isph_surface_tension_csf: both sweeps; f [nlocal, 3] incremented in place.  plan: a HaloForward for the off-rank
+    ghosts (None on one rank).  Returns nmag [nlocal, 4] with with_nmag=True."""
+    pv, dev, keep, cp, rho, wall_normal = _csf_view(parts, colmap, prm, vfrac, Gc, kernel, kinds, pnd, rho, wall_normal)
+    _same_side(dev, f)
+    n = int(parts["nlocal"])
+    _need(f, 3 * n, "f [nlocal][3]")
+    nmag = _out_like(dev, parts["x"], (n, 4)) if with_nmag else None
+    _check(lib().isph_surface_tension_csf(ctx.h, C.byref(pv), C.byref(cp), None if plan is None else plan.h, _ptr(rho),
+                                          _ptr(wall_normal), _ptr(f), _ptr(nmag), dev))
+    return nmag
+
+
+def pairwise_force(ctx, parts, colmap, model, phase, s, f, kernel="wendland", kinds=None):
+    """isph_pairwise_force: f [nlocal, 3] incremented in place; phase as in CsfParams; s [nphase, nphase].  Returns the
+    sum of the added forces (the functor's _f_sum)."""
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, keep=keep, kinds=kinds)
+    ph = np.ascontiguousarray([0] + [int(q) for q in phase], dtype=np.int32)
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1]:
+        raise OperandError("s must be [nphase][nphase]")
+    nphase = int(s.shape[0])
+    _same_side(dev, f)
+    _need(ph, pv.ntypes + 1, "phase [ntypes+1]"); _need(f, 3 * int(parts["nlocal"]), "f [nlocal][3]")
+    if ph.min() < 0 or ph.max() >= nphase:
+        raise OperandError("phase outside [0, nphase)")
+    fsum = np.zeros(3)
+    m = PAIRWISE_MODELS[model] if isinstance(model, str) else int(model)
+    _check(lib().isph_pairwise_force(ctx.h, C.byref(pv), m, _ptr(ph), _ptr(s), nphase, _ptr(f), _ptr(fsum), dev))
+    return fsum

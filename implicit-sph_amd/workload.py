@@ -189,7 +189,7 @@ def make_cavity(nfluid, wall=6, dim=3, pgrid=(1, 1, 1), rank=0, brick=(8, 8, 8),
     is [0, 2 pi).  Besides the arrays of make_tgv the dict carries
       kinds   [FLUID, SOLID, SOLID]  ("type:1 fluid:moving, type:2/3 solid:fixed", lid-driven-cavity.xml)
       normal  [nall][3] unit normals pointing into the fluid on the solid particles within the cut of the fluid
-              (the reference gets them from computeNormals, out of scope: they are an input here)
+              (written analytically here; hip.compute_normals is the reference's computeNormals on the device)
       dt      0.1 h / Umax (.lmp: tstep)
     wall must cover the cut (wall * dx >= cut) so the fluid never sees its periodic image."""
     ncell = nfluid + 2 * wall
@@ -325,3 +325,47 @@ def renumber(parts, order):
     out["neigh_idx"] = idmap[parts["neigh_idx"][src]].astype(np.int32)
     out["neigh_ptr"] = nptr2.astype(parts["neigh_ptr"].dtype)
     return out
+
+
+def make_droplet(N, dim=2, shape="square", rdrop=0.6, wall_layers=0, jitter=0.0, seed=42, pgrid=(1, 1, 1), rank=0,
+                 brick=(8, 8, 8), umax=0.5, nu=0.1, rho=1.0):
+    """Two-phase droplet of sph-script/square-droplet-{2d,3d}.lmp: a simple-cubic lattice of (2 N)^dim sites in a
+    periodic box (`lattice sq ${dx} origin 0.5 0.5 0`), h = 1.4 dx, Wendland kernel, cut = 3 h; the sites closer than
+    rdrop * N cells to the box centre along every axis (shape "square": the script's `region droplet block`, rdrop 0.3
+    in a box of half width 0.5 = 0.6 N cells) or in distance (shape "circle") are type 1, the others type 2, both
+    fluid, phases 1 / 2, rho = 1, nu = 0.1, dt = 0.4 dx / Umax.  In the generators' units: the periodic box is
+    [0, 2 pi)^dim.  Labels go by lattice site, so images carry their owner's label and jitter does not move the
+    interface.  jitter: largest displacement per axis in units of dx (seeded).
+
+    wall_layers > 0: sph-script/liquid-drop-on-solid-2d.lmp -- `wall_layers` (the script: 4) layers of solid particles
+    (type 3, phase 0, fixed) at the bottom and at the top of the y axis, the drop resting on the lower slab, cut = 2 h.
+    The script's hex lattice becomes the square lattice (+ jitter) of the other generators here, and the box stays the
+    periodic cube of 2 N cells, so the two slabs meet across the periodic boundary.
+
+    Besides the arrays of make_tgv the dict carries kinds (per type), phase (per type, phase[t - 1] of type t), dt."""
+    assert shape in ("square", "circle")
+    ncell = 2 * N
+    cut_over_h = 2.0 if wall_layers > 0 else 3.0
+    h_over_dx = 1.4
+    spec = TGVSpec(dim=dim, ncell=(ncell,) * dim, pgrid=pgrid, rank=rank, brick=tuple(brick)[:dim], origin=(0.5,) * dim,
+                   h_over_dx=h_over_dx, cut_over_h=cut_over_h, mode=JITTER if jitter > 0 else LATTICE,
+                   jitter_amp=jitter / h_over_dx, seed=seed, umax=umax, nu=nu, rho=rho)
+    assert ncell * spec.dx >= 2.0 * spec.cut, "box shorter than two cuts"
+    assert wall_layers == 0 or wall_layers * spec.dx >= spec.cut - 1e-12, "wall thinner than the kernel support"
+    p = make_tgv(spec)
+    tag0 = p["tag"].astype(np.int64) - 1
+    idx = np.stack([tag0 % ncell, (tag0 // ncell) % ncell, tag0 // (ncell * ncell)], axis=1)[:, :dim]   # lattice site
+    ctr = np.full(dim, N - 0.5)
+    half = rdrop * N
+    if wall_layers > 0:
+        ctr[1] = wall_layers + half - 0.5                      # the drop rests on the lower slab
+    d = idx - ctr
+    inner = np.all(np.abs(d) < half, axis=1) if shape == "square" else np.sum(d * d, axis=1) < half * half
+    typ = np.where(inner, 1, 2).astype(np.int32)
+    kinds, phase = [FLUID_KIND, FLUID_KIND], [1, 2]
+    if wall_layers > 0:
+        typ[(idx[:, 1] < wall_layers) | (idx[:, 1] >= ncell - wall_layers)] = 3
+        kinds, phase = kinds + [SOLID_KIND], phase + [0]
+    p.update(type=typ, v=np.zeros((p["nall"], 3)), kinds=kinds, phase=phase, dt=0.4 * spec.dx / umax, N=N,
+             site=idx, centre=(ctr + 0.5) * spec.dx, rdrop=half * spec.dx, wall_layers=wall_layers)
+    return p

@@ -627,6 +627,62 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
                          double shiftcut, double nonfluidweight, double dt, double *x, double *v, double *p,
                          double *vmax_out, int on_device);
 
+/* ---- two-phase flow: wall normals and surface tension ------------------- */
+
+/* PairISPH_Corrected::computeNormals for boundary_particle == Solid without use_part (ref: pair_isph_corrected.cpp:
+ * 374-425) -> Corrected::FunctorOuterNormal (functor_normal.h:57-133), both of its passes ((Fluid, Solid) and (Solid,
+ * Fluid), orientation -1 on Fluid / buffer particles and +1 on Solid ones, :381-386) in one neighbour sweep: unit
+ * normals normal_out [nlocal][3] (zero where a particle has no neighbour of the opposite kind, and on other kinds) and,
+ * when pnd_out is not NULL, the particle number density of isph_compute_pnd [nlocal].  Needs P->Gc and P->vfrac.
+ * Ghost values are the caller's forward comm.  bd_coord (functor_normal.h:138-191) and use_part are not provided. */
+int isph_compute_normals(isph_ctx *ctx, const isph_particles *P, double *normal_out, double *pnd_out, int on_device);
+
+/* st.csf of the reference: color 0 Corrected / 1 Adami ("Color Gradient", color.h:28-66), alpha, theta (contact
+ * angle of phase 1; pi - theta for the others), epsilon (in-phase volume-ratio cut-off), kappa; defaults 1, 0, 0.01,
+ * 100 (pair_isph.cpp:1583-1586).  phase: [ntypes+1] getParticlePhase(type) (pair_isph.cpp:169), host always,
+ * solids 0. */
+typedef struct {
+  int color;
+  double alpha, theta, epsilon, kappa;
+  const int *phase;
+} isph_csf_params;
+void isph_csf_params_default(isph_csf_params *p);
+
+/* PairISPH_Corrected::computeSurfaceTension_ContinuumSurfaceForce (ref: pair_isph_corrected.cpp:684-758) as two
+ * neighbour sweeps.  Both need P->Gc and P->vfrac and the filter (Fluid, Fluid).
+ *
+ * isph_csf_phase_normal = FunctorOuterPhaseGradient (functor_phase_gradient.h:49-141) + FunctorOuterNormalizeVector
+ * (functor_normalize_vector.h:29-41) + FunctorOuterCorrectPhaseNormal (functor_correct_phase_normal.h:43-95, only when
+ * wall_normal is given; reads P->pnd): nmag_out [nlocal][4] = {n_x, n_y, n_z, |grad c|} (32-byte aligned when on the
+ * device), grad_out [nlocal][3] the gradient before normalisation (may be NULL).  rho [nall] or NULL (= 1);
+ * wall_normal = pair->normal, owned rows read.
+ *
+ * isph_csf_force = FunctorOuterPhaseDivergence (functor_phase_divergence.h:41-98) + FunctorOuterContinuumSurfaceForce
+ * (functor_continuum_surface_force.h:52-64): nmag [nall][4] with the ghost records filled (the reference's forward
+ * comms of work3 / work), f_inout [nlocal][3] receives -= alpha (1 - exp(-kappa/|kappa_i|)) kappa_i n_i mag_i,
+ * kappa_out [nlocal] the curvature (may be NULL).  DEPARTURE: an active particle whose curvature is exactly 0 adds
+ * nothing; the reference computes alpha (1 - exp(+inf)) 0 = NaN there (:58-62), which on an exact lattice is a matter
+ * of summation order on every flat interface.
+ *
+ * isph_surface_tension_csf = both sweeps; ghost records are read through P->colmap (an image of an owned particle
+ * reads its owner), off-rank ghosts (colmap >= nlocal) through one isph_halo_forward of the records when plan is not
+ * NULL (with plan == NULL every ghost must be such an image).  nmag_out [nlocal][4] or NULL. */
+int isph_csf_phase_normal(isph_ctx *ctx, const isph_particles *P, const isph_csf_params *prm, const double *rho,
+                          const double *wall_normal, double *grad_out, double *nmag_out, int on_device);
+int isph_csf_force(isph_ctx *ctx, const isph_particles *P, const isph_csf_params *prm, const double *nmag,
+                   double *f_inout, double *kappa_out, int on_device);
+int isph_surface_tension_csf(isph_ctx *ctx, const isph_particles *P, const isph_csf_params *prm,
+                             const isph_halo_plan *plan, const double *rho, const double *wall_normal, double *f_inout,
+                             double *nmag_out, int on_device);
+
+/* PairISPH_Corrected::computeSurfaceTension_PairwiseForce (ref: pair_isph_corrected.cpp:760-784) ->
+ * FunctorOuterPairwiseForce (functor_pairwise_force.h:31-83), filter (Fluid, Fluid):
+ * f_i += sum_j -F(s[phase_i][phase_j], r, sqrt(cutsq)) r_ij / r with model 0 TartakovskyMeakin, 1 / 2
+ * TartakovskyPanchenko Var1 / Var2 (pairwise_force.h:38-118).  phase [ntypes+1] and s [nphase][nphase] are host
+ * arrays; f_sum (host, may be NULL) receives this rank's sum of the added forces, the functor's _f_sum. */
+int isph_pairwise_force(isph_ctx *ctx, const isph_particles *P, int model, const int *phase, const double *s,
+                        int nphase, double *f_inout, double f_sum[3], int on_device);
+
 #ifdef __cplusplus
 }
 #endif
