@@ -2021,3 +2021,7 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 // wall normals, continuum surface force, pairwise force (isph_compute_normals, isph_csf_*, isph_surface_tension_csf,
 // isph_pairwise_force)
 #include "surface_tension.hpp"
+
+// smoothed field, electrostatic body force, random stress (isph_smooth_field, isph_electrostatic_force, isph_random_stress_*,
+// isph_force_from_random_stress)
+#include "body_force.hpp"

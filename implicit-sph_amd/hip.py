@@ -28,6 +28,8 @@ EXPORTS = [
     "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
+    "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
+    "isph_force_from_random_stress",
 ]
 
 
@@ -254,6 +256,18 @@ def lib():
                                                C.c_void_p, C.c_void_p, C.c_int]
         L.isph_pairwise_force.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_int]
+        L.isph_smooth_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.isph_ek_params_default.argtypes = [C.c_void_p]
+        L.isph_ek_params_default.restype = None
+        L.isph_electrostatic_force.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_random_stress_tensor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong, C.c_ulonglong, C.c_void_p,
+                                                C.c_int]
+        L.isph_random_stress_force.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_force_from_random_stress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong,
+                                                    C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -1334,3 +1348,114 @@ def pairwise_force(ctx, parts, colmap, model, phase, s, f, kernel="wendland", ki
     m = PAIRWISE_MODELS[model] if isinstance(model, str) else int(model)
     _check(lib().isph_pairwise_force(ctx.h, C.byref(pv), m, _ptr(ph), _ptr(s), nphase, _ptr(f), _ptr(fsum), dev))
     return fsum
+
+
+# ---- body forces: electrostatic force and random stress -------------------------------------------------------------
+
+def smooth_field(ctx, parts, colmap, f, vfrac, filt=None, out=None, kernel="wendland", kinds=None):
+    """isph_smooth_field == FunctorOuterSmoothField, one pass: f [nall] -> sf [nlocal].  filt = (filt_i, filt_j) or None;
+    rows whose kind fails filt_i are not written: they keep what `out` holds (zeros when out is None)."""
+    if vfrac is None:
+        raise OperandError("smooth_field needs vfrac [nall]")
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, keep=keep, kinds=kinds)
+    f = _f64(f)
+    _same_side(dev, f, out)
+    n = int(parts["nlocal"])
+    _need(f, int(parts["nall"]), "f [nall]")
+    if out is None:
+        out = _out_like(dev, f, (n,))
+    _need(out, n, "sf_out [nlocal]")
+    fi, fj = filt if filt is not None else (127, 127)
+    _check(lib().isph_smooth_field(ctx.h, C.byref(pv), _ptr(f), int(filt is not None), int(fi), int(fj), _ptr(out), dev))
+    return out
+
+
+class EkParams(C.Structure):
+    """isph_ek_params: pb.ezcb, pb.psiref, pb.gamma (defaults 0, 1, 0: pair_isph.cpp:1684-1698), pb_e = pb.e (the field
+    used without phi) and ae_e = ae.e (phigrad = -ae_e on the buffer rows)."""
+    _fields_ = [("ezcb", C.c_double), ("psiref", C.c_double), ("gamma", C.c_double), ("pb_e", C.c_double * 3),
+                ("ae_e", C.c_double * 3)]
+
+    def __init__(self, ezcb=0.0, psiref=1.0, gamma=0.0, pb_e=(0.0, 0.0, 0.0), ae_e=(0.0, 0.0, 0.0)):
+        super().__init__(float(ezcb), float(psiref), float(gamma), (C.c_double * 3)(*[float(v) for v in pb_e]),
+                         (C.c_double * 3)(*[float(v) for v in ae_e]))
+
+
+def electrostatic_force(ctx, parts, colmap, prm, psi, vfrac, phi=None, f=None, antisym=False, Gc=None, pnd=None,
+                        morris_holmes=None, morris_safe_coeff=0.43301, kernel="wendland", kinds=None, with_gradients=True):
+    """isph_electrostatic_force: the psi gradient (Fluid, All; MorrisHolmes mirror when pnd is given), the phi gradient
+    (Fluid, Fluid; -ae_e on the buffer rows) and the force in one sweep.  psi, phi [nall]; f [nlocal, 3] is incremented
+    in place (None: gradients only).  morris_holmes: None = mirrored exactly when pnd is given.  Returns (psigrad,
+    phigrad), each [nlocal, 3] (phigrad None without phi), or None with with_gradients=False."""
+    if vfrac is None:
+        raise OperandError("electrostatic_force needs vfrac [nall]")
+    if morris_holmes is None:
+        morris_holmes = pnd is not None
+    if morris_holmes and pnd is None:
+        raise OperandError("the MorrisHolmes mirror needs pnd [nall]")
+    if not morris_holmes:
+        pnd = None
+    if not antisym and Gc is None:
+        raise OperandError("the Symmetric gradient (antisym = 0) needs Gc")
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, Gc=Gc, keep=keep, kinds=kinds, pnd=pnd,
+                                   morris_safe_coeff=morris_safe_coeff)
+    psi = _f64(psi)
+    phi = None if phi is None else _f64(phi)
+    _same_side(dev, psi, phi, f)
+    n, na = int(parts["nlocal"]), int(parts["nall"])
+    _need(psi, na, "psi [nall]"); _need(phi, na, "phi [nall]"); _need(f, 3 * n, "f [nlocal][3]")
+    gpsi = _out_like(dev, psi, (n, 3)) if with_gradients else None
+    gphi = _out_like(dev, psi, (n, 3)) if with_gradients and phi is not None else None
+    _check(lib().isph_electrostatic_force(ctx.h, C.byref(pv), int(antisym), C.byref(prm), _ptr(psi), _ptr(phi), _ptr(gpsi),
+                                          _ptr(gphi), _ptr(f), dev))
+    return (gpsi, gphi) if with_gradients else None
+
+
+def _rs_view(parts, colmap, vfrac, kernel, kinds):
+    if vfrac is None:
+        raise OperandError("the random stress needs vfrac [nall]")
+    keep = []
+    return particles_view(parts, colmap, kernel=kernel, vfrac=vfrac, keep=keep, kinds=kinds)
+
+
+def random_stress_tensor(ctx, parts, colmap, tag, seed, step, kernel="wendland", kinds=None):
+    """isph_random_stress_tensor: rs [nlocal, 6], the traceless symmetric tensor of every Fluid particle packed as (0,0),
+    (0,1), (1,1), (0,2), (1,2), (2,2); a function of (seed, step, tag) alone (Philox4x32-10)."""
+    keep = []
+    pv, dev, keep = particles_view(parts, colmap, kernel=kernel, keep=keep, kinds=kinds)
+    tag = _i32(tag)
+    _same_side(dev, tag)
+    n = int(parts["nlocal"])
+    _need(tag, n, "tag [nlocal]")
+    rs = _out_like(dev, parts["x"], (n, 6))
+    _check(lib().isph_random_stress_tensor(ctx.h, C.byref(pv), _ptr(tag), int(seed), int(step), _ptr(rs), dev))
+    return rs
+
+
+def random_stress_force(ctx, parts, colmap, dt, kBT, nu, rho, rs, f, vfrac, kernel="wendland", kinds=None):
+    """isph_random_stress_force: f [nlocal, 3] incremented in place on the Fluid rows; rs [nall, 6] with the ghost records
+    filled; nu, rho [nlocal]."""
+    pv, dev, keep = _rs_view(parts, colmap, vfrac, kernel, kinds)
+    nu, rho, rs = _f64(nu), _f64(rho), _f64(rs)
+    _same_side(dev, nu, rho, rs, f)
+    n = int(parts["nlocal"])
+    _need(nu, n, "nu [nlocal]"); _need(rho, n, "rho [nlocal]"); _need(rs, 6 * int(parts["nall"]), "rs [nall][6]")
+    _need(f, 3 * n, "f [nlocal][3]")
+    _check(lib().isph_random_stress_force(ctx.h, C.byref(pv), float(dt), float(kBT), _ptr(nu), _ptr(rho), _ptr(rs), _ptr(f), dev))
+
+
+def force_from_random_stress(ctx, parts, colmap, tag, seed, step, dt, kBT, nu, rho, f, vfrac, plan=None, kernel="wendland",
+                             kinds=None, with_rs=False):
+    """isph_force_from_random_stress: tensors, ghost fill (through colmap; plan: a HaloForward for the off-rank ghosts) and
+    the sweep in one call; f [nlocal, 3] incremented in place.  Returns rs [nlocal, 6] with with_rs=True."""
+    pv, dev, keep = _rs_view(parts, colmap, vfrac, kernel, kinds)
+    tag, nu, rho = _i32(tag), _f64(nu), _f64(rho)
+    _same_side(dev, tag, nu, rho, f)
+    n = int(parts["nlocal"])
+    _need(tag, n, "tag [nlocal]"); _need(nu, n, "nu [nlocal]"); _need(rho, n, "rho [nlocal]"); _need(f, 3 * n, "f [nlocal][3]")
+    rs = _out_like(dev, parts["x"], (n, 6)) if with_rs else None
+    _check(lib().isph_force_from_random_stress(ctx.h, C.byref(pv), None if plan is None else plan.h, _ptr(tag), int(seed),
+                                               int(step), float(dt), float(kBT), _ptr(nu), _ptr(rho), _ptr(f), _ptr(rs), dev))
+    return rs

@@ -683,6 +683,88 @@ int isph_surface_tension_csf(isph_ctx *ctx, const isph_particles *P, const isph_
 int isph_pairwise_force(isph_ctx *ctx, const isph_particles *P, int model, const int *phase, const double *s,
                         int nphase, double *f_inout, double f_sum[3], int on_device);
 
+/* ---- body forces: electrostatic force and random stress ------------------ */
+
+/* FunctorOuterSmoothField, scalar form (functor_smooth_field.h:43-106): sf_i = f_i W(0,h_ii) V_i + sum_j f_j W(r_ij) V_j,
+ * with FilterBinary(filt_i, filt_j) when use_filter.  f [nall], sf_out [nlocal].  One pass.  Rows whose kind fails the
+ * filter are NOT written (the functor returns first): they keep what sf_out held.  Needs P->vfrac [nall].
+ *
+ * The smoothing loop of computeAppliedElectricPotential (pair_isph_corrected.cpp:576-593, ae.smooth_phi passes over the
+ * conductivity that feeds isph_assemble_applied_potential) is the caller's to write.  That loop copies only nlocal
+ * entries of the result back into its input sigmatmp and communicates `work`, not sigmatmp: from the second pass on the
+ * reference still reads the UNSMOOTHED ghost values.  This entry point is one pass, and the caller decides what the
+ * ghosts of f hold (its own forward comm of the previous pass, or the reference's stale values). */
+int isph_smooth_field(isph_ctx *ctx, const isph_particles *P, const double *f /*[nall]*/, int use_filter, int filt_i,
+                      int filt_j, double *sf_out /*[nlocal]*/, int on_device);
+
+typedef struct {
+  double ezcb, psiref, gamma;   /* pb.ezcb, pb.psiref, pb.gamma: 0, 1, 0 (pair_isph.cpp:1684-1698) */
+  double pb_e[3];               /* pb.e: the field used when phi == NULL                           */
+  double ae_e[3];               /* ae.e: phigrad = -ae_e on the buffer rows                        */
+} isph_ek_params;
+void isph_ek_params_default(isph_ek_params *p);
+
+/* computePsiGradient + computePhiGradient + computeElectrostaticForce in ONE neighbour sweep.
+ *
+ * psi gradient = Corrected::FunctorOuterGradient (functor_gradient.h:80-169) with FilterBinary(Fluid, All)
+ * (pair_isph_corrected.cpp:540-565).  The reference's call sites use the Symmetric family (default template argument,
+ * :551-558): antisym = 0 needs P->Gc; antisym = 1 is offered as everywhere else in this ABI.  When P->morris_holmes is
+ * set, a pair whose i is not Solid and whose j is Solid is weighted by MirrorMorrisHolmes::computeMirrorCoefficient(
+ * sqrt(cutsq)) (functor_boundary_morris_holmes.h:99-102, mirror_morris_holmes.h:39-52): needs P->pnd and P->vfrac, both
+ * [nall].  Rows that fail the filter hold exact zeros (the memset at :544).
+ *
+ * phi gradient (only when phi != NULL; phigrad_out is not touched otherwise) = the same functor with
+ * FilterBinary(Fluid, Fluid) and MirrorNothing; afterwards the rows whose kind is exactly BufferDirichlet or
+ * BufferNeumann hold -ae_e in all three components (pair_isph_corrected.cpp:621-651).  Fluid = 99 contains the buffer
+ * bits, so buffer rows do pass the filter first; the override decides their value.
+ *
+ * force on EVERY owned particle, no filter (functor_electrostatic_force.h:39-56, pair_isph.cpp:679-687):
+ *   f_i[k] -= ezcb 2 sinh(psi_i) / (1 + 2 gamma sinh^2(psi_i / 2)) (-psiref d_k psi_i + e_k),  k < dim,
+ * e = -grad phi_i (after the override) when phi is given, else pb_e.  The functor uses sinh also when the
+ * Poisson-Boltzmann solve was linearized; so does this.
+ *
+ * psi, phi [nall] with ghosts filled; psigrad_out, phigrad_out [nlocal][3] or NULL; f_inout [nlocal][3], or NULL for the
+ * gradients alone. */
+int isph_electrostatic_force(isph_ctx *ctx, const isph_particles *P, int antisym, const isph_ek_params *prm,
+                             const double *psi /*[nall]*/, const double *phi /*[nall] or NULL*/,
+                             double *psigrad_out /*[nlocal][3] or NULL*/, double *phigrad_out /*[nlocal][3] or NULL*/,
+                             double *f_inout /*[nlocal][3] or NULL: gradients only*/, int on_device);
+
+/* ns.is_fluctuation_enabled -> computeForceFromRandomStress (pair_isph_corrected.cpp:130-132, 812-826).
+ *
+ * isph_random_stress_tensor = computeRandomStressTensor (pair_isph.cpp:710-758) on the owned rows with kind & Fluid:
+ * dim^2 standard normals g, R[k2][k1] = g[k2 dim + k1], T = (R + R^T) / 2, T[k][k] -= tr T / dim; other rows hold
+ * zeros.  rs_out [nlocal][6] = T packed as (0,0), (0,1), (1,1), (0,2), (1,2), (2,2), the order of Lc (48 bytes per ghost
+ * record instead of the 72 of the reference's three [nmax][3] arrays; in 2-D the last three are zero), 16-byte aligned
+ * when on the device.  tag [nlocal] = atom->tag.
+ *
+ * DEPARTURE: the reference draws from LAMMPS' per-rank RanMars stream in ilist order, so its numbers depend on the
+ * decomposition and the atom order.  Here the normals are a pure function of (seed, step, tag): Philox4x32-10 with
+ * key = (seed low 32, seed high 32) and counter = (tag, b, step low, step high) for the draw block b = 0..1 (2-D) or
+ * 0..4 (3-D); the outputs (o0, o1, o2, o3) give u1 = (((o0 2^32 + o1) >> 11) + 0.5) 2^-53 and u2 likewise from (o2, o3);
+ * g[2b] = sqrt(-2 ln u1) cos(2 pi u2), g[2b+1] = sqrt(-2 ln u1) sin(2 pi u2); the tenth normal in 3-D is dropped.  The
+ * same particle gets the same tensor on any rank count and in any atom order.
+ *
+ * isph_random_stress_force = FunctorOuterRandomStress with FunctorOuterDivergenceAntiSymmetric
+ * (functor_random_stress.h:54-74) on the rows with kind & Fluid, pairs FilterBinary(Fluid, Fluid):
+ *   d_c = -sum_j r_ij . (T_i[:,c] + T_j[:,c]) W'/r sqrt(V_i V_j),   f_i[c] += d_c sqrt(2 kBT nu_i rho_i / dt / V_i),
+ * all dim columns from one sweep (the reference makes three functor calls per particle).  rs [nall][6] with the ghost
+ * records filled; nu, rho [nlocal]; does not read Gc.
+ *
+ * isph_force_from_random_stress = tensors + ghost fill + sweep; ghost records are read through P->colmap (an image of an
+ * owned particle reads its owner), off-rank ghosts (colmap >= nlocal) through one isph_halo_forward of the 6-double
+ * records when plan is not NULL.  rs_out [nlocal][6] or NULL. */
+int isph_random_stress_tensor(isph_ctx *ctx, const isph_particles *P, const int *tag /*[nlocal]*/,
+                              unsigned long long seed, unsigned long long step,
+                              double *rs_out /*[nlocal][6]*/, int on_device);
+int isph_random_stress_force(isph_ctx *ctx, const isph_particles *P, double dt, double kBT, const double *nu /*[nlocal]*/,
+                             const double *rho /*[nlocal]*/, const double *rs /*[nall][6], ghosts filled*/,
+                             double *f_inout /*[nlocal][3]*/, int on_device);
+int isph_force_from_random_stress(isph_ctx *ctx, const isph_particles *P, const isph_halo_plan *plan, const int *tag,
+                                  unsigned long long seed, unsigned long long step, double dt, double kBT,
+                                  const double *nu, const double *rho, double *f_inout,
+                                  double *rs_out /*[nlocal][6] or NULL*/, int on_device);
+
 #ifdef __cplusplus
 }
 #endif
