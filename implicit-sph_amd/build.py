@@ -76,6 +76,22 @@ def build_cpp_test(force=False):
     return CPP_TEST
 
 
+CPP_CHEB_TEST = os.path.join(ROOT, "tests", "cpp", "test_chebyshev_wrappers")
+
+
+def build_cpp_chebyshev_test(force=False):
+    """C++ driver of the Chebyshev requests of PrecondWrapper_Ifpack / PrecondWrapper_ML (host/*.h), linked like
+    build_cpp_test; used by tests/test_gpu_chebyshev_wrappers.py."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_chebyshev_wrappers.cpp")
+    host = os.path.join(PKG, "host")
+    deps = [src] + [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(INC, "isph_hip.h")]
+    if force or _stale(CPP_CHEB_TEST, deps):
+        build_hip()
+        _run(["g++", "-O2", "-std=c++17", "-I", INC, "-I", host, "-o", CPP_CHEB_TEST, src,
+              "-L", PKG, "-lisph_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return CPP_CHEB_TEST
+
+
 RANK_THREADS = os.path.join(ROOT, "tests", "cpp", "librank_threads.so")
 
 
@@ -129,4 +145,5 @@ def build_cpp_mpi(force=False):
 
 
 def build_all(force=False):
-    return build_host(force), build_hip(force), build_cpp_test(force), build_cpp_mpi(force), build_rank_threads(force)
+    return (build_host(force), build_hip(force), build_cpp_test(force), build_cpp_mpi(force), build_rank_threads(force),
+            build_cpp_chebyshev_test(force))

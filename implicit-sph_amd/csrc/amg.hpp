@@ -12,11 +12,15 @@
 //   * Gauss-Seidel local to blocks of `block` rows (ML: local to the processor), one residual per sweep:
 //     x += M_B^-1 (b - A x), M_B = blockdiag[(D+L_B) D^-1 (D+U_B)], run through the ILU chunk stream (k_ilu_schedule in Gauss-Seidel mode);
 //   * damping from rho = ||D^-1 A||_inf ("eigen-analysis: type" Anorm).
+// isph_amg_params::smoother = 2 replaces the Gauss-Seidel sweeps by ML's "Chebyshev" ("MLS") smoother: a polynomial of
+// degree `sweeps` in D^-1 A with the same rho per level (chebyshev.hpp) -- no factor, no dense block inverses, not local
+// to blocks, a symmetric operator; the hierarchy is built by the same code whatever the smoother.
 // Set-up kernels work on device CSR copies, one wave per row (rows hold ~100 entries on the fine level); the
 // cycle itself uses the SELL SpMV and the chunk-stream triangular solves of the rest of the library.
 #pragma once
 #include <rocprim/rocprim.hpp>
 
+#include "chebyshev.hpp"
 #include "ilu.hpp"
 #include "solver.hpp"
 
@@ -54,6 +58,7 @@ struct AmgLevel {
   isph_ilu *sgs = nullptr;   // block-local symmetric Gauss-Seidel in stream form
   DevBuf<double> wsgs;       // small coarse levels: the same smoother as dense 64 x 64 inverses (k_sgs_dense_build)
   DevBuf<double> wfwd, wbwd; // ... of the forward / backward sweep alone (isph_amg::gs_eff)
+  Cheb *cheb = nullptr;      // isph_amg_params::smoother == 2: the Chebyshev polynomial of this level (chebyshev.hpp)
   DevBuf<int> agg;
   DevBuf<double> nv, x, b, r, z;
 };
@@ -63,6 +68,7 @@ struct AmgLevel {
 struct isph_amg {
   int nlev = 0, block = 512, sweeps = 1, singular = 0;
   int gs_eff = 0;         // isph_amg_params::smoother == 1: forward sweeps before, backward sweeps after the coarse correction
+  int cheb = 0;           // isph_amg_params::smoother == 2: Chebyshev polynomial of degree `sweeps` in D^-1 A, before and after
   int coarse_smooth = 0;  // coarsest level solved by the smoother: singular system (precond_ml.h:97-127) or a level too
                           // large for the dense inverse (no coarsening possible: isolated / Dirichlet rows dominate)
   std::vector<isph::AmgLevel *> L;
@@ -685,6 +691,10 @@ __global__ void k_low32(long long nnz, const unsigned long long *__restrict__ ke
 // C = X * Y, one workgroup per row of C, LDS accumulator: direct-addressed when Y has <= TABLE columns, open
 // addressing otherwise.  Thread t walks entries t, t+BS, .. of X's row and the whole Y row behind each.
 // FILL = false counts the row's entries.  Output columns are in table order (the SELL conversion sorts rows).
+// BS = 64 (every caller): ONE wave adds into a row's table, in the order of its lanes and of the rows they walk, so two
+// builds of one matrix give the same bits.  With four waves per row the additions to a slot interleaved in the order
+// the waves happened to arrive and the last bits of every coarse operator changed from build to build.
+constexpr int kSpgemmAhead = 8;
 template <int TABLE, int BS, bool FILL>
 __global__ __launch_bounds__(BS) void k_spgemm(int n, int ycols, int yrows, const rp_t *__restrict__ xrp,
                                                const int *__restrict__ xci, const double *__restrict__ xv,
@@ -692,6 +702,7 @@ __global__ __launch_bounds__(BS) void k_spgemm(int n, int ycols, int yrows, cons
                                                const double *__restrict__ yv, int *__restrict__ ccnt,
                                                const rp_t *__restrict__ crp, int *__restrict__ cci,
                                                double *__restrict__ cv, int *__restrict__ err) {
+  static_assert(BS == kWave, "one wave per row: the order of the additions into the table must not depend on scheduling");
   __shared__ int tk[TABLE];
   __shared__ double tv[TABLE];
   __shared__ int s_cnt;
@@ -705,22 +716,37 @@ __global__ __launch_bounds__(BS) void k_spgemm(int n, int ycols, int yrows, cons
     const int k = xci[p];
     if (k >= yrows) continue;
     const double xa = xv[p];
-    for (rp_t q = yrp[k]; q < yrp[k + 1]; ++q) {
-      const int c = yci[q];
-      int slot = dense ? c : (int)((amg_hash32((unsigned)c)) & (TABLE - 1));
-      if (dense) {
-        tk[slot] = c;  // benign race: every writer stores the same value
-      } else {
-        int tries = 0;
-        while (true) {
-          const int old = atomicCAS(&tk[slot], -1, c);
-          if (old == -1 || old == c) break;
-          slot = (slot + 1) & (TABLE - 1);
-          if (++tries >= TABLE) { atomicOr(err, 2); slot = -1; break; }  // table full
-        }
-        if (slot < 0) continue;
+    // the Y row in groups of kSpgemmAhead entries whose loads are issued together (the walk is a chain of dependent
+    // L2 round trips otherwise); the additions keep the order of the row
+    const rp_t yend = yrp[k + 1];
+    for (rp_t q0 = yrp[k]; q0 < yend; q0 += kSpgemmAhead) {
+      int cc[kSpgemmAhead];
+      double yy[kSpgemmAhead];
+#pragma unroll
+      for (int u = 0; u < kSpgemmAhead; ++u) {
+        const bool in = q0 + u < yend;
+        cc[u] = in ? yci[q0 + u] : -1;
+        yy[u] = (FILL && in) ? yv[q0 + u] : 0.0;
       }
-      if (FILL) atomicAdd(&tv[slot], xa * yv[q]);
+#pragma unroll
+      for (int u = 0; u < kSpgemmAhead; ++u) {
+        const int c = cc[u];
+        if (c < 0) continue;
+        int slot = dense ? c : (int)((amg_hash32((unsigned)c)) & (TABLE - 1));
+        if (dense) {
+          tk[slot] = c;  // benign race: every writer stores the same value
+        } else {
+          int tries = 0;
+          while (true) {
+            const int old = atomicCAS(&tk[slot], -1, c);
+            if (old == -1 || old == c) break;
+            slot = (slot + 1) & (TABLE - 1);
+            if (++tries >= TABLE) { atomicOr(err, 2); slot = -1; break; }  // table full
+          }
+          if (slot < 0) continue;
+        }
+        if (FILL) atomicAdd(&tv[slot], xa * yy[u]);
+      }
     }
   }
   __syncthreads();
@@ -1279,6 +1305,7 @@ inline void amg_level_destroy(AmgLevel *L) {
   if (L->APm) isph_mat_destroy(L->APm);
   if (L->sgs) ilu_destroy(L->sgs);
   L->wsgs.release(); L->wfwd.release(); L->wbwd.release();
+  if (L->cheb) cheb_destroy(L->cheb);
   L->agg.release(); L->nv.release(); L->x.release(); L->b.release(); L->r.release(); L->z.release();
   delete L;
 }
@@ -1574,17 +1601,6 @@ __global__ void k_amg_ext_fill(int n, int nrecv, const rp_t *__restrict__ prp, c
   }
 }
 
-// in-place all-reduce of a few host numbers (op 0 sum, 1 max); every rank of the communicator calls it
-inline int amg_host_allreduce(isph_ctx *ctx, double *h, int count, int op) {
-  DevTmp<double> d;
-  ISPH_CHECK(d.reserve((size_t)count));
-  ISPH_CHECK_HIP(hipMemcpyAsync(d.p, h, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
-  ISPH_CHECK(comm_allreduce(ctx, d.p, count, op, ctx->stream));
-  ISPH_CHECK_HIP(hipMemcpyAsync(h, d.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
-  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  return ISPH_SUCCESS;
-}
-
 // P (n x nagg, this rank's rows) -> Pext ((n + ghosts of A) x (nagg + ghosts of the coarse level)) and the coarse halo
 // lists.  K: longest P row on any send list of any rank (agreed by the caller).
 // Two halves, so that the ranks can agree between them: everything of the first half that can fail on one rank alone
@@ -1756,12 +1772,17 @@ inline int amg_level_buffers(AmgLevel *L) {
 inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
                       isph_amg **out) {
   ISPH_REQUIRE(prm->max_levels >= 1 && prm->max_levels <= 8, "max_levels must be in [1,8]");
-  ISPH_REQUIRE(prm->block >= 64 && prm->block <= 1024 && prm->block % 64 == 0, "smoother block must be a multiple of 64 in [64,1024]");
+  ISPH_REQUIRE(prm->smoother == 2 || (prm->block >= 64 && prm->block <= 1024 && prm->block % 64 == 0),
+               "smoother block must be a multiple of 64 in [64,1024]");   // (Chebyshev has no blocks: the field is not read)
   ISPH_REQUIRE(prm->sweeps >= 1, "smoother sweeps must be >= 1");
+  ISPH_REQUIRE(prm->smoother >= 0 && prm->smoother <= 2,
+               "smoother must be 0 (symmetric Gauss-Seidel), 1 (Gauss-Seidel, efficient symmetric) or 2 (Chebyshev)");
+  ISPH_REQUIRE(prm->smoother != 2 || prm->sweeps <= kChebMaxDegree, "Chebyshev smoother: sweeps is the polynomial degree, at most 16");
+  ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_ratio > 1.0, "Chebyshev smoother: cheb_ratio (\"smoother: Chebyshev alpha\") must be > 1");
   isph_amg *G = new isph_amg();
   G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
-  ISPH_REQUIRE(prm->smoother == 0 || prm->smoother == 1, "smoother must be 0 (symmetric Gauss-Seidel) or 1 (Gauss-Seidel, efficient symmetric)");
   G->gs_eff = prm->smoother == 1;
+  G->cheb = prm->smoother == 2;
   DevTmp<char> tmp;
   DevTmp<int> derr;
   DevTmp<double> dg;
@@ -1804,7 +1825,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     const int n = L->A.n;
     if (dist) {   // go on while any rank is above coarse_max (and none has failed)
       double h[2] = {rc == ISPH_SUCCESS && n > prm->coarse_max ? 1.0 : 0.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (amg_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
+      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
       if (h[1] != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); break; }
       if (h[0] == 0.0) break;
     } else if (n <= prm->coarse_max) break;
@@ -1825,7 +1846,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     bool identity = false;
     if (dist) {   // ... when no rank can go on; a rank that cannot while others can passes its level on unchanged (P = I)
       double h[2] = {stop ? 0.0 : 1.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (amg_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
+      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
       if (h[1] != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
       identity = stop && h[0] != 0.0 && rc == ISPH_SUCCESS;
       stop = h[0] == 0.0 || rc != ISPH_SUCCESS;
@@ -1850,14 +1871,14 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
                            (const int *)H.send_idx.p, (const rp_t *)L->P.rp.p, kmax.p);
       if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, kmax.p, &hk);
       double h[2] = {(double)hk, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (amg_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
+      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
       if (h[1] != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
       AmgExtendState est;
       const int Kx = std::max((int)h[0], 1);
       // (a rank without ghost columns of its own still owes its neighbours their rows)
       if (H.npeers > 0) rc = amg_extend_pack(ctx, H, L->P, Kx, est, cs_ptr, cs_idx, tmp);
       double h2 = rc == ISPH_SUCCESS ? 0.0 : 1.0;   // nobody enters the exchange unless everybody can
-      if (amg_host_allreduce(ctx, &h2, 1, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
+      if (comm_host_allreduce(ctx, &h2, 1, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
       if (h2 != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
       if (H.npeers > 0) {
         rc = amg_extend_finish(ctx, H, L->P, Kx, est, Pext, cr_ptr, tmp);
@@ -1866,7 +1887,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     }
     if (rc == ISPH_SUCCESS) rc = amg_transpose(ctx, L->P, R, tmp);
     if (rc == ISPH_SUCCESS) rc = amg_spgemm_ap(ctx, L->A, extended ? Pext : L->P, AP, tmp, derr.p);
-    if (rc == ISPH_SUCCESS) rc = amg_spgemm_t<4096, 256>(ctx, R, AP, Lc->A, tmp, derr.p);
+    if (rc == ISPH_SUCCESS) rc = amg_spgemm_t<4096, 64>(ctx, R, AP, Lc->A, tmp, derr.p);
     Pext.release();
     int herr = 0;
     if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr.p, &herr);
@@ -1904,17 +1925,31 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     std::vector<double> h((size_t)ctx->nranks + 1, 0.0);
     h[(size_t)ctx->rank] = (double)G->L.back()->A.n;
     h[(size_t)ctx->nranks] = rc == ISPH_SUCCESS ? 0.0 : 1.0;
-    if (amg_host_allreduce(ctx, h.data(), ctx->nranks + 1, 0) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
+    if (comm_host_allreduce(ctx, h.data(), ctx->nranks + 1, 0) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
     else if (h[(size_t)ctx->nranks] != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
     double tot = 0.0;
     for (int r = 0; r < ctx->nranks; ++r) { if (r == ctx->rank) nc_off = (int)tot; tot += h[(size_t)r]; }
     nc_glob = tot > 2.0e9 ? 2000000000 : (int)tot;
     G->coarse_smooth = G->singular || nc_glob > kAmgDenseMax;
   }
-  for (int l = 0; l < G->nlev && rc == ISPH_SUCCESS; ++l) {
+  // Chebyshev across ranks: rho of a level is all-reduced, one collective call per level.  The walk is entered only
+  // when the set-up has succeeded so far -- after the consensus above that is all ranks or none, and with success on all
+  // ranks every rank has gone through the same coarsening steps, so nlev is agreed here (a rank that failed in a step
+  // holds one level less than its peers; none of them walks).  A failure that arises INSIDE the walk is carried through
+  // the remaining levels' all-reduces (prior_failure), so that the ranks' calls still pair up.
+  const bool walk = dist && G->cheb && rc == ISPH_SUCCESS;
+  for (int l = 0; l < G->nlev && (rc == ISPH_SUCCESS || walk); ++l) {
     AmgLevel *L = G->L[(size_t)l];
-    rc = amg_level_buffers(L);
+    if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L);
     const bool last = l == G->nlev - 1;
+    if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
+      if (!last || G->coarse_smooth) {
+        const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, 0.0, 0.0, /*empty_ok=*/l > 0, /*collective=*/dist,
+                                  /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb);
+        if (rc == ISPH_SUCCESS) rc = r2;
+      }
+      continue;
+    }
     // coarse levels are small: 64-row blocks keep enough waves busy (an 8-block level ran its sweeps on 8 waves)
     if (rc == ISPH_SUCCESS && (!last || G->coarse_smooth)) {
       const char *env_stream = getenv("ISPH_AMG_COARSE_STREAM");   // the chunk-stream sweeps on every level (rounds 2-4)
@@ -1939,7 +1974,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   }
   if (dist) {   // the smoothers are built per rank: a failure there must keep every rank out of the collective steps below
     double h = rc == ISPH_SUCCESS ? 0.0 : 1.0;
-    if (amg_host_allreduce(ctx, &h, 1, 1) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
+    if (comm_host_allreduce(ctx, &h, 1, 1) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
     else if (h != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
   }
   if (rc == ISPH_SUCCESS && !G->coarse_smooth && dist && G->nlev > 1) {
@@ -2016,7 +2051,9 @@ inline int amg_vcycle(isph_ctx *ctx, const isph_amg *G, int l, const double *b, 
   AmgLevel *L = G->L[(size_t)l];
   const int n = L->A.n;
   if (l == G->nlev - 1) {
-    if (G->coarse_smooth) {
+    if (G->coarse_smooth && G->cheb) {
+      ISPH_CHECK(cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/true));   // the level is "solved" by the same polynomial
+    } else if (G->coarse_smooth) {
       ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true));
       for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false));
     } else if (G->dist && G->nlev > 1) {
@@ -2037,8 +2074,12 @@ inline int amg_vcycle(isph_ctx *ctx, const isph_amg *G, int l, const double *b, 
   }
   AmgLevel *Lc = G->L[(size_t)l + 1];
   const int pre = G->gs_eff ? 1 : 0, post = G->gs_eff ? 2 : 0;
-  ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true, pre));
-  for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false, pre));
+  if (G->cheb) {
+    ISPH_CHECK(cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/true));
+  } else {
+    ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true, pre));
+    for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false, pre));
+  }
   ISPH_CHECK(spmv_dev(ctx, L->Am, x, L->r.p, nullptr, b, -1.0));   // r = b - A x
   if (L->R.n > 0)   // (a rank without rows still walks the cycle: its neighbours' exchanges and the all-reduces count on it)
     hipLaunchKernelGGL(k_csr_spmv_wave, dim3(amg_wave_grid(L->R.n)), dim3(256), 0, ctx->stream, L->R.n, (const rp_t *)L->R.rp.p,
@@ -2046,6 +2087,11 @@ inline int amg_vcycle(isph_ctx *ctx, const isph_amg *G, int l, const double *b, 
   ISPH_CHECK(amg_vcycle(ctx, G, l + 1, Lc->b.p, Lc->x.p));
   ISPH_CHECK(spmv_dev(ctx, L->Pm, Lc->x.p, x, nullptr, x, 1.0));   // x += P e
   int first = 0;
+  if (G->cheb) {
+    // r still holds b - A x of before the correction: r -= (A P) e is the residual the polynomial's first step needs
+    if (L->APm) ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));
+    return cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/false, L->APm ? (const double *)L->r.p : nullptr);
+  }
   if (L->APm) {
     // r still holds b - A x of before the correction: r -= (A P) e, then the first post-smoothing sweep uses it
     ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));

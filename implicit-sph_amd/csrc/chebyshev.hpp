@@ -1,0 +1,384 @@
+// chebyshev.hpp -- Chebyshev polynomial in D^-1 A: the "Chebyshev" / "MLS" smoother of the SA-AMG (amg.hpp) and the
+// stand-alone preconditioner isph_prec_create_chebyshev ("Precond Type" = "Chebyshev" of PrecondWrapper_Ifpack).
+//
+// The recurrence is Ifpack_Chebyshev::ApplyInverse / ML_Cheby restated from the packages' algorithm (Trilinos is not
+// vendored: unpinned against them):
+//     lambda = rho = ||D^-1 A||_inf (all-reduced maximum on several ranks), beta = 1.1 lambda, alpha = lambda / ratio,
+//     theta = (beta + alpha) / 2, delta = (beta - alpha) / 2, sigma = theta / delta, rho_0 = 1 / sigma
+//     step 1:        w = (1/theta) D^-1 (b - A y),                              y += w
+//     step k = 2..d: rho_k = 1 / (2 sigma - rho_{k-1}),
+//                    w = rho_k rho_{k-1} w + (2 rho_k / delta) D^-1 (b - A y),  y += w
+// Every step is  w = c1 w + c2 D^-1 (b - A y),  y += w  with two scalars the host computes in double and passes as kernel
+// arguments.  No dependency chain, no set-up beyond the diagonal, no dependence on the row order, the block size or
+// the rank count -- and a fixed linear operator, so CG may use it.
+//
+// One step is ONE sweep of the matrix (k_sell_cheby_step: the slice walk of k_sell_spmv16 / k_sell_spmv with the update
+// in the epilogue); the product-free first step of a zero guess (and of a residual the caller already holds) is a
+// streaming kernel (k_cheby_first).  ISPH_CHEB_UNFUSED=1 (read at set-up) runs the same recurrence as
+// spmv_dev(.., badd = b, alpha = -1) plus a streaming update: the cross-check and the timing baseline of the fused step.
+#pragma once
+#include "solver.hpp"
+
+namespace isph {
+
+constexpr int kChebMaxDegree = 16;
+
+struct Cheb {
+  int n = 0, degree = 1, unfused = 0;
+  double lambda = 0.0, alpha = 0.0, beta = 0.0;
+  double c1[kChebMaxDegree], c2[kChebMaxDegree];   // step k (0-based): w = c1[k] w + c2[k] D^-1 (b - A y)
+  DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
+};
+
+inline void cheb_destroy(Cheb *C) {
+  if (!C) return;
+  C->dinv.release(); C->w.release(); C->t.release(); C->r.release();
+  delete C;
+}
+
+// the 2d scalars of the recurrence (double, host)
+inline void cheb_coefficients(Cheb *C) {
+  const double theta = 0.5 * (C->beta + C->alpha), delta = 0.5 * (C->beta - C->alpha), sigma = theta / delta;
+  double rho_old = 1.0 / sigma;
+  C->c1[0] = 0.0;
+  C->c2[0] = 1.0 / theta;
+  for (int k = 1; k < C->degree; ++k) {
+    const double rho_new = 1.0 / (2.0 * sigma - rho_old);
+    C->c1[k] = rho_new * rho_old;
+    C->c2[k] = 2.0 * rho_new / delta;
+    rho_old = rho_new;
+  }
+}
+
+// the one expression of the update, shared by the fused and the unfused kernels (same bits from the same operands)
+__device__ __forceinline__ double cheb_increment(double c1, double c2, double w_old, double dinv, double r) {
+  const double t = dinv * r;
+  return fma(c1, w_old, c2 * t);
+}
+
+// ---- set-up: 1 / a_ii, rho = max_i sum_j |a_ij| / |a_ii| (ghost columns included: the row is the row of the global
+// matrix, whichever rank owns its columns), a flag for a zero diagonal.  One wave per slice, lane == row.
+// out[0]: bit pattern of rho (a non-negative double orders like its bits), out[1]: 1 when a diagonal entry is zero.
+// empty_ok: a row without any entry (coarse operators of the AMG can have them) gets dinv = 0 and is left alone.
+__global__ __launch_bounds__(kBlock) void k_cheby_setup(int nrow, int nslices, const long long *__restrict__ slice_off,
+                                                        const int *__restrict__ scol, const double *__restrict__ sval,
+                                                        int empty_ok, double *__restrict__ dinv,
+                                                        unsigned long long *__restrict__ out) {
+  const int slice = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
+  if (slice >= nslices) return;
+  const int lane = threadIdx.x & 63, row = slice * kSlice + lane;
+  const long long off = slice_off[slice];
+  const int w = (int)((slice_off[slice + 1] - off) >> 6);
+  double d = 0.0, s = 0.0;
+  for (int k = 0; k < w; ++k) {   // padding: value 0
+    const long long p = sell_pos(off, lane, k);
+    const double v = sval[p];
+    if (scol[p] == row) d += v;
+    s += fabs(v);
+  }
+  bool bad = false;
+  double q = 0.0;
+  if (row < nrow) {
+    if (d != 0.0) {
+      dinv[row] = 1.0 / d;
+      q = s / fabs(d);
+    } else {
+      dinv[row] = 0.0;
+      bad = !(empty_ok && s == 0.0);
+    }
+  }
+  // wave maximum through the bit patterns (two 32-bit halves would not order: compare as 64-bit in a butterfly)
+  unsigned long long bits = (unsigned long long)__double_as_longlong(q);
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(bits, o, 64);
+    bits = other > bits ? other : bits;
+  }
+  if (lane == 0 && bits > out[0]) atomicMax(&out[0], bits);
+  if (__ballot(bad) != 0ull && lane == 0) atomicMax(&out[1], 1ull);
+}
+
+// ---- one step in one sweep of the matrix ------------------------------------------------------------------------------
+// (A y)_i by the slice walk of k_sell_spmv16 (C16: pair-interleaved SELL-64, lane == row, 16-bit windowed columns through
+// the per-wave LDS table) or of k_sell_spmv (32-bit columns: the aux operators of the AMG), non-temporal matrix loads,
+// XCD remap; then  w_i = c1 w_i + c2 dinv_i (b_i - (A y)_i),  yout_i = y_i + w_i.
+// yout must NOT alias y: other waves still gather y.  c1 == 0 (first step): w is not read.
+template <bool C16, bool LIST, bool GHOST>
+__global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslices, int nblocks_padded,
+                                                            const long long *__restrict__ slice_off,
+                                                            const void *__restrict__ cols, const int *__restrict__ wtab,
+                                                            const double *__restrict__ sval, const double *__restrict__ y,
+                                                            const double *__restrict__ yg, const double *__restrict__ b,
+                                                            const double *__restrict__ dinv, double *__restrict__ w,
+                                                            double *__restrict__ yout, double c1, double c2,
+                                                            const int *__restrict__ slice_list) {
+  constexpr int UNROLL = 8;
+  __shared__ int tab[C16 ? kBlock / kWave : 1][64];
+  const int blk = xcd_remap(blockIdx.x, nblocks_padded);
+  const int wave = threadIdx.x >> 6;
+  int slice = blk * (kBlock / kWave) + wave;
+  if (slice >= nslices) return;
+  if (LIST) slice = slice_list[slice];
+  const int lane = threadIdx.x & 63;
+  if (C16) {
+    tab[wave][lane] = wtab[(long long)slice * 64 + lane] << 10;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  const int *__restrict__ tw = tab[C16 ? wave : 0];
+  const long long off = slice_off[slice];
+  const int npair = (int)((slice_off[slice + 1] - off) >> 7);
+  const double2 *__restrict__ v = reinterpret_cast<const double2 *>(sval + off) + lane;
+  const unsigned *__restrict__ c16 = reinterpret_cast<const unsigned *>(static_cast<const unsigned short *>(cols) + off) + lane;
+  const int2 *__restrict__ c32 = reinterpret_cast<const int2 *>(static_cast<const int *>(cols) + off) + lane;
+  double acc0 = 0.0, acc1 = 0.0;
+  int q = 0;
+  for (; q + UNROLL <= npair; q += UNROLL) {
+    double2 vv[UNROLL];
+    int ca[UNROLL], cb[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      vv[u].x = __builtin_nontemporal_load(&v[(q + u) * 64].x);
+      vv[u].y = __builtin_nontemporal_load(&v[(q + u) * 64].y);
+      if (C16) {
+        ca[u] = (int)__builtin_nontemporal_load(&c16[(q + u) * 64]);
+      } else {
+        ca[u] = __builtin_nontemporal_load(&c32[(q + u) * 64].x);
+        cb[u] = __builtin_nontemporal_load(&c32[(q + u) * 64].y);
+      }
+    }
+    double xa[UNROLL], xb[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      if (C16) {
+        const unsigned lo = (unsigned)ca[u] & 0xffffu, hi = (unsigned)ca[u] >> 16;
+        xa[u] = x_at<GHOST>(y, yg, nrow, tw[lo >> 10] | (int)(lo & 1023u));
+        xb[u] = x_at<GHOST>(y, yg, nrow, tw[hi >> 10] | (int)(hi & 1023u));
+      } else {
+        xa[u] = x_at<GHOST>(y, yg, nrow, ca[u]);
+        xb[u] = x_at<GHOST>(y, yg, nrow, cb[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      acc0 = fma(vv[u].x, xa[u], acc0);
+      acc1 = fma(vv[u].y, xb[u], acc1);
+    }
+  }
+  for (; q < npair; ++q) {
+    const double2 vv = v[q * 64];
+    int ca, cb;
+    if (C16) {
+      const unsigned cc = c16[q * 64];
+      const unsigned lo = cc & 0xffffu, hi = cc >> 16;
+      ca = tw[lo >> 10] | (int)(lo & 1023u);
+      cb = tw[hi >> 10] | (int)(hi & 1023u);
+    } else {
+      const int2 cc = c32[q * 64];
+      ca = cc.x;
+      cb = cc.y;
+    }
+    acc0 = fma(vv.x, x_at<GHOST>(y, yg, nrow, ca), acc0);
+    acc1 = fma(vv.y, x_at<GHOST>(y, yg, nrow, cb), acc1);
+  }
+  const int row = slice * kSlice + lane;
+  if (row < nrow) {
+    const double r = b[row] - (acc0 + acc1);
+    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? w[row] : 0.0, dinv[row], r);
+    w[row] = wn;
+    yout[row] = y[row] + wn;
+  }
+}
+
+// ---- streaming kernels ------------------------------------------------------------------------------------------------
+// The product-free first step:  w = c2 D^-1 r,  yout = yin + w  (yin == NULL: the zero guess, yout = w).  r is b for a
+// zero guess, or a residual b - A yin the caller already holds.  VEC: 16-byte loads and stores (all pointers aligned).
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void k_cheby_first(int n, double c2, const double *__restrict__ dinv,
+                                                        const double *__restrict__ r, const double *yin,
+                                                        double *__restrict__ w, double *yout) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (VEC) {
+    const long long n2 = n >> 1;
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv), *r2 = reinterpret_cast<const double2 *>(r);
+    const double2 *y2 = reinterpret_cast<const double2 *>(yin);
+    double2 *w2 = reinterpret_cast<double2 *>(w), *o2 = reinterpret_cast<double2 *>(yout);
+    for (long long i = t0; i < n2; i += stride) {
+      const double2 d = d2[i], rr = r2[i];
+      double2 wn, yo;
+      wn.x = cheb_increment(0.0, c2, 0.0, d.x, rr.x);
+      wn.y = cheb_increment(0.0, c2, 0.0, d.y, rr.y);
+      yo = wn;
+      if (yin) { const double2 yy = y2[i]; yo.x = yy.x + wn.x; yo.y = yy.y + wn.y; }
+      w2[i] = wn;
+      o2[i] = yo;
+    }
+    if ((n & 1) && t0 == 0) {
+      const int i = n - 1;
+      const double wn = cheb_increment(0.0, c2, 0.0, dinv[i], r[i]);
+      w[i] = wn;
+      yout[i] = yin ? yin[i] + wn : wn;
+    }
+  } else {
+    for (long long i = t0; i < n; i += stride) {
+      const double wn = cheb_increment(0.0, c2, 0.0, dinv[i], r[i]);
+      w[i] = wn;
+      yout[i] = yin ? yin[i] + wn : wn;
+    }
+  }
+}
+
+// ISPH_CHEB_UNFUSED=1: the update behind a separate r = b - A y
+__global__ __launch_bounds__(kBlock) void k_cheby_update(int n, double c1, double c2, const double *__restrict__ dinv,
+                                                         const double *__restrict__ r, double *__restrict__ w,
+                                                         const double *yin, double *yout) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? w[i] : 0.0, dinv[i], r[i]);
+    w[i] = wn;
+    yout[i] = yin[i] + wn;
+  }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+// collective: every rank of the context calls this together (stand-alone: a context with a communicator; AMG: a
+// hierarchy across ranks) -- rho is the all-reduced maximum and a failure on one rank is a failure on all.
+// prior_failure: this rank has already failed and only takes part in the collective step.
+inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio, double lambda_max, double lambda_min,
+                      bool empty_ok, bool collective, bool prior_failure, Cheb **out) {
+  const Sell &S = A->S;
+  int rc = ISPH_SUCCESS;
+  Cheb *C = new Cheb();
+  C->n = S.nrow;
+  C->degree = degree;
+  const char *env = getenv("ISPH_CHEB_UNFUSED");
+  C->unfused = env && env[0] == '1';
+  DevTmp<unsigned long long> flag;
+  double h[2] = {0.0, prior_failure ? 1.0 : 0.0};   // rho, failure
+  if (!prior_failure) {
+    const size_t m = (size_t)(S.nrow > 0 ? S.nrow : 1) + 64;
+    rc = flag.reserve(2);
+    if (rc == ISPH_SUCCESS) rc = C->dinv.reserve(m);
+    if (rc == ISPH_SUCCESS) rc = C->w.reserve(m);
+    if (rc == ISPH_SUCCESS) rc = C->t.reserve(m);
+    if (rc == ISPH_SUCCESS && C->unfused) rc = C->r.reserve(m);
+    if (rc == ISPH_SUCCESS && hipMemsetAsync(flag.p, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess)
+      rc = fail("memset failed", __FILE__, __LINE__);
+    unsigned long long hb[2] = {0ull, 0ull};
+    if (rc == ISPH_SUCCESS) {
+      if (S.nslices > 0)
+        hipLaunchKernelGGL(k_cheby_setup, dim3((S.nslices + 3) / 4), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices,
+                           (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, empty_ok ? 1 : 0,
+                           C->dinv.p, flag.p);
+      if (hipMemcpyAsync(hb, flag.p, sizeof(hb), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+          hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+        rc = fail("Chebyshev set-up failed", __FILE__, __LINE__);
+    }
+    if (rc == ISPH_SUCCESS && hb[1] != 0ull)
+      rc = fail("Chebyshev: the matrix has a zero diagonal entry (the polynomial acts on D^-1 A)", __FILE__, __LINE__);
+    memcpy(&h[0], &hb[0], sizeof(double));
+    if (rc != ISPH_SUCCESS) h[1] = 1.0;
+  }
+  if (collective) {
+    if (comm_host_allreduce(ctx, h, 2, /*max*/ 1) != ISPH_SUCCESS) { if (rc == ISPH_SUCCESS) rc = fail("Chebyshev: the all-reduce of rho failed", __FILE__, __LINE__); }
+    else if (h[1] != 0.0 && rc == ISPH_SUCCESS) rc = fail("Chebyshev: set-up failed on another rank", __FILE__, __LINE__);
+  }
+  if (rc != ISPH_SUCCESS || prior_failure) { cheb_destroy(C); return rc != ISPH_SUCCESS ? rc : ISPH_FAILURE; }
+  C->lambda = lambda_max > 0.0 ? lambda_max : h[0];
+  if (!(C->lambda > 0.0)) C->lambda = 1.0;   // a level without entries: D^-1 A is empty, any interval does
+  C->beta = 1.1 * C->lambda;
+  C->alpha = lambda_min > 0.0 ? lambda_min : C->lambda / ratio;
+  if (!(C->alpha < C->beta)) { cheb_destroy(C); return fail("Chebyshev: lambda_min must be below 1.1 lambda_max", __FILE__, __LINE__); }
+  cheb_coefficients(C);
+  *out = C;
+  return ISPH_SUCCESS;
+}
+
+template <bool LIST, bool GHOST>
+inline void cheb_step_launch(isph_ctx *ctx, const Sell &S, bool c16, int nsl, const int *list, const Cheb *C, const double *b,
+                             const double *y, const double *yg, double *yout, double c1, double c2) {
+  if (nsl <= 0) return;
+  int nbp = 0;
+  const int grid = spmv_grid(nsl, &nbp);
+  if (c16)
+    hipLaunchKernelGGL((k_sell_cheby_step<true, LIST, GHOST>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       (const long long *)S.slice_off.p, (const void *)S.col16.p, (const int *)S.wtab.p, (const double *)S.val.p, y, yg,
+                       b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
+  else
+    hipLaunchKernelGGL((k_sell_cheby_step<false, LIST, GHOST>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       (const long long *)S.slice_off.p, (const void *)S.col.p, (const int *)nullptr, (const double *)S.val.p, y, yg,
+                       b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
+}
+
+// one step with a matrix product: yout = y + w, w = c1 w + c2 D^-1 (b - A y); yout != y.  With a halo plan the exchange
+// of y overlaps the interior slices exactly as in spmv_dev.
+inline int cheb_step(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const double *b, const double *y, double *yout, double c1,
+                     double c2) {
+  const Sell &S = A->S;
+  if (C->unfused) {
+    ISPH_CHECK(spmv_dev(ctx, A, y, C->r.p, nullptr, b, -1.0));   // r = b - A y
+    hipLaunchKernelGGL(k_cheby_update, dim3(stream_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, S.nrow, c1, c2,
+                       (const double *)C->dinv.p, (const double *)C->r.p, C->w.p, y, yout);
+    ISPH_CHECK_HIP(hipGetLastError());
+    return ISPH_SUCCESS;
+  }
+  ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);   // a sweep of the caller's operator, like spmv_dev's
+  const bool halo = !A->local && (S.ncol != S.nrow || A->halo.nsend > 0);
+  const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
+  if (!halo) {
+    cheb_step_launch<false, false>(ctx, S, c16, S.nslices, nullptr, C, b, y, nullptr, yout, c1, c2);
+  } else {
+    const isph_halo &H = A->halo;
+    ISPH_CHECK(halo_begin(ctx, A, y));
+    cheb_step_launch<true, false>(ctx, S, c16, H.n_int, H.list_int.p, C, b, y, nullptr, yout, c1, c2);
+    ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
+    cheb_step_launch<true, true>(ctx, S, c16, H.n_bnd, H.list_bnd.p, C, b, y, ctx->xghost.p, yout, c1, c2);
+  }
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+inline void cheb_first_launch(isph_ctx *ctx, const Cheb *C, const double *r, const double *yin, double *yout) {
+  const int n = C->n;
+  if (n <= 0) return;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(yin) | reinterpret_cast<uintptr_t>(yout);
+  if ((bits & 15) == 0)   // (dinv and w are buffers of the pool)
+    hipLaunchKernelGGL((k_cheby_first<true>), dim3(stream_grid((n + 1) / 2)), dim3(kBlock), 0, ctx->stream, n, C->c2[0],
+                       (const double *)C->dinv.p, r, yin, C->w.p, yout);
+  else
+    hipLaunchKernelGGL((k_cheby_first<false>), dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, n, C->c2[0],
+                       (const double *)C->dinv.p, r, yin, C->w.p, yout);
+}
+
+// y <- y + p(D^-1 A) D^-1 (b - A y), p of degree C->degree.
+//   zero_guess: y is not read (y = p(D^-1 A) D^-1 b); the first step makes no matrix product.
+//   r0 != NULL (with a guess): b - A y is already there (the AMG cycle's A P shortcut); again no product in step 1.
+// The steps ping-pong between y and C->t; the result is in y for every degree.
+inline int cheb_apply(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const double *b, double *y, bool zero_guess,
+                      const double *r0 = nullptr) {
+  ISPH_REQUIRE(C != nullptr && C->n == A->S.nrow, "Chebyshev: not set up for this matrix");
+  const int d = C->degree;
+  const size_t nbytes = sizeof(double) * (size_t)(C->n > 0 ? C->n : 0);
+  double *T = C->t.p;
+  const double *cur;
+  int k0;   // first step that needs a product
+  if (zero_guess || r0) {
+    // d - 1 products follow: an even number ends where it starts
+    double *first = ((d - 1) % 2 == 0) ? y : T;
+    cheb_first_launch(ctx, C, zero_guess ? b : r0, zero_guess ? nullptr : y, first);
+    cur = first;
+    k0 = 1;
+  } else {
+    cur = y;
+    k0 = 0;
+  }
+  for (int k = k0; k < d; ++k) {
+    double *nxt = cur == y ? T : y;
+    ISPH_CHECK(cheb_step(ctx, A, C, b, cur, nxt, C->c1[k], C->c2[k]));
+    cur = nxt;
+  }
+  if (cur != y && nbytes > 0)   // (a guess and an odd number of products)
+    ISPH_CHECK_HIP(hipMemcpyAsync(y, T, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+}  // namespace isph

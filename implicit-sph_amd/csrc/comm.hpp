@@ -59,6 +59,19 @@ inline int comm_allreduce(isph_ctx *ctx, double *d, int count, int op, hipStream
   return ISPH_SUCCESS;
 }
 
+// in-place all-reduce of a few host numbers (op 0 sum, 1 max); every rank of the communicator calls it.  The one place
+// where a host value crosses the ranks: a consensus, a level's rho -- whoever needs one goes through here, so that the
+// ranks' collective calls pair up one to one.
+inline int comm_host_allreduce(isph_ctx *ctx, double *h, int count, int op) {
+  DevTmp<double> d;
+  ISPH_CHECK(d.reserve((size_t)count));
+  ISPH_CHECK_HIP(hipMemcpyAsync(d.p, h, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, ctx->stream));
+  ISPH_CHECK(comm_allreduce(ctx, d.p, count, op, ctx->stream));
+  ISPH_CHECK_HIP(hipMemcpyAsync(h, d.p, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return ISPH_SUCCESS;
+}
+
 // Point-to-point exchange with every peer of a halo plan, `ncomp` doubles per listed entry, on stream s.
 // reverse = false: send ranges -> peers, recv ranges <- peers (owners to ghosts); true: the roles swapped (ghost
 // contributions back to their owners, the "Add" of the overlapped Schwarz).

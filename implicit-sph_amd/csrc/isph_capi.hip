@@ -11,6 +11,7 @@
 #include "krylov.hpp"
 #include "sell.hpp"
 #include "solver.hpp"
+#include "chebyshev.hpp"
 #include "amg.hpp"
 #include "schwarz.hpp"
 #include "gcrodr.hpp"
@@ -120,6 +121,7 @@ int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, double *z
   if (M->type == 3) return amg_apply(ctx, M->amg, r, z);
   if (M->type == 4) return schwarz_apply(ctx, M->schwarz, r, z);
   if (M->type == 5) return overlap_apply(ctx, M->ovl, r, z);
+  if (M->type == 6) return cheb_apply(ctx, M->cheb_A, M->cheb, r, z, /*zero_guess=*/true);
   return ilu_apply(ctx, M->ilu, r, z);
 }
 
@@ -1231,6 +1233,36 @@ int isph_prec_create_blocks_fill(isph_ctx *ctx, const isph_mat *A, int nblocks, 
   return ISPH_SUCCESS;
 }
 
+/* ---- Chebyshev polynomial in D^-1 A ------------------------------------ */
+
+void isph_cheb_params_default(isph_cheb_params *p) {
+  // Ifpack_Chebyshev's defaults: "chebyshev: degree" 1, "chebyshev: ratio eigenvalue" 30; the eigenvalues from rho
+  p->degree = 1; p->ratio = 30.0; p->lambda_max = 0.0; p->lambda_min = 0.0;
+}
+
+static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec *M) {
+  ISPH_REQUIRE(prm->degree >= 1 && prm->degree <= kChebMaxDegree, "Chebyshev: degree must be in [1,16]");
+  ISPH_REQUIRE(prm->ratio > 1.0, "Chebyshev: ratio (\"chebyshev: ratio eigenvalue\") must be > 1");
+  M->type = 6;
+  M->cheb_A = A;
+  return cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
+                    /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb);
+}
+
+int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **Mout) {
+  ISPH_REQUIRE(ctx && A && Mout, "NULL argument");
+  isph_cheb_params def;
+  isph_cheb_params_default(&def);
+  if (!prm) prm = &def;
+  isph_prec *M = new isph_prec();
+  M->n = A->S.nrow;
+  const int rc = prec_chebyshev_init(ctx, A, prm, M);
+  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
+  M->order = A->order;
+  *Mout = M;
+  return ISPH_SUCCESS;
+}
+
 int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int block_size, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && type && Mout, "NULL argument");
   isph_prec *M = new isph_prec();
@@ -1276,8 +1308,15 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
     prm.block = block_size;
     M->type = 3;
     rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
+  } else if (!strncmp(type, "chebyshev", 9) && type[9] >= '1' && type[9] <= '9' &&
+             (type[10] == 0 || (type[9] == '1' && type[10] >= '0' && type[10] <= '6' && type[11] == 0))) {
+    // "chebyshev<d>", d = 1..16: Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults
+    isph_cheb_params prm;
+    isph_cheb_params_default(&prm);
+    prm.degree = atoi(type + 9);
+    rc = prec_chebyshev_init(ctx, A, &prm, M);
   } else {
-    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg)", __FILE__, __LINE__);
+    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>, d = 1..16)", __FILE__, __LINE__);
   }
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;
@@ -1349,6 +1388,7 @@ void isph_prec_destroy(isph_prec *M) {
   if (M->amg) amg_destroy(M->amg);
   if (M->schwarz) schwarz_destroy(M->schwarz);
   if (M->ovl) overlap_destroy(M->ovl);
+  if (M->cheb) cheb_destroy(M->cheb);
   delete M;
 }
 
@@ -1436,6 +1476,7 @@ void isph_amg_params_default(isph_amg_params *p) {
   // PrecondWrapper_ML::setParameters(NULL), ref: precond_ml.h:44-55, plus ML's own defaults
   p->max_levels = 5; p->coarse_max = 128; p->omega = 4.0 / 3.0; p->block = 512; p->sweeps = 1; p->theta = 0.0;
   p->smoother = 0;
+  p->cheb_ratio = 20.0;  // ML's "smoother: Chebyshev alpha"
 }
 
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,

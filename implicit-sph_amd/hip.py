@@ -29,14 +29,14 @@ EXPORTS = [
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
-    "isph_force_from_random_stress",
+    "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev",
 ]
 
 
 class AmgParams(C.Structure):
     """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55)."""
     _fields_ = [("max_levels", C.c_int), ("coarse_max", C.c_int), ("omega", C.c_double), ("block", C.c_int),
-                ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int)]
+                ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -222,6 +222,8 @@ def lib():
         L.isph_amg_params_default.argtypes = [C.c_void_p]
         L.isph_prec_create_amg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_levels.argtypes = [C.c_void_p]
+        L.isph_cheb_params_default.argtypes = [C.c_void_p]
+        L.isph_prec_create_chebyshev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_aggregates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -678,6 +680,7 @@ class Precond:
         the library's row numbering)"""
         self.ctx, self.n = ctx, A.info()["nrow"]
         self.h = C.c_void_p()
+        self.A = A if kind.startswith("chebyshev") else None   # the polynomial applies the matrix: keep it alive
         if block_ptr is not None:
             assert kind.startswith("bjacobi-ilu") and kind[11:].isdigit()
             bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
@@ -769,6 +772,28 @@ class PrecondOverlap(Precond):
         peers, sp, si, rp_ = (np.ascontiguousarray(a, dtype=np.int32) for a in (plan.peers, plan.send_ptr, plan.send_idx, plan.recv_ptr))
         _check(lib().isph_prec_create_overlap(ctx.h, Aext.h, self.n, int(level_of_fill), {"add": 0, "zero": 1}[combine],
                                               len(peers), _ptr(peers), _ptr(sp), _ptr(si), _ptr(rp_), C.byref(self.h)))
+
+
+class ChebParams(C.Structure):
+    """Mirror of isph_cheb_params: Ifpack's "chebyshev: degree", "chebyshev: ratio eigenvalue", "chebyshev: max eigenvalue",
+    "chebyshev: min eigenvalue" (<= 0: from rho = ||D^-1 A||_inf)."""
+    _fields_ = [("degree", C.c_int), ("ratio", C.c_double), ("lambda_max", C.c_double), ("lambda_min", C.c_double)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().isph_cheb_params_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class PrecondChebyshev(Precond):
+    """isph_prec_create_chebyshev: Chebyshev polynomial in D^-1 A ("Precond Type" = "Chebyshev").  The matrix is applied,
+    not copied: it is kept alive here."""
+
+    def __init__(self, ctx, A, degree=1, ratio=30.0, lambda_max=0.0, lambda_min=0.0):
+        self.ctx, self.h, self.n, self.A = ctx, C.c_void_p(), A.info()["nrow"], A
+        prm = ChebParams(degree=int(degree), ratio=float(ratio), lambda_max=float(lambda_max), lambda_min=float(lambda_min))
+        _check(lib().isph_prec_create_chebyshev(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
 
 
 def solve_block(ctx, blocks, b, x, prec=None, params=None, lda=None):

@@ -118,8 +118,25 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
     const std::string type = _param->get("Precond Type", "ILU");
     const int fill = _param->get("fact: level-of-fill", 1);
     const int overlap = _param->get("Overlap Level", 1);
+    if (type == "Chebyshev") {
+      // Ifpack_Chebyshev with its own keys and defaults; a polynomial in D^-1 A has no subdomains and no overlap
+      isph_cheb_params cp;
+      isph_cheb_params_default(&cp);
+      cp.degree = _param->get("chebyshev: degree", cp.degree);
+      cp.ratio = _param->get("chebyshev: ratio eigenvalue", cp.ratio);
+      cp.lambda_max = _param->get("chebyshev: max eigenvalue", cp.lambda_max);
+      cp.lambda_min = _param->get("chebyshev: min eigenvalue", cp.lambda_min);
+      if (_comm.MyPID() == 0 && !_warned) {
+        std::printf(">> PrecondWrapper_Ifpack(HIP): Chebyshev polynomial of degree %d in D^-1 A; \"Overlap Level\" and "
+                    "\"isph: block rows\" mean nothing for this type and are ignored\n", cp.degree);
+        _warned = true;
+      }
+      free();
+      return isph_prec_create_chebyshev(ctx, A, &cp, &_M);
+    }
     if (type != "ILU") {
-      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): Precond Type '%s' is not available; only ILU\n", type.c_str());
+      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): Precond Type '%s' is not available; available: \"ILU\", \"Chebyshev\"\n",
+                   type.c_str());
       return ISPH_FAILURE;
     }
     if (fill < 0 || fill > 8) {

@@ -56,14 +56,20 @@ class PrecondWrapper_ML : public PrecondWrapper {
     // the reference's benchmark protocol asks for (bench-script/hopper/tgv/1728/ml.xml)
     const bool gs = smo == "ML Gauss-Seidel" || smo == "Gauss-Seidel";
     const bool eff = gs && _param->get("smoother: Gauss-Seidel efficient symmetric", false);
-    if (agg != "Uncoupled" || !(smo == "symmetric Gauss-Seidel" || eff)) {
-      std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): only Uncoupled aggregation with symmetric Gauss-Seidel, or Gauss-Seidel "
-                           "with \"smoother: Gauss-Seidel efficient symmetric\", is available\n");
+    // "Chebyshev" ("MLS" is ML's old name for it; the line the benchmark's ml.xml carries commented out): a polynomial of
+    // degree "smoother: sweeps" in D^-1 A on [rho / "smoother: Chebyshev alpha", 1.1 rho]
+    const bool cheb = smo == "Chebyshev" || smo == "MLS";
+    if (agg != "Uncoupled" || !(smo == "symmetric Gauss-Seidel" || eff || cheb)) {
+      std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): aggregation '%s' with smoother '%s' is not available; available: "
+                           "\"Uncoupled\" aggregation with \"symmetric Gauss-Seidel\", with \"Gauss-Seidel\" / \"ML Gauss-Seidel\" "
+                           "plus \"smoother: Gauss-Seidel efficient symmetric\", or with \"Chebyshev\" / \"MLS\"\n",
+                   agg.c_str(), smo.c_str());
       return ISPH_FAILURE;
     }
     isph_amg_params prm;
     isph_amg_params_default(&prm);
-    prm.smoother = eff ? 1 : 0;
+    prm.smoother = cheb ? 2 : eff ? 1 : 0;
+    if (cheb) prm.cheb_ratio = _param->get("smoother: Chebyshev alpha", 20.0);
     // (ml.xml of the benchmark protocol asks for 10 levels; the device hierarchy holds 8, and 3-4 are reached at 10^6 rows)
     prm.max_levels = _param->get("max levels", 5) > 8 ? 8 : _param->get("max levels", 5);
     prm.coarse_max = _param->get("coarse: max size", 128);

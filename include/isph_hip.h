@@ -198,6 +198,8 @@ int isph_spmv_time(isph_ctx *ctx, const isph_mat *A, const double *x_dev, double
  *                   Comm.NumProc() == 1); see isph_prec_create_schwarz
  *   "sa-amg"        PrecondWrapper_ML::create() with its default parameters and no null vector
  *                   (isph_prec_create_amg takes the parameters and the null vector of a singular system)
+ *   "chebyshev<d>"  d = 1..16: Chebyshev polynomial of degree d in D^-1 A, Ifpack's "Precond Type" = "Chebyshev"
+ *                   (isph_prec_create_chebyshev takes the ratio and the eigenvalues)
  * Rebuilt every solve in the reference (solver_lin_belos.h:153,190). */
 /* block_size 0 ("bjacobi-ilu<k>" only): the matrix' own subdomains, i.e. the bricks the assembly sorted the particles
  * into (isph_ctx_set_ordering); fails for a matrix in the caller's numbering. */
@@ -255,6 +257,26 @@ int isph_prec_schwarz_export(isph_ctx *ctx, const isph_prec *M, int *rows, int *
 int isph_prec_create_overlap(isph_ctx *ctx, const isph_mat *Aext, int nlocal, int level_of_fill, int combine, int npeers,
                              const int *peer_rank, const int *send_ptr, const int *send_idx, const int *recv_ptr,
                              isph_prec **M);
+
+/* Ifpack's "Precond Type" = "Chebyshev" (Ifpack_Chebyshev::ApplyInverse; ML_Cheby is the same recurrence): z = p(D^-1 A)
+ * D^-1 r with the Chebyshev polynomial of degree `degree` (1..16) for the interval [alpha, beta],
+ *   lambda = lambda_max (<= 0: rho = max_i sum_j |a_ij| / |a_ii|, an upper bound of the spectrum of D^-1 A; with a halo
+ *   plan the all-reduced maximum over the ranks), beta = 1.1 lambda, alpha = lambda_min (<= 0: lambda / ratio),
+ *   theta = (beta + alpha) / 2, delta = (beta - alpha) / 2, sigma = theta / delta, rho_0 = 1 / sigma,
+ *   step 1:        w = (1 / theta) D^-1 r,  z = w                               (zero start: no matrix product)
+ *   step k = 2..d: rho_k = 1 / (2 sigma - rho_{k-1}),  w = rho_k rho_{k-1} w + (2 rho_k / delta) D^-1 (r - A z),  z += w.
+ * The start is always zero.  Each step k >= 2 is one sweep of the matrix with the update in the kernel's epilogue
+ * (ISPH_CHEB_UNFUSED=1 at create time: a product and a vector kernel instead, for cross-checks).  A fixed linear operator:
+ * any Krylov solver of isph_solve / isph_solve_block may use it.  Works on several ranks through A's halo plan (the create
+ * call is then collective).  A must outlive the preconditioner: it is applied, not copied.  Fails for a matrix with a zero
+ * diagonal entry.  isph_prec_create(type = "chebyshev<d>") is degree d with the other defaults (Ifpack's: degree 1,
+ * ratio 30).  The recurrence is restated from the two packages' algorithm and unpinned against them. */
+typedef struct {
+  int degree;
+  double ratio, lambda_max, lambda_min;
+} isph_cheb_params;
+void isph_cheb_params_default(isph_cheb_params *p);
+int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **M);
 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r /*[h|d]*/,
@@ -546,8 +568,17 @@ typedef struct {
    * (the wrapper's default, precond_ml.h:50-52); 1 = "ML Gauss-Seidel" / "Gauss-Seidel" with "smoother: Gauss-Seidel
    * efficient symmetric" (the ml.xml of the reference's benchmark protocol, bench-script/hopper/tgv/1728/ml.xml):
    * `sweeps` FORWARD sweeps before the coarse correction, `sweeps` BACKWARD sweeps after it.  (With a null vector the
-   * coarsest level is still solved by symmetric sweeps.) */
+   * coarsest level is still solved by symmetric sweeps.)
+   * 2 = "Chebyshev" ("MLS" is ML's old name for it): a Chebyshev polynomial of degree `sweeps` (ML's meaning of
+   * "smoother: sweeps" for this smoother, at most 16) in D^-1 A before and after the coarse correction, on the interval
+   * [rho / cheb_ratio, 1.1 rho] with rho = ||D^-1 A||_inf of the level (see isph_cheb_params for the recurrence).  No
+   * Gauss-Seidel factor is built and `block` is not used; the hierarchy is the one smoother 0 builds, bit for bit.  The
+   * polynomial of one level depends neither on the row order nor on the rank count (rho is all-reduced); the AMG result
+   * as a whole still does, because the Uncoupled aggregates, and with them the cycle, follow the decomposition.  The
+   * cycle is a fixed linear operator, symmetric for a symmetric matrix: "Block CG" may use it.  With a null vector the coarsest level is "solved" by the same polynomial.
+   * Departures from ML: lambda_max is the Anorm bound rho, not ML's 10 CG steps, and the 1.1 boost is kept on top. */
   int smoother;
+  double cheb_ratio; /* smoother 2: "smoother: Chebyshev alpha", lambda_max / lambda_min of the interval; default 20 */
 } isph_amg_params;
 void isph_amg_params_default(isph_amg_params *p);
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,
