@@ -2066,3 +2066,6 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 // smoothed field, electrostatic body force, random stress (isph_smooth_field, isph_electrostatic_force, isph_random_stress_*,
 // isph_force_from_random_stress)
 #include "body_force.hpp"
+
+// ghost atoms and the full neighbour list of one rank (isph_nlist_build, isph_nlist_info, isph_nlist_get, isph_nlist_destroy)
+#include "neighbours.hpp"

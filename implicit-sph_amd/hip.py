@@ -30,6 +30,7 @@ EXPORTS = [
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
     "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev",
+    "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
 ]
 
 
@@ -270,6 +271,11 @@ def lib():
         L.isph_force_from_random_stress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_ulonglong,
                                                     C.c_ulonglong, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                     C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_nlist_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                       C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.isph_nlist_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_nlist_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_nlist_destroy.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1484,3 +1490,71 @@ def force_from_random_stress(ctx, parts, colmap, tag, seed, step, dt, kBT, nu, r
     _check(lib().isph_force_from_random_stress(ctx.h, C.byref(pv), None if plan is None else plan.h, _ptr(tag), int(seed),
                                                int(step), float(dt), float(kBT), _ptr(nu), _ptr(rho), _ptr(f), _ptr(rs), dev))
     return rs
+
+
+class NeighbourList:
+    """isph_nlist: ghost atoms (periodic images) and the full neighbour list of one rank's owned particles, built on the
+    device (isph_nlist_build) -- the device twin of workload.make_cloud.  x [nlocal, 3]: a numpy array or a torch device
+    tensor; the outputs of get() live on the same side.  lo / hi / periodic: the box, `dim` entries each (or three).
+    Raises ValueError before any library call for a wrong x shape, cut <= 0 or a periodic axis shorter than two cuts."""
+
+    def __init__(self, ctx, x, lo, hi, periodic, cut, dim, wrap=True):
+        self.h = C.c_void_p()
+        self.ctx = ctx
+        if dim not in (2, 3):
+            raise ValueError("dim must be 2 or 3")
+        if len(x.shape) != 2 or int(x.shape[1]) != 3:
+            raise ValueError("x must be [nlocal, 3], got %s" % (tuple(x.shape),))
+        if not float(cut) > 0.0:
+            raise ValueError("cut must be positive")
+        lo3 = [float(v) for v in (list(lo) + [0.0] * 3)[:3]]
+        hi3 = [float(v) for v in (list(hi) + [1.0] * 3)[:3]]
+        per3 = [int(bool(v)) for v in (list(periodic) + [0] * 3)[:3]]
+        for a in range(dim):
+            if per3[a] and hi3[a] - lo3[a] < 2.0 * float(cut):
+                raise ValueError("periodic axis %d is shorter than two cuts" % a)
+        x = _f64(x)
+        if _is_torch(x) and not x.is_contiguous():
+            x = x.contiguous()
+        self.dev = _on_device(x)
+        self._like = x
+        self.dim, self.nlocal = dim, int(x.shape[0])
+        _check(lib().isph_nlist_build(ctx.h, dim, self.nlocal, _ptr(x), (C.c_double * 3)(*lo3), (C.c_double * 3)(*hi3),
+                                      (C.c_int * 3)(*per3), float(cut), int(bool(wrap)), self.dev, C.byref(self.h)))
+
+    @property
+    def info(self):
+        """dict(nlocal, nghost, entries, fits32)"""
+        a = (C.c_longlong * 4)()
+        _check(lib().isph_nlist_info(self.h, a))
+        return dict(nlocal=int(a[0]), nghost=int(a[1]), entries=int(a[2]), fits32=int(a[3]))
+
+    def _empty(self, shape, kind):
+        if self.dev:
+            import torch
+            return torch.empty(shape, dtype=getattr(torch, kind), device=self._like.device)
+        return np.empty(shape, dtype=getattr(np, kind))
+
+    def get(self, ptr64=False):
+        """dict(x [nall, 3], owner_index [nall], neigh_ptr [nlocal + 1], neigh_idx [entries]).  neigh_ptr is int32 while
+        the entries fit (the rule of workload.make_cloud) unless ptr64 is set, else int64."""
+        i = self.info
+        nall = i["nlocal"] + i["nghost"]
+        wide = bool(ptr64) or not i["fits32"]
+        x, own = self._empty((nall, 3), "float64"), self._empty((nall,), "int32")
+        nptr = self._empty((i["nlocal"] + 1,), "int64" if wide else "int32")
+        nidx = self._empty((i["entries"],), "int32")
+        _check(lib().isph_nlist_get(self.ctx.h, self.h, _ptr(x), _ptr(own), _ptr(nptr) if wide else None,
+                                    None if wide else _ptr(nptr), _ptr(nidx), self.dev))
+        return dict(x=x, owner_index=own, neigh_ptr=nptr, neigh_idx=nidx)
+
+    def close(self):
+        if self.h:
+            lib().isph_nlist_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

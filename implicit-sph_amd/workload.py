@@ -168,6 +168,42 @@ def make_cloud(x_owned, box, h, cut, dim=3, like=None):
     return out
 
 
+def make_cloud_device(ctx, x_owned, box, h, cut, dim=3, like=None):
+    """make_cloud on the device (hip.NeighbourList / isph_nlist_build): the same dict with the same keys, bit for bit the
+    same arrays, for owned positions x_owned [nlocal, 3] that are a torch device tensor (a numpy array is uploaded first).
+    x, type, neigh_ptr, neigh_idx and owner_index are device tensors (rho, nu, tag, v and owner_rank too); rho / nu / type
+    are gathered from `like` (a make_tgv dict, numpy or device arrays) on the device.  Nothing but the two counts comes
+    back to the host.  hip.particles_view and the operator wrappers take the dict like an uploaded make_cloud dict."""
+    import torch
+    from . import hip
+    L = [float(v) for v in box]
+    if dim not in (2, 3) or len(L) < dim or not float(cut) > 0.0 or any(L[a] < 2.0 * float(cut) for a in range(dim)):
+        raise ValueError("make_cloud_device: bad arguments (box shorter than two cuts?)")
+    if not hip._is_torch(x_owned):
+        x_owned = torch.from_numpy(np.ascontiguousarray(x_owned, dtype=np.float64)).to(torch.device("cuda", 0))
+    nl = hip.NeighbourList(ctx, x_owned, [0.0] * dim, L[:dim], [1] * dim, cut, dim, wrap=True)
+    g = nl.get()
+    info = nl.info
+    nl.close()
+    n, nall = info["nlocal"], info["nlocal"] + info["nghost"]
+    dev = x_owned.device
+    own = g["owner_index"]
+    spec = like["spec"] if like is not None else None
+    out = dict(spec=spec, dim=dim, nlocal=n, nall=nall, x=g["x"], v=torch.zeros((nall, 3), dtype=torch.float64, device=dev),
+               tag=own + 1, type=torch.ones(nall, dtype=torch.int32, device=dev),
+               owner_rank=torch.zeros(nall, dtype=torch.int32, device=dev), owner_index=own,
+               neigh_ptr=g["neigh_ptr"], neigh_idx=g["neigh_idx"], h=float(h), cut=float(cut))
+    if like is not None:
+        idx = own.to(torch.int64)
+        for k in ("rho", "nu", "type"):
+            src = like[k]
+            if not hip._is_torch(src):
+                src = torch.from_numpy(np.ascontiguousarray(src)).to(dev)
+            out[k] = src[:n][idx].contiguous()
+        out["dt"] = like.get("dt")
+    return out
+
+
 def single_rank_colmap(parts):
     """Matrix column of every particle on one rank: ghosts are periodic images,
     their column is the owner's local id (Epetra LID of the shared tag)."""

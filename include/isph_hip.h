@@ -796,6 +796,43 @@ int isph_force_from_random_stress(isph_ctx *ctx, const isph_particles *P, const 
                                   const double *nu, const double *rho, double *f_inout,
                                   double *rs_out /*[nlocal][6] or NULL*/, int on_device);
 
+/* ---- ghost atoms and the full neighbour list ----------------------------- */
+
+/* What LAMMPS does between two calls of PairISPH::compute when the particles have moved, for ONE rank: wrap into the box,
+ * create the ghost atoms (periodic images within the cut of a face) and rebuild the full neighbour list (Neighbor::build).
+ * The device twin of isph_cloud_build (isph_workload.h): for a fully periodic box with lo = 0 the result equals it bit for
+ * bit -- the same ghosts in the same order, the same positions, owners, offsets and list entries.
+ *
+ *   wrap (periodic axes, wrap != 0)   t = x - lo, P = hi - lo: r = fmod(t, P); r < 0: r += P; r >= P: r = 0; x = r + lo
+ *   images  on a periodic axis a shift +1 when x_a - lo_a < cut, -1 when x_a >= hi_a - cut; every non-zero combination of
+ *           the shifts, z outermost and x innermost, ascending, owners ascending; position x_a + s_a P_a (z = 0 in 2-D)
+ *   list    j != i with ((d0 d0) + d1 d1) + d2 d2 < cut cut, every product and sum rounded (no fused multiply-add);
+ *           every row in ascending particle index; offsets in the CSR form of isph_particles
+ *
+ * A non-periodic axis gets no wrap and no images.  Off-rank ghosts (LAMMPS' Comm) are the caller's.  Every device buffer
+ * comes from the library's pool; only the two counts (ghosts, list entries) are read back during the build. */
+typedef struct isph_nlist isph_nlist;
+
+/* x: [nlocal][3] [h|d].  lo/hi/periodic: the caller's box (LAMMPS domain->boxlo/boxhi/periodicity).
+ * wrap != 0: owned positions are first wrapped into [lo, hi) on periodic axes.
+ * cut: one radius (the caller passes its largest pair cut + skin).
+ * Fails (-1, isph_last_error) for dim not 2|3, cut <= 0, or a periodic axis shorter than 2 cut. */
+int isph_nlist_build(isph_ctx *ctx, int dim, int nlocal, const double *x,
+                     const double lo[3], const double hi[3], const int periodic[3],
+                     double cut, int wrap, int on_device, isph_nlist **out);
+
+/* info: [0] nlocal  [1] nghost  [2] list entries  [3] 1 when the entries fit 32-bit offsets (fewer than 2^31 - 1) */
+int isph_nlist_info(const isph_nlist *nl, long long info[4]);
+
+/* copies out; any pointer may be NULL; neigh_ptr (32-bit) only when info[3]; all [h|d] per on_device.
+ * x_all [nall][3], owner_index [nall], neigh_ptr64 / neigh_ptr [nlocal + 1], neigh_idx [entries].
+ * isph_ctx_hold_neighbours is keyed on the caller's list arrays: a caller that copies a rebuilt list into the arrays of the
+ * list before must drop the hold first (isph_ctx_hold_neighbours(ctx, 0)), or the operators keep reading the old layout. */
+int isph_nlist_get(isph_ctx *ctx, const isph_nlist *nl, double *x_all, int *owner_index,
+                   long long *neigh_ptr64, int *neigh_ptr, int *neigh_idx, int on_device);
+
+int isph_nlist_destroy(isph_ctx *ctx, isph_nlist *nl);
+
 #ifdef __cplusplus
 }
 #endif

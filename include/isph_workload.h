@@ -68,7 +68,9 @@ long long isph_tgv_fill64(const isph_tgv_spec *s, double *x, double *v, int *tag
  * particles have moved (Neighbor::build with `neighbor ${skin} bin`, bench-script/hopper/tgv/1728/tgv-3d-p24.lmp:95-96).
  * x_all == NULL: returns the number of ghosts.  Otherwise fills x_all[nall][3] (owned first), owner_index[nall],
  * neigh_ptr[nlocal+1] and -- when neigh_idx != NULL -- the lists (ascending particle index per row); returns the
- * number of list entries (call once with neigh_idx == NULL to size it).  < 0: bad arguments (L < 2 cut). */
+ * number of list entries (call once with neigh_idx == NULL to size it).  < 0: bad arguments (L < 2 cut).
+ * Device twin: isph_nlist_build (isph_hip.h) produces the same arrays bit for bit from positions on the device, and
+ * also takes a box away from the origin and non-periodic axes. */
 long long isph_cloud_build(int dim, int nlocal, const double *x, const double *L, double cut, double *x_all,
                            int *owner_index, long long *neigh_ptr, int *neigh_idx);
 

@@ -2,13 +2,15 @@
 pressure-correction time steps on the device, Symmetric operator family, device-resident arrays: computePre (volumes,
 G_i, L_i) -> wall normals + particle number density (with walls) -> continuum surface force -> Helmholtz with that force
 (theta = 1/2, dim right-hand sides, FGMRES + block ILU(0)) -> Poisson -> zero mean -> corrections -> advance.  The
-neighbour list of every step comes from the host (LAMMPS' job): workload.make_cloud on the moved particles.
+neighbour list of every step comes from the host (LAMMPS' job): workload.make_cloud on the moved particles -- or, with
+--neighbours device, from workload.make_cloud_device: the positions then never leave the GPU between two steps.
 
 Then the four surface-tension sweeps beside gradient + divergence on the same particles, HIP events around each call on
 the context's stream, neighbour layout held, warm, median and spread of --repeats calls.
 
     python scripts/droplet_step.py --dim 2 --N 512
-    python scripts/droplet_step.py --dim 3 --N 64"""
+    python scripts/droplet_step.py --dim 3 --N 64
+    python scripts/droplet_step.py --dim 2 --N 512 --neighbours device"""
 import argparse
 import os
 import sys
@@ -28,6 +30,8 @@ ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--repeats", type=int, default=20)
 ap.add_argument("--walls", action="store_true", help="liquid drop on a solid slab (2-D)")
 ap.add_argument("--jitter", type=float, default=0.05)
+ap.add_argument("--neighbours", default="host", choices=["host", "device"],
+                help="where ghosts and neighbour list of the moved particles are rebuilt between two steps")
 args = ap.parse_args()
 
 dim = args.dim
@@ -51,6 +55,8 @@ def sync():
 
 
 def upload(parts):
+    if hip._is_torch(parts["x"]):                   # built on the device: nothing to upload
+        return parts, parts["owner_index"], parts["owner_index"].to(torch.int64)
     d = dict(parts)
     for k in ("x", "type", "neigh_ptr", "neigh_idx"):
         d[k] = T(parts[k])
@@ -58,6 +64,7 @@ def upload(parts):
 
 
 parts = p0
+like_d = dict(p0, **{k: T(p0[k]) for k in ("type", "rho", "nu")})
 x_own, typ_own = p0["x"][:n].copy(), p0["type"][:n].copy()
 v = torch.zeros((n, 3), dtype=torch.float64, device=dev)
 p = torch.zeros(n, dtype=torch.float64, device=dev)
@@ -65,7 +72,11 @@ g = np.zeros(3)
 print("droplet %d-D, %d particles, %d phases%s, h = %.4g, cut = %.4g, dt = %.4g"
       % (dim, n, 2, " + walls" if args.walls else "", h, cut, dt))
 for step in range(args.steps):
-    if step > 0:                                   # the host rebuilds ghosts and lists from the moved particles
+    if step > 0 and args.neighbours == "device":   # ghosts and lists of the moved particles, rebuilt where they are
+        tn = sync()
+        parts = workload.make_cloud_device(ctx, x_own, (L,) * dim, h, cut, dim=dim, like=like_d)
+        print("step %d: ghosts + neighbour list on the device %.2f ms" % (step, (sync() - tn) * 1e3))
+    elif step > 0:                                 # the host rebuilds ghosts and lists from the moved particles
         like = dict(p0, type=np.r_[typ_own, p0["type"][n:]])
         parts = workload.make_cloud(x_own, (L,) * dim, h, cut, dim=dim, like=like)
     dp, colmap, own = upload(parts)
@@ -112,7 +123,7 @@ for step in range(args.steps):
     t6 = sync()
     ctx.hold_neighbours(False)
     v, p = vd, pd
-    x_own = xd.cpu().numpy()
+    x_own = xd if args.neighbours == "device" else xd.cpu().numpy()
     print("step %d: computePre %.2f  normals %.2f  surface tension %.2f  helmholtz %.2f [%d its, conv %d]  poisson %.2f [%d its, conv %d]"
           "  correct+advance %.2f  total %.2f ms   max|f| %.3g  max|v| %.3g"
           % (step, (t1 - t0) * 1e3, (t2 - t1) * 1e3, (t3 - t2) * 1e3, (t4 - t3) * 1e3, ih.iters, ih.converged, (t5 - t4) * 1e3,

@@ -15,7 +15,9 @@ are handed to them as Fluid, which is what their bit-test filters see in the ref
 Then one fluctuating TGV step (isph_force_from_random_stress -> Helmholtz -> Poisson -> corrections), and the two new
 sweeps beside the launches they replace on the same particles: HIP events around each call on the context's stream,
 neighbour layout held, 3 warm-up calls, median and spread of --repeats calls.  Linear solves: FGMRES(50); block ILU(0) for
-the Helmholtz system, --prec for the applied potential and the pressure Poisson equation.
+the Helmholtz system, --prec for the applied potential and the pressure Poisson equation.  --neighbours device: ghosts and
+neighbour list of the fluctuating step are rebuilt from the particle positions on the device (workload.make_cloud_device)
+instead of coming from the host generator.
 
     python scripts/electroosmotic_step.py --dim 2 --N 1024
     python scripts/electroosmotic_step.py --dim 3 --N 96"""
@@ -37,6 +39,8 @@ ap.add_argument("--N", type=int, default=1024, help="cells per box edge")
 ap.add_argument("--repeats", type=int, default=20)
 ap.add_argument("--prec", default="sa-amg", choices=["sa-amg", "bjacobi-ilu0"], help="of the two scalar elliptic solves")
 ap.add_argument("--max-iters", type=int, default=4000, help="of every linear solve (GMRES(50) + block ILU(0))")
+ap.add_argument("--neighbours", default="host", choices=["host", "device"],
+                help="where ghosts and neighbour list of the fluctuating step are built")
 args = ap.parse_args()
 
 FLUID, SOLID, BUF_D, BUF_N, ALL = 99, 12, 32, 64, 127
@@ -67,6 +71,8 @@ def sync():
 
 
 def upload(parts):
+    if hip._is_torch(parts["x"]):                   # built on the device: nothing to upload
+        return parts, parts["owner_index"], parts["owner_index"].to(torch.int64)
     d = dict(parts)
     for k in ("x", "type", "neigh_ptr", "neigh_idx"):
         d[k] = T(parts[k])
@@ -216,10 +222,16 @@ ctx.hold_neighbours(False)
 # ---- the fluctuating TGV step -----------------------------------------------------------------------------------------
 sp = spec(workload.JITTER)
 parts = workload.make_tgv(sp)
-n, nall = parts["nlocal"], parts["nall"]
+n = parts["nlocal"]
+v0 = parts["v"][:n]
+if args.neighbours == "device":                     # the same particles: ghosts and list rebuilt where the positions are
+    tn = sync()
+    parts = workload.make_cloud_device(ctx, T(parts["x"][:n]), (L,) * dim, sp.h, sp.cut, dim=dim, like=parts)
+    print("ghosts + neighbour list on the device %.2f ms" % ((sync() - tn) * 1e3))
+nall = parts["nall"]
 dp, colmap, own = upload(parts)
 ghost = lambda a: a[own].contiguous()
-tag = T(parts["tag"][:n])
+tag = parts["tag"][:n].contiguous() if hip._is_torch(parts["tag"]) else T(parts["tag"][:n])
 rho = torch.full((nall,), 1.0, dtype=torch.float64, device=dev)
 nu = torch.full((nall,), 0.1, dtype=torch.float64, device=dev)
 dt, kBT, seed = sp.dt, 1e-6, 20240917
@@ -232,7 +244,7 @@ t1 = sync()
 f = torch.zeros((n, 3), dtype=torch.float64, device=dev)
 hip.force_from_random_stress(ctx, dp, colmap, tag, seed, 0, dt, kBT, nu[:n].contiguous(), rho[:n].contiguous(), f, vfrac)
 t2 = sync()
-v, p = T(parts["v"][:n]), torch.zeros(n, dtype=torch.float64, device=dev)
+v, p = T(v0), torch.zeros(n, dtype=torch.float64, device=dev)
 vstar, p, text = momentum_step(dp, colmap, own, None, vfrac, G, Lc, f, v, p, rho, nu, dt)
 t3 = sync()
 print("computePre %.2f  random stress %.2f  %s  total %.2f ms   max|f| %.3g  net force / sum|f| %.2e"
