@@ -983,6 +983,12 @@ int isph_mat_info(const isph_mat *A, long long info[6]) {
   return ISPH_SUCCESS;
 }
 
+int isph_mat_column_bits(isph_ctx *ctx, const isph_mat *A, int *bits) {
+  ISPH_REQUIRE(ctx && A && bits, "NULL argument");
+  *bits = (!A->local && !A->aux && sell_cols16(ctx, A->S)) ? 16 : 32;  // the condition of spmv_dev
+  return ISPH_SUCCESS;
+}
+
 int isph_mat_export_rows(isph_ctx *ctx, const isph_mat *A, int row_begin, int nrows, long long *rowptr, int *colidx,
                          double *val, long long capacity) {
   ISPH_REQUIRE(ctx && A && rowptr && colidx && val, "NULL argument");
@@ -1009,7 +1015,8 @@ int isph_mat_export_rows(isph_ctx *ctx, const isph_mat *A, int row_begin, int nr
       const long long len1 = rp1[1];
       ord.resize((size_t)len1); tc.assign(colidx + rowptr[i], colidx + rowptr[i] + len1); tv.assign(val + rowptr[i], val + rowptr[i] + len1);
       for (long long k = 0; k < len1; ++k) { if (tc[(size_t)k] < S.nrow) tc[(size_t)k] = hperm[(size_t)tc[(size_t)k]]; ord[(size_t)k] = (int)k; }
-      std::sort(ord.begin(), ord.end(), [&](int a, int c) { return tc[(size_t)a] < tc[(size_t)c]; });
+      // stable: duplicate columns keep the order k_sell_sort_rows gave them (their order in the caller's row)
+      std::stable_sort(ord.begin(), ord.end(), [&](int a, int c) { return tc[(size_t)a] < tc[(size_t)c]; });
       for (long long k = 0; k < len1; ++k) { colidx[rowptr[i] + k] = tc[(size_t)ord[(size_t)k]]; val[rowptr[i] + k] = tv[(size_t)ord[(size_t)k]]; }
       rowptr[i + 1] = rowptr[i] + len1;
     }
@@ -1076,7 +1083,8 @@ int isph_mat_export_csr(isph_ctx *ctx, const isph_mat *A, int *rowptr, int *coli
     for (long long k = 0; k < nnz; ++k)
       if (ci[(size_t)k] < S.nrow) ci[(size_t)k] = hperm[(size_t)ci[(size_t)k]];
   }
-  // sort columns inside each row (Epetra OptimizeStorage order)
+  // sort columns inside each row (Epetra OptimizeStorage order); stable: duplicate columns keep the order
+  // k_sell_sort_rows gave them (their order in the caller's row)
   std::vector<int> perm;
   long long q = 0;
   for (int i = 0; i < S.nrow; ++i) {
@@ -1084,7 +1092,7 @@ int isph_mat_export_csr(isph_ctx *ctx, const isph_mat *A, int *rowptr, int *coli
     const long long b = rp[(size_t)r], e = rp[(size_t)r + 1];
     perm.resize((size_t)(e - b));
     std::iota(perm.begin(), perm.end(), 0);
-    std::sort(perm.begin(), perm.end(), [&](int a, int c) { return ci[(size_t)(b + a)] < ci[(size_t)(b + c)]; });
+    std::stable_sort(perm.begin(), perm.end(), [&](int a, int c) { return ci[(size_t)(b + a)] < ci[(size_t)(b + c)]; });
     rowptr[i] = (int)q;
     for (long long k = b; k < e; ++k, ++q) {
       colidx[q] = ci[(size_t)(b + perm[(size_t)(k - b)])];

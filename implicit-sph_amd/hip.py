@@ -18,7 +18,7 @@ KERNELS = {"wendland": 0, "quintic": 1, "cubic": 2}
 
 EXPORTS = [
     "isph_ctx_create", "isph_comm_unique_id", "isph_ctx_create_dist", "isph_ctx_create_hostcomm", "isph_ctx_sync", "isph_ctx_destroy", "isph_pool_trim", "isph_pool_set_cap", "isph_set_exact_stream_threshold", "isph_pool_cached_bytes", "isph_pool_info", "isph_halo_create", "isph_halo_forward", "isph_halo_destroy", "isph_prec_create_overlap",
-    "isph_last_error", "isph_mat_create_csr", "isph_mat_create_csr_bjacobi", "isph_mat_create_csr_blocks", "isph_mat_create_csr_coords", "isph_mat_create_csr_coords_bjacobi", "isph_ingress_info", "isph_mat_set_halo", "isph_mat_info", "isph_mat_export_csr", "isph_mat_export_rows",
+    "isph_last_error", "isph_mat_create_csr", "isph_mat_create_csr_bjacobi", "isph_mat_create_csr_blocks", "isph_mat_create_csr_coords", "isph_mat_create_csr_coords_bjacobi", "isph_ingress_info", "isph_mat_set_halo", "isph_mat_info", "isph_mat_export_csr", "isph_mat_export_rows", "isph_mat_column_bits",
     "isph_mat_destroy", "isph_spmv", "isph_spmv_time", "isph_prec_create", "isph_prec_create_blocks", "isph_prec_create_blocks_fill", "isph_prec_apply",
     "isph_prec_export_ilu", "isph_prec_nnz", "isph_prec_info", "isph_prec_destroy", "isph_solver_params_default", "isph_solve",
     "isph_ctx_set_profile", "isph_ctx_hold_neighbours", "isph_ctx_profile_read", "isph_ctx_set_ordering", "isph_ctx_set_periodic_box", "isph_mat_ordering_info", "isph_mat_ordering", "isph_mat_ordering_faces", "isph_ctx_halo_profile_read", "isph_ctx_comm_info", "isph_device_identity", "isph_assemble_poisson", "isph_assemble_helmholtz", "isph_assemble_solute_transport", "isph_assemble_applied_potential", "isph_compute_volumes", "isph_compute_pnd", "isph_compute_corrections", "isph_gradient", "isph_divergence", "isph_correct_velocity_pressure",
@@ -184,6 +184,7 @@ def lib():
         L.isph_mat_info.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_mat_export_csr.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_mat_export_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong]
+        L.isph_mat_column_bits.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_mat_destroy.argtypes = [C.c_void_p]
         L.isph_spmv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_spmv_time.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
@@ -625,6 +626,12 @@ class Matrix:
         v = np.zeros(cap)
         _check(lib().isph_mat_export_rows(self.ctx.h, self.h, int(row_begin), int(nrows), _ptr(rp), _ptr(ci), _ptr(v), cap))
         return rp, ci[:rp[-1]], v[:rp[-1]]
+
+    def column_bits(self):
+        """isph_mat_column_bits: 16 when the product reads the windowed 16-bit columns (built on first use), else 32"""
+        b = C.c_int()
+        _check(lib().isph_mat_column_bits(self.ctx.h, self.h, C.byref(b)))
+        return b.value
 
     def sampled_product(self, x, nsamples=64, rows_per_sample=64, seed=0):
         """(A x) on `nsamples` runs of `rows_per_sample` consecutive rows, computed ON THE HOST from exported rows: an

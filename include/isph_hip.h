@@ -170,6 +170,11 @@ int isph_mat_export_csr(isph_ctx *ctx, const isph_mat *A, int *rowptr, int *coli
  * No reference counterpart (Epetra_CrsMatrix::ExtractMyRowView is the closest). */
 int isph_mat_export_rows(isph_ctx *ctx, const isph_mat *A, int row_begin, int nrows, long long *rowptr, int *colidx,
                          double *val, long long capacity);
+/* *bits = 16 when the product of this matrix reads the windowed 16-bit copy of its columns (every 64-row slice touches at
+ * most 64 aligned windows of 1024 columns, padding included), 32 when it reads the 32-bit columns (some slice touches more,
+ * or the matrix is one of the library's own transfer / coarse operators).  Asks exactly as the product does, so the
+ * 16-bit copy is built on the first call if no product has built it yet.  No reference counterpart. */
+int isph_mat_column_bits(isph_ctx *ctx, const isph_mat *A, int *bits);
 void isph_mat_destroy(isph_mat *A);
 
 /* y = A x  (Epetra_CrsMatrix::Apply incl. the ghost Import; ref: solver_lin.h:133).
@@ -178,7 +183,7 @@ void isph_mat_destroy(isph_mat *A);
 int isph_spmv(isph_ctx *ctx, const isph_mat *A, const double *x /*[h|d]*/,
               double *y /*[h|d]*/, int on_device);
 /* Time `reps` back-to-back SpMV launches with HIP events on the library
- * stream; returns the average kernel time in milliseconds.  variant 0 = the production kernel; 1..5 = experimental
+ * stream; returns the average kernel time in milliseconds.  variant 0 = the production kernel; 1..6 = experimental
  * instantiations of the 32-bit-column kernel (unroll / cache policy), for scripts/spmv_variants.py only. */
 int isph_spmv_time(isph_ctx *ctx, const isph_mat *A, const double *x_dev, double *y_dev,
                    int reps, int variant, double *avg_ms);
