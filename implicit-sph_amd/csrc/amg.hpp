@@ -68,6 +68,7 @@ struct AmgLevel {
 struct isph_amg {
   int nlev = 0, block = 512, sweeps = 1, singular = 0;
   int gs_eff = 0;         // isph_amg_params::smoother == 1: forward sweeps before, backward sweeps after the coarse correction
+  int cheb_value_bits = 64;   // smoother == 2: 32 = every level's polynomial sweeps a float plane of its operator (chebyshev.hpp)
   int cheb = 0;           // isph_amg_params::smoother == 2: Chebyshev polynomial of degree `sweeps` in D^-1 A, before and after
   int coarse_smooth = 0;  // coarsest level solved by the smoother: singular system (precond_ml.h:97-127) or a level too
                           // large for the dense inverse (no coarsening possible: isolated / Dirichlet rows dominate)
@@ -1779,7 +1780,10 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
                "smoother must be 0 (symmetric Gauss-Seidel), 1 (Gauss-Seidel, efficient symmetric) or 2 (Chebyshev)");
   ISPH_REQUIRE(prm->smoother != 2 || prm->sweeps <= kChebMaxDegree, "Chebyshev smoother: sweeps is the polynomial degree, at most 16");
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_ratio > 1.0, "Chebyshev smoother: cheb_ratio (\"smoother: Chebyshev alpha\") must be > 1");
+  ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_value_bits == 0 || prm->cheb_value_bits == 64 || prm->cheb_value_bits == 32,
+               "Chebyshev smoother: cheb_value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
   isph_amg *G = new isph_amg();
+  G->cheb_value_bits = (prm->smoother == 2 && prm->cheb_value_bits == 32) ? 32 : 64;
   G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
   G->gs_eff = prm->smoother == 1;
   G->cheb = prm->smoother == 2;
@@ -1898,7 +1902,9 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     // without ghost columns A (x + P e) = A x + (A P) e: the cycle updates the residual with the product already at hand
     // (a fifth of A's entries) instead of a second sweep over A
     // (not on a rank that sends to neighbours: the product it saves is also this rank's part of their exchange)
-    if (rc == ISPH_SUCCESS && ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
+    // (not with cheb_value_bits 32 either: the post-smoother is the polynomial of fl32(A) and forms b - fl32(A) x itself)
+    if (rc == ISPH_SUCCESS && G->cheb_value_bits != 32 &&
+        ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
       rc = mat_from_device_csr(ctx, AP.n, AP.m, AP.rp.p, AP.ci.p, AP.v.p, AP.nnz, &L->APm, /*rows_sorted=*/true);
       if (rc == ISPH_SUCCESS) L->APm->local = true;
     }
@@ -1945,7 +1951,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
       if (!last || G->coarse_smooth) {
         const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, 0.0, 0.0, /*empty_ok=*/l > 0, /*collective=*/dist,
-                                  /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb);
+                                  /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits);
         if (rc == ISPH_SUCCESS) rc = r2;
       }
       continue;
@@ -2089,8 +2095,11 @@ inline int amg_vcycle(isph_ctx *ctx, const isph_amg *G, int l, const double *b, 
   int first = 0;
   if (G->cheb) {
     // r still holds b - A x of before the correction: r -= (A P) e is the residual the polynomial's first step needs
-    if (L->APm) ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));
-    return cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/false, L->APm ? (const double *)L->r.p : nullptr);
+    // (cheb_value_bits 32: that residual is the one of A, and the smoother is the polynomial of fl32(A) -- its first step
+    // forms b - fl32(A) x itself, one more sweep of the float plane, or the cycle would be neither operator)
+    const bool shortcut = L->APm != nullptr && G->cheb_value_bits != 32;
+    if (shortcut) ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));
+    return cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/false, shortcut ? (const double *)L->r.p : nullptr);
   }
   if (L->APm) {
     // r still holds b - A x of before the correction: r -= (A P) e, then the first post-smoothing sweep uses it

@@ -16,7 +16,15 @@
 // in the epilogue); the product-free first step of a zero guess (and of a residual the caller already holds) is a
 // streaming kernel (k_cheby_first).  ISPH_CHEB_UNFUSED=1 (read at set-up) runs the same recurrence as
 // spmv_dev(.., badd = b, alpha = -1) plus a streaming update: the cross-check and the timing baseline of the fused step.
+//
+// value_bits = 32: the polynomial of A~ = fl32(A).  Set-up rounds every stored value of A to the nearest float into a
+// plane of its own (k_cheby_round: same element positions as S.val, 4 B per stored entry, owned by the Cheb), and D^-1,
+// rho, the interval and the scalars all come from that plane; the sweeps then stream 4 B instead of 8 B of value per
+// entry, convert to double and run the fma chain of the double kernel in the same order.  Vectors, accumulators and
+// the update stay double: the result is the fp64 recurrence on A~, a fixed linear operator like the one on A.
+// 100^3: 147.8 against 207.1 us per step for 0.62 of the bytes -- no longer HBM-bound.
 #pragma once
+#include <cfloat>
 #include "solver.hpp"
 
 namespace isph {
@@ -24,15 +32,17 @@ namespace isph {
 constexpr int kChebMaxDegree = 16;
 
 struct Cheb {
-  int n = 0, degree = 1, unfused = 0;
+  int n = 0, degree = 1, unfused = 0, value_bits = 64;
   double lambda = 0.0, alpha = 0.0, beta = 0.0;
   double c1[kChebMaxDegree], c2[kChebMaxDegree];   // step k (0-based): w = c1[k] w + c2[k] D^-1 (b - A y)
   DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
+  DevBuf<float> val32;                               // value_bits 32: fl32 of S.val, position by position (padding 0)
 };
+
 
 inline void cheb_destroy(Cheb *C) {
   if (!C) return;
-  C->dinv.release(); C->w.release(); C->t.release(); C->r.release();
+  C->dinv.release(); C->w.release(); C->t.release(); C->r.release(); C->val32.release();
   delete C;
 }
 
@@ -56,12 +66,33 @@ __device__ __forceinline__ double cheb_increment(double c1, double c2, double w_
   return fma(c1, w_old, c2 * t);
 }
 
+// ---- value_bits 32: the float plane.  v32[p] = (float)val[p] (round to nearest even, subnormals kept) for every stored
+// position, padding included (0 stays 0); out[2] = 1 when a magnitude exceeds FLT_MAX.  n2 = stored / 2 (a slice holds a
+// multiple of 128 entries), one double2 in and one float2 out per trip.
+__global__ __launch_bounds__(kBlock) void k_cheby_round(long long n2, const double *__restrict__ val, float *__restrict__ v32,
+                                                        unsigned long long *__restrict__ out) {
+  const double2 *__restrict__ in = reinterpret_cast<const double2 *>(val);
+  float2 *__restrict__ o = reinterpret_cast<float2 *>(v32);
+  bool over = false;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long long)gridDim.x * blockDim.x) {
+    const double2 v = in[i];
+    over = over || fabs(v.x) > (double)FLT_MAX || fabs(v.y) > (double)FLT_MAX;
+    float2 f;
+    f.x = (float)v.x;
+    f.y = (float)v.y;
+    o[i] = f;
+  }
+  if (over) atomicMax(&out[2], 1ull);
+}
+
 // ---- set-up: 1 / a_ii, rho = max_i sum_j |a_ij| / |a_ii| (ghost columns included: the row is the row of the global
 // matrix, whichever rank owns its columns), a flag for a zero diagonal.  One wave per slice, lane == row.
 // out[0]: bit pattern of rho (a non-negative double orders like its bits), out[1]: 1 when a diagonal entry is zero.
 // empty_ok: a row without any entry (coarse operators of the AMG can have them) gets dinv = 0 and is left alone.
+// VT = float: the values of the float plane, widened -- the diagonal and rho of fl32(A).
+template <class VT>
 __global__ __launch_bounds__(kBlock) void k_cheby_setup(int nrow, int nslices, const long long *__restrict__ slice_off,
-                                                        const int *__restrict__ scol, const double *__restrict__ sval,
+                                                        const int *__restrict__ scol, const VT *__restrict__ sval,
                                                         int empty_ok, double *__restrict__ dinv,
                                                         unsigned long long *__restrict__ out) {
   const int slice = blockIdx.x * (kBlock / kWave) + (threadIdx.x >> 6);
@@ -72,7 +103,7 @@ __global__ __launch_bounds__(kBlock) void k_cheby_setup(int nrow, int nslices, c
   double d = 0.0, s = 0.0;
   for (int k = 0; k < w; ++k) {   // padding: value 0
     const long long p = sell_pos(off, lane, k);
-    const double v = sval[p];
+    const double v = (double)sval[p];
     if (scol[p] == row) d += v;
     s += fabs(v);
   }
@@ -102,16 +133,18 @@ __global__ __launch_bounds__(kBlock) void k_cheby_setup(int nrow, int nslices, c
 // the per-wave LDS table) or of k_sell_spmv (32-bit columns: the aux operators of the AMG), non-temporal matrix loads,
 // XCD remap; then  w_i = c1 w_i + c2 dinv_i (b_i - (A y)_i),  yout_i = y_i + w_i.
 // yout must NOT alias y: other waves still gather y.  c1 == 0 (first step): w is not read.
-template <bool C16, bool LIST, bool GHOST>
+// VT = float: sval is the float plane (64 x float2 = 512 B per wave load), each value widened before its fma.
+template <bool C16, bool LIST, bool GHOST, class VT>
 __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslices, int nblocks_padded,
                                                             const long long *__restrict__ slice_off,
                                                             const void *__restrict__ cols, const int *__restrict__ wtab,
-                                                            const double *__restrict__ sval, const double *__restrict__ y,
+                                                            const VT *__restrict__ sval, const double *__restrict__ y,
                                                             const double *__restrict__ yg, const double *__restrict__ b,
                                                             const double *__restrict__ dinv, double *__restrict__ w,
                                                             double *__restrict__ yout, double c1, double c2,
                                                             const int *__restrict__ slice_list) {
   constexpr int UNROLL = 8;
+  typedef typename SellPair<VT>::type VT2;
   __shared__ int tab[C16 ? kBlock / kWave : 1][64];
   const int blk = xcd_remap(blockIdx.x, nblocks_padded);
   const int wave = threadIdx.x >> 6;
@@ -127,13 +160,13 @@ __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslice
   const int *__restrict__ tw = tab[C16 ? wave : 0];
   const long long off = slice_off[slice];
   const int npair = (int)((slice_off[slice + 1] - off) >> 7);
-  const double2 *__restrict__ v = reinterpret_cast<const double2 *>(sval + off) + lane;
+  const VT2 *__restrict__ v = reinterpret_cast<const VT2 *>(sval + off) + lane;
   const unsigned *__restrict__ c16 = reinterpret_cast<const unsigned *>(static_cast<const unsigned short *>(cols) + off) + lane;
   const int2 *__restrict__ c32 = reinterpret_cast<const int2 *>(static_cast<const int *>(cols) + off) + lane;
   double acc0 = 0.0, acc1 = 0.0;
   int q = 0;
   for (; q + UNROLL <= npair; q += UNROLL) {
-    double2 vv[UNROLL];
+    VT2 vv[UNROLL];
     int ca[UNROLL], cb[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -160,12 +193,12 @@ __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslice
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      acc0 = fma(vv[u].x, xa[u], acc0);
-      acc1 = fma(vv[u].y, xb[u], acc1);
+      acc0 = fma((double)vv[u].x, xa[u], acc0);
+      acc1 = fma((double)vv[u].y, xb[u], acc1);
     }
   }
   for (; q < npair; ++q) {
-    const double2 vv = v[q * 64];
+    const VT2 vv = v[q * 64];
     int ca, cb;
     if (C16) {
       const unsigned cc = c16[q * 64];
@@ -177,8 +210,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslice
       ca = cc.x;
       cb = cc.y;
     }
-    acc0 = fma(vv.x, x_at<GHOST>(y, yg, nrow, ca), acc0);
-    acc1 = fma(vv.y, x_at<GHOST>(y, yg, nrow, cb), acc1);
+    acc0 = fma((double)vv.x, x_at<GHOST>(y, yg, nrow, ca), acc0);
+    acc1 = fma((double)vv.y, x_at<GHOST>(y, yg, nrow, cb), acc1);
   }
   const int row = slice * kSlice + lane;
   if (row < nrow) {
@@ -242,36 +275,48 @@ __global__ __launch_bounds__(kBlock) void k_cheby_update(int n, double c1, doubl
 // collective: every rank of the context calls this together (stand-alone: a context with a communicator; AMG: a
 // hierarchy across ranks) -- rho is the all-reduced maximum and a failure on one rank is a failure on all.
 // prior_failure: this rank has already failed and only takes part in the collective step.
+// value_bits: 64, or 32 = the polynomial of fl32(A) (the caller has checked the value).
 inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio, double lambda_max, double lambda_min,
-                      bool empty_ok, bool collective, bool prior_failure, Cheb **out) {
+                      bool empty_ok, bool collective, bool prior_failure, Cheb **out, int value_bits = 64) {
   const Sell &S = A->S;
   int rc = ISPH_SUCCESS;
   Cheb *C = new Cheb();
   C->n = S.nrow;
   C->degree = degree;
+  C->value_bits = value_bits == 32 ? 32 : 64;
+  const bool f32 = C->value_bits == 32;
   const char *env = getenv("ISPH_CHEB_UNFUSED");
   C->unfused = env && env[0] == '1';
   DevTmp<unsigned long long> flag;
   double h[2] = {0.0, prior_failure ? 1.0 : 0.0};   // rho, failure
   if (!prior_failure) {
     const size_t m = (size_t)(S.nrow > 0 ? S.nrow : 1) + 64;
-    rc = flag.reserve(2);
+    rc = flag.reserve(3);
     if (rc == ISPH_SUCCESS) rc = C->dinv.reserve(m);
+    if (rc == ISPH_SUCCESS && f32) rc = C->val32.reserve((size_t)(S.stored > 0 ? S.stored : 1));
     if (rc == ISPH_SUCCESS) rc = C->w.reserve(m);
     if (rc == ISPH_SUCCESS) rc = C->t.reserve(m);
     if (rc == ISPH_SUCCESS && C->unfused) rc = C->r.reserve(m);
-    if (rc == ISPH_SUCCESS && hipMemsetAsync(flag.p, 0, 2 * sizeof(unsigned long long), ctx->stream) != hipSuccess)
+    if (rc == ISPH_SUCCESS && hipMemsetAsync(flag.p, 0, 3 * sizeof(unsigned long long), ctx->stream) != hipSuccess)
       rc = fail("memset failed", __FILE__, __LINE__);
-    unsigned long long hb[2] = {0ull, 0ull};
+    unsigned long long hb[3] = {0ull, 0ull, 0ull};
     if (rc == ISPH_SUCCESS) {
-      if (S.nslices > 0)
-        hipLaunchKernelGGL(k_cheby_setup, dim3((S.nslices + 3) / 4), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices,
+      if (f32 && S.stored > 0)   // one streaming pass over S.val; the set-up kernel below then reads the plane
+        hipLaunchKernelGGL(k_cheby_round, dim3(stream_grid(S.stored / 2)), dim3(kBlock), 0, ctx->stream, S.stored / 2, (const double *)S.val.p, C->val32.p, flag.p);
+      if (S.nslices > 0 && f32)
+        hipLaunchKernelGGL((k_cheby_setup<float>), dim3((S.nslices + 3) / 4), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices,
+                           (const long long *)S.slice_off.p, (const int *)S.col.p, (const float *)C->val32.p, empty_ok ? 1 : 0,
+                           C->dinv.p, flag.p);
+      else if (S.nslices > 0)
+        hipLaunchKernelGGL((k_cheby_setup<double>), dim3((S.nslices + 3) / 4), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices,
                            (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, empty_ok ? 1 : 0,
                            C->dinv.p, flag.p);
       if (hipMemcpyAsync(hb, flag.p, sizeof(hb), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
           hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
         rc = fail("Chebyshev set-up failed", __FILE__, __LINE__);
     }
+    if (rc == ISPH_SUCCESS && hb[2] != 0ull)
+      rc = fail("Chebyshev: a matrix value exceeds the range of single precision (value_bits = 32 rounds the values to float)", __FILE__, __LINE__);
     if (rc == ISPH_SUCCESS && hb[1] != 0ull)
       rc = fail("Chebyshev: the matrix has a zero diagonal entry (the polynomial acts on D^-1 A)", __FILE__, __LINE__);
     memcpy(&h[0], &hb[0], sizeof(double));
@@ -292,20 +337,37 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
   return ISPH_SUCCESS;
 }
 
-template <bool LIST, bool GHOST>
-inline void cheb_step_launch(isph_ctx *ctx, const Sell &S, bool c16, int nsl, const int *list, const Cheb *C, const double *b,
-                             const double *y, const double *yg, double *yout, double c1, double c2) {
+template <bool LIST, bool GHOST, class VT>
+inline void cheb_step_launch(isph_ctx *ctx, const Sell &S, bool c16, int nsl, const int *list, const Cheb *C, const VT *val,
+                             const double *b, const double *y, const double *yg, double *yout, double c1, double c2) {
   if (nsl <= 0) return;
   int nbp = 0;
   const int grid = spmv_grid(nsl, &nbp);
   if (c16)
-    hipLaunchKernelGGL((k_sell_cheby_step<true, LIST, GHOST>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
-                       (const long long *)S.slice_off.p, (const void *)S.col16.p, (const int *)S.wtab.p, (const double *)S.val.p, y, yg,
+    hipLaunchKernelGGL((k_sell_cheby_step<true, LIST, GHOST, VT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       (const long long *)S.slice_off.p, (const void *)S.col16.p, (const int *)S.wtab.p, val, y, yg,
                        b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
   else
-    hipLaunchKernelGGL((k_sell_cheby_step<false, LIST, GHOST>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
-                       (const long long *)S.slice_off.p, (const void *)S.col.p, (const int *)nullptr, (const double *)S.val.p, y, yg,
+    hipLaunchKernelGGL((k_sell_cheby_step<false, LIST, GHOST, VT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       (const long long *)S.slice_off.p, (const void *)S.col.p, (const int *)nullptr, val, y, yg,
                        b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
+}
+
+// the fused sweep over the double values of the matrix or over the float plane of the preconditioner
+template <class VT>
+inline int cheb_step_fused(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const VT *val, bool halo, bool c16, const double *b,
+                           const double *y, double *yout, double c1, double c2) {
+  const Sell &S = A->S;
+  if (!halo) {
+    cheb_step_launch<false, false, VT>(ctx, S, c16, S.nslices, nullptr, C, val, b, y, nullptr, yout, c1, c2);
+  } else {
+    const isph_halo &H = A->halo;
+    ISPH_CHECK(halo_begin(ctx, A, y));
+    cheb_step_launch<true, false, VT>(ctx, S, c16, H.n_int, H.list_int.p, C, val, b, y, nullptr, yout, c1, c2);
+    ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
+    cheb_step_launch<true, true, VT>(ctx, S, c16, H.n_bnd, H.list_bnd.p, C, val, b, y, ctx->xghost.p, yout, c1, c2);
+  }
+  return ISPH_SUCCESS;
 }
 
 // one step with a matrix product: yout = y + w, w = c1 w + c2 D^-1 (b - A y); yout != y.  With a halo plan the exchange
@@ -314,7 +376,8 @@ inline int cheb_step(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const doub
                      double c2) {
   const Sell &S = A->S;
   if (C->unfused) {
-    ISPH_CHECK(spmv_dev(ctx, A, y, C->r.p, nullptr, b, -1.0));   // r = b - A y
+    // r = b - A y (value_bits 32: the product reads the float plane)
+    ISPH_CHECK(spmv_dev(ctx, A, y, C->r.p, nullptr, b, -1.0, C->value_bits == 32 ? (const float *)C->val32.p : nullptr));
     hipLaunchKernelGGL(k_cheby_update, dim3(stream_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, S.nrow, c1, c2,
                        (const double *)C->dinv.p, (const double *)C->r.p, C->w.p, y, yout);
     ISPH_CHECK_HIP(hipGetLastError());
@@ -323,15 +386,8 @@ inline int cheb_step(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const doub
   ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);   // a sweep of the caller's operator, like spmv_dev's
   const bool halo = !A->local && (S.ncol != S.nrow || A->halo.nsend > 0);
   const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
-  if (!halo) {
-    cheb_step_launch<false, false>(ctx, S, c16, S.nslices, nullptr, C, b, y, nullptr, yout, c1, c2);
-  } else {
-    const isph_halo &H = A->halo;
-    ISPH_CHECK(halo_begin(ctx, A, y));
-    cheb_step_launch<true, false>(ctx, S, c16, H.n_int, H.list_int.p, C, b, y, nullptr, yout, c1, c2);
-    ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
-    cheb_step_launch<true, true>(ctx, S, c16, H.n_bnd, H.list_bnd.p, C, b, y, ctx->xghost.p, yout, c1, c2);
-  }
+  if (C->value_bits == 32) ISPH_CHECK(cheb_step_fused<float>(ctx, A, C, (const float *)C->val32.p, halo, c16, b, y, yout, c1, c2));
+  else ISPH_CHECK(cheb_step_fused<double>(ctx, A, C, (const double *)S.val.p, halo, c16, b, y, yout, c1, c2));
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }

@@ -1245,16 +1245,19 @@ int isph_prec_create_blocks_fill(isph_ctx *ctx, const isph_mat *A, int nblocks, 
 
 void isph_cheb_params_default(isph_cheb_params *p) {
   // Ifpack_Chebyshev's defaults: "chebyshev: degree" 1, "chebyshev: ratio eigenvalue" 30; the eigenvalues from rho
-  p->degree = 1; p->ratio = 30.0; p->lambda_max = 0.0; p->lambda_min = 0.0;
+  p->degree = 1; p->ratio = 30.0; p->lambda_max = 0.0; p->lambda_min = 0.0; p->value_bits = 64;
 }
 
 static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec *M) {
   ISPH_REQUIRE(prm->degree >= 1 && prm->degree <= kChebMaxDegree, "Chebyshev: degree must be in [1,16]");
   ISPH_REQUIRE(prm->ratio > 1.0, "Chebyshev: ratio (\"chebyshev: ratio eigenvalue\") must be > 1");
+  ISPH_REQUIRE(prm->value_bits == 0 || prm->value_bits == 64 || prm->value_bits == 32,
+               "Chebyshev: value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
   M->type = 6;
   M->cheb_A = A;
   return cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
-                    /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb);
+                    /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb,
+                    prm->value_bits == 32 ? 32 : 64);
 }
 
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **Mout) {
@@ -1271,11 +1274,30 @@ int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb
   return ISPH_SUCCESS;
 }
 
+int isph_prec_value_bits(const isph_prec *M) {
+  if (!M) return 0;
+  if (M->type == 6 && M->cheb) return M->cheb->value_bits;
+  if (M->type == 3 && M->amg && M->amg->cheb) return M->amg->cheb_value_bits;
+  return 0;
+}
+
+// "chebyshev<d>" or "chebyshev<d>-f32", d = 1..16; *bits = 64 or 32
+static bool parse_chebyshev_type(const char *type, int *degree, int *bits) {
+  if (strncmp(type, "chebyshev", 9) != 0 || type[9] < '1' || type[9] > '9') return false;
+  const char *tail = type + 10;
+  if (type[9] == '1' && *tail >= '0' && *tail <= '6') ++tail;
+  if (*tail != 0 && strcmp(tail, "-f32") != 0) return false;
+  *degree = atoi(type + 9);
+  *bits = *tail ? 32 : 64;
+  return true;
+}
+
 int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int block_size, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && type && Mout, "NULL argument");
   isph_prec *M = new isph_prec();
   M->n = A->S.nrow;
   int rc = ISPH_SUCCESS;
+  int cheb_degree = 0, cheb_bits = 64;
   if (!strcmp(type, "none")) {
     M->type = 0;
   } else if (!strcmp(type, "jacobi")) {
@@ -1316,15 +1338,16 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
     prm.block = block_size;
     M->type = 3;
     rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
-  } else if (!strncmp(type, "chebyshev", 9) && type[9] >= '1' && type[9] <= '9' &&
-             (type[10] == 0 || (type[9] == '1' && type[10] >= '0' && type[10] <= '6' && type[11] == 0))) {
-    // "chebyshev<d>", d = 1..16: Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults
+  } else if (parse_chebyshev_type(type, &cheb_degree, &cheb_bits)) {
+    // "chebyshev<d>", d = 1..16: Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults;
+    // "chebyshev<d>-f32": the same with value_bits = 32
     isph_cheb_params prm;
     isph_cheb_params_default(&prm);
-    prm.degree = atoi(type + 9);
+    prm.degree = cheb_degree;
+    prm.value_bits = cheb_bits;
     rc = prec_chebyshev_init(ctx, A, &prm, M);
   } else {
-    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>, d = 1..16)", __FILE__, __LINE__);
+    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16)", __FILE__, __LINE__);
   }
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;
@@ -1485,6 +1508,7 @@ void isph_amg_params_default(isph_amg_params *p) {
   p->max_levels = 5; p->coarse_max = 128; p->omega = 4.0 / 3.0; p->block = 512; p->sweeps = 1; p->theta = 0.0;
   p->smoother = 0;
   p->cheb_ratio = 20.0;  // ML's "smoother: Chebyshev alpha"
+  p->cheb_value_bits = 64;
 }
 
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,

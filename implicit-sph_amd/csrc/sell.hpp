@@ -395,17 +395,24 @@ __device__ __forceinline__ double x_at(const double *__restrict__ x, const doubl
   return x[c];
 }
 
-template <int UNROLL, bool DOT, bool NT = false, bool LIST = false, bool GHOST = false>
+// VT = float: sval is a float copy of the values in the same positions (the value plane of a Chebyshev preconditioner with
+// value_bits 32, chebyshev.hpp); each value is widened before its fma, everything else is the double kernel.
+template <class VT> struct SellPair;
+template <> struct SellPair<double> { typedef double2 type; };
+template <> struct SellPair<float> { typedef float2 type; };
+
+template <int UNROLL, bool DOT, bool NT = false, bool LIST = false, bool GHOST = false, class VT = double>
 __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int nblocks_padded,
                                                       const long long *__restrict__ slice_off,
                                                       const int *__restrict__ scol,
-                                                      const double *__restrict__ sval,
+                                                      const VT *__restrict__ sval,
                                                       const double *__restrict__ x, double *__restrict__ y,
                                                       const double *__restrict__ nvec,
                                                       double *__restrict__ dot_partial,
                                                       const int *__restrict__ slice_list = nullptr,
                                                       const double *__restrict__ xg = nullptr,
                                                       const double *badd = nullptr, double alpha = 1.0) {
+  typedef typename SellPair<VT>::type VT2;
   const int b = xcd_remap(blockIdx.x, nblocks_padded);
   int slice = b * (kBlock / kWave) + (threadIdx.x >> 6);
   if (slice >= nslices) return;
@@ -413,12 +420,12 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int
   const int lane = threadIdx.x & 63;
   const long long off = slice_off[slice];
   const int npair = (int)((slice_off[slice + 1] - off) >> 7);
-  const double2 *__restrict__ v = reinterpret_cast<const double2 *>(sval + off) + lane;
+  const VT2 *__restrict__ v = reinterpret_cast<const VT2 *>(sval + off) + lane;
   const int2 *__restrict__ c = reinterpret_cast<const int2 *>(scol + off) + lane;
   double acc0 = 0.0, acc1 = 0.0;
   int q = 0;
   for (; q + UNROLL <= npair; q += UNROLL) {
-    double2 vv[UNROLL];
+    VT2 vv[UNROLL];
     int2 cc[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -440,15 +447,15 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      acc0 = fma(vv[u].x, xa[u], acc0);
-      acc1 = fma(vv[u].y, xb[u], acc1);
+      acc0 = fma((double)vv[u].x, xa[u], acc0);
+      acc1 = fma((double)vv[u].y, xb[u], acc1);
     }
   }
   for (; q < npair; ++q) {
-    const double2 vv = v[q * 64];
+    const VT2 vv = v[q * 64];
     const int2 cc = c[q * 64];
-    acc0 = fma(vv.x, x_at<GHOST>(x, xg, nrow, cc.x), acc0);
-    acc1 = fma(vv.y, x_at<GHOST>(x, xg, nrow, cc.y), acc1);
+    acc0 = fma((double)vv.x, x_at<GHOST>(x, xg, nrow, cc.x), acc0);
+    acc1 = fma((double)vv.y, x_at<GHOST>(x, xg, nrow, cc.y), acc1);
   }
   const int row = slice * kSlice + lane;
   double r = acc0 + acc1;
@@ -531,18 +538,19 @@ __global__ __launch_bounds__(kBlock) void k_sell_compress_cols(int slice_begin, 
   }
 }
 
-template <int UNROLL, bool DOT, bool LIST = false, bool GHOST = false>
+template <int UNROLL, bool DOT, bool LIST = false, bool GHOST = false, class VT = double>
 __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, int nblocks_padded,
                                                         const long long *__restrict__ slice_off,
                                                         const unsigned short *__restrict__ c16,
                                                         const int *__restrict__ wtab,
-                                                        const double *__restrict__ sval,
+                                                        const VT *__restrict__ sval,
                                                         const double *__restrict__ x, double *__restrict__ y,
                                                         const double *__restrict__ nvec,
                                                         double *__restrict__ dot_partial,
                                                         const int *__restrict__ slice_list = nullptr,
                                                         const double *__restrict__ xg = nullptr,
                                                         const double *badd = nullptr, double alpha = 1.0) {
+  typedef typename SellPair<VT>::type VT2;
   __shared__ int tab[kBlock / kWave][64];
   const int b = xcd_remap(blockIdx.x, nblocks_padded);
   const int wave = threadIdx.x >> 6;
@@ -556,12 +564,12 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, i
   const int *__restrict__ tw = tab[wave];
   const long long off = slice_off[slice];
   const int npair = (int)((slice_off[slice + 1] - off) >> 7);
-  const double2 *__restrict__ v = reinterpret_cast<const double2 *>(sval + off) + lane;
+  const VT2 *__restrict__ v = reinterpret_cast<const VT2 *>(sval + off) + lane;
   const unsigned *__restrict__ c = reinterpret_cast<const unsigned *>(c16 + off) + lane;  // two 16-bit columns
   double acc0 = 0.0, acc1 = 0.0;
   int q = 0;
   for (; q + UNROLL <= npair; q += UNROLL) {
-    double2 vv[UNROLL];
+    VT2 vv[UNROLL];
     unsigned cc[UNROLL];
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
@@ -578,16 +586,16 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, i
     }
 #pragma unroll
     for (int u = 0; u < UNROLL; ++u) {
-      acc0 = fma(vv[u].x, xa[u], acc0);
-      acc1 = fma(vv[u].y, xb[u], acc1);
+      acc0 = fma((double)vv[u].x, xa[u], acc0);
+      acc1 = fma((double)vv[u].y, xb[u], acc1);
     }
   }
   for (; q < npair; ++q) {
-    const double2 vv = v[q * 64];
+    const VT2 vv = v[q * 64];
     const unsigned cc = c[q * 64];
     const unsigned lo = cc & 0xffffu, hi = cc >> 16;
-    acc0 = fma(vv.x, x_at<GHOST>(x, xg, nrow, tw[lo >> 10] | (int)(lo & 1023u)), acc0);
-    acc1 = fma(vv.y, x_at<GHOST>(x, xg, nrow, tw[hi >> 10] | (int)(hi & 1023u)), acc1);
+    acc0 = fma((double)vv.x, x_at<GHOST>(x, xg, nrow, tw[lo >> 10] | (int)(lo & 1023u)), acc0);
+    acc1 = fma((double)vv.y, x_at<GHOST>(x, xg, nrow, tw[hi >> 10] | (int)(hi & 1023u)), acc1);
   }
   const int row = slice * kSlice + lane;
   double r = acc0 + acc1;

@@ -29,7 +29,7 @@ EXPORTS = [
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
-    "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev",
+    "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
 ]
 
@@ -37,7 +37,8 @@ EXPORTS = [
 class AmgParams(C.Structure):
     """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55)."""
     _fields_ = [("max_levels", C.c_int), ("coarse_max", C.c_int), ("omega", C.c_double), ("block", C.c_int),
-                ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double)]
+                ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double),
+                ("cheb_value_bits", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -226,6 +227,8 @@ def lib():
         L.isph_prec_amg_levels.argtypes = [C.c_void_p]
         L.isph_cheb_params_default.argtypes = [C.c_void_p]
         L.isph_prec_create_chebyshev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.isph_prec_value_bits.argtypes = [C.c_void_p]
+        L.isph_prec_value_bits.restype = C.c_int
         L.isph_prec_amg_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_aggregates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -713,6 +716,12 @@ class Precond:
         _check(lib().isph_prec_apply(self.ctx.h, self.h, _ptr(r), _ptr(z), _on_device(r, z)))
         return z
 
+    @property
+    def value_bits(self):
+        """isph_prec_value_bits: 32 or 64 = the width of the matrix values the Chebyshev sweeps read (the Chebyshev
+        preconditioner, or an AMG with the Chebyshev smoother); 0 for every other preconditioner."""
+        return int(lib().isph_prec_value_bits(self.h))
+
     def info(self):
         a = (C.c_longlong * 4)()
         _check(lib().isph_prec_info(self.ctx.h, self.h, a))
@@ -789,8 +798,9 @@ class PrecondOverlap(Precond):
 
 class ChebParams(C.Structure):
     """Mirror of isph_cheb_params: Ifpack's "chebyshev: degree", "chebyshev: ratio eigenvalue", "chebyshev: max eigenvalue",
-    "chebyshev: min eigenvalue" (<= 0: from rho = ||D^-1 A||_inf)."""
-    _fields_ = [("degree", C.c_int), ("ratio", C.c_double), ("lambda_max", C.c_double), ("lambda_min", C.c_double)]
+    "chebyshev: min eigenvalue" (<= 0: from rho = ||D^-1 A||_inf); value_bits 64 | 32 (the polynomial of fl32(A))."""
+    _fields_ = [("degree", C.c_int), ("ratio", C.c_double), ("lambda_max", C.c_double), ("lambda_min", C.c_double),
+                ("value_bits", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -801,11 +811,13 @@ class ChebParams(C.Structure):
 
 class PrecondChebyshev(Precond):
     """isph_prec_create_chebyshev: Chebyshev polynomial in D^-1 A ("Precond Type" = "Chebyshev").  The matrix is applied,
-    not copied: it is kept alive here."""
+    not copied: it is kept alive here.  value_bits = 32: the sweeps read the matrix values rounded to float (a plane the
+    preconditioner owns); the result is the fp64 recurrence on fl32(A)."""
 
-    def __init__(self, ctx, A, degree=1, ratio=30.0, lambda_max=0.0, lambda_min=0.0):
+    def __init__(self, ctx, A, degree=1, ratio=30.0, lambda_max=0.0, lambda_min=0.0, value_bits=64):
         self.ctx, self.h, self.n, self.A = ctx, C.c_void_p(), A.info()["nrow"], A
-        prm = ChebParams(degree=int(degree), ratio=float(ratio), lambda_max=float(lambda_max), lambda_min=float(lambda_min))
+        prm = ChebParams(degree=int(degree), ratio=float(ratio), lambda_max=float(lambda_max), lambda_min=float(lambda_min),
+                         value_bits=int(value_bits))
         _check(lib().isph_prec_create_chebyshev(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
 
 

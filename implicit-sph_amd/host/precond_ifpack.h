@@ -126,9 +126,18 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       cp.ratio = _param->get("chebyshev: ratio eigenvalue", cp.ratio);
       cp.lambda_max = _param->get("chebyshev: max eigenvalue", cp.lambda_max);
       cp.lambda_min = _param->get("chebyshev: min eigenvalue", cp.lambda_min);
+      // device-side extension (not a reference key): 32 = the sweeps read the matrix values rounded to float, the
+      // polynomial is that of fl32(A) (isph_cheb_params::value_bits).  Read for this type only.
+      cp.value_bits = _param->get("isph: chebyshev value bits", 64);
+      if (cp.value_bits != 64 && cp.value_bits != 32) {
+        std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): \"isph: chebyshev value bits\" = %d is not available; available: 64, 32\n",
+                     cp.value_bits);
+        return ISPH_FAILURE;
+      }
       if (_comm.MyPID() == 0 && !_warned) {
-        std::printf(">> PrecondWrapper_Ifpack(HIP): Chebyshev polynomial of degree %d in D^-1 A; \"Overlap Level\" and "
-                    "\"isph: block rows\" mean nothing for this type and are ignored\n", cp.degree);
+        std::printf(">> PrecondWrapper_Ifpack(HIP): Chebyshev polynomial of degree %d in D^-1 A (%d-bit matrix values); "
+                    "\"Overlap Level\" and \"isph: block rows\" mean nothing for this type and are ignored\n", cp.degree,
+                    cp.value_bits);
         _warned = true;
       }
       free();

@@ -70,6 +70,14 @@ class PrecondWrapper_ML : public PrecondWrapper {
     isph_amg_params_default(&prm);
     prm.smoother = cheb ? 2 : eff ? 1 : 0;
     if (cheb) prm.cheb_ratio = _param->get("smoother: Chebyshev alpha", 20.0);
+    // device-side extension (not a reference key), read for the Chebyshev smoother only: 32 = the smoother's sweeps read
+    // the level operators rounded to float (isph_amg_params::cheb_value_bits); the hierarchy itself stays fp64
+    if (cheb) prm.cheb_value_bits = _param->get("isph: chebyshev value bits", 64);
+    if (cheb && prm.cheb_value_bits != 64 && prm.cheb_value_bits != 32) {
+      std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): \"isph: chebyshev value bits\" = %d is not available; available: 64, 32\n",
+                   prm.cheb_value_bits);
+      return ISPH_FAILURE;
+    }
     // (ml.xml of the benchmark protocol asks for 10 levels; the device hierarchy holds 8, and 3-4 are reached at 10^6 rows)
     prm.max_levels = _param->get("max levels", 5) > 8 ? 8 : _param->get("max levels", 5);
     prm.coarse_max = _param->get("coarse: max size", 128);

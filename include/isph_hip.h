@@ -205,6 +205,7 @@ int isph_spmv_time(isph_ctx *ctx, const isph_mat *A, const double *x_dev, double
  *                   (isph_prec_create_amg takes the parameters and the null vector of a singular system)
  *   "chebyshev<d>"  d = 1..16: Chebyshev polynomial of degree d in D^-1 A, Ifpack's "Precond Type" = "Chebyshev"
  *                   (isph_prec_create_chebyshev takes the ratio and the eigenvalues)
+ *   "chebyshev<d>-f32"  the same with value_bits = 32: the polynomial of A rounded to single precision
  * Rebuilt every solve in the reference (solver_lin_belos.h:153,190). */
 /* block_size 0 ("bjacobi-ilu<k>" only): the matrix' own subdomains, i.e. the bricks the assembly sorted the particles
  * into (isph_ctx_set_ordering); fails for a matrix in the caller's numbering. */
@@ -275,13 +276,28 @@ int isph_prec_create_overlap(isph_ctx *ctx, const isph_mat *Aext, int nlocal, in
  * any Krylov solver of isph_solve / isph_solve_block may use it.  Works on several ranks through A's halo plan (the create
  * call is then collective).  A must outlive the preconditioner: it is applied, not copied.  Fails for a matrix with a zero
  * diagonal entry.  isph_prec_create(type = "chebyshev<d>") is degree d with the other defaults (Ifpack's: degree 1,
- * ratio 30).  The recurrence is restated from the two packages' algorithm and unpinned against them. */
+ * ratio 30).  The recurrence is restated from the two packages' algorithm and unpinned against them.
+ * value_bits (not a reference parameter): 64 (the default; 0 means the same) or 32.  With 32 the preconditioner is exactly
+ * the fp64 recurrence above applied to A~ = fl32(A) in place of A: the create call rounds every stored value of A to the
+ * nearest float (ties to even, subnormals kept) into a plane the preconditioner owns (4 B per stored entry), and D^-1,
+ * rho, the interval and the 2d scalars all come from A~.  The sweeps stream 4 B instead of 8 B of value per entry and
+ * widen each value before its fma; vectors, accumulators and the update stay double.  A~ is a fixed linear operator,
+ * symmetric when A is, so every Krylov solver may still use it; the outer iteration works on the true A.  The create
+ * call fails when a value exceeds the range of single precision, and with "zero diagonal" when a diagonal entry rounds
+ * to 0.  A must still outlive the preconditioner (columns and slice offsets are A's).  Any other value is refused.
+ * Measured at 100^3 (profiles/chebyshev_f32_100cubed.txt): one step 147.8 against 207.1 us, "chebyshev3"
+ * 13.8 against 16.4 ms per solve with 22 iterations either way; not measured on more than one rank.
+ * Call isph_cheb_params_default FIRST and then change fields: the struct grows at its tail. */
 typedef struct {
   int degree;
   double ratio, lambda_max, lambda_min;
+  int value_bits;
 } isph_cheb_params;
 void isph_cheb_params_default(isph_cheb_params *p);
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **M);
+/* 32 or 64: the width of the matrix values the Chebyshev sweeps of M read (a Chebyshev preconditioner, or an AMG with
+ * smoother = 2); 0 for every other preconditioner and for NULL. */
+int isph_prec_value_bits(const isph_prec *M);
 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r /*[h|d]*/,
@@ -563,7 +579,8 @@ int isph_solve_block(isph_ctx *ctx, int dim, const isph_mat *const *blocks, cons
  * More than one rank (a context with a communicator, A with its halo plan set): the call is COLLECTIVE.  Aggregates and
  * prolongator stay on the rank (Uncoupled), the coarse operators are P^T A P with the whole A -- ghost columns and a halo
  * plan per level, derived from A's -- and the coarsest systems of all ranks are solved as one (a dense inverse on every
- * rank; the smoother when nullvec is given).  Every rank must call it, with the same parameters. */
+ * rank; the smoother when nullvec is given).  Every rank must call it, with the same parameters.
+ * Call isph_amg_params_default FIRST and then change fields: the struct grows at its tail. */
 typedef struct {
   int max_levels, coarse_max;
   double omega;
@@ -584,6 +601,13 @@ typedef struct {
    * Departures from ML: lambda_max is the Anorm bound rho, not ML's 10 CG steps, and the 1.1 boost is kept on top. */
   int smoother;
   double cheb_ratio; /* smoother 2: "smoother: Chebyshev alpha", lambda_max / lambda_min of the interval; default 20 */
+  /* smoother 2 only (not read otherwise): 64 (default; 0 means the same) or 32 = the polynomial of every level (the
+   * coarsest included when a null vector is given) is that of fl32(A_l), see isph_cheb_params::value_bits.  Only the
+   * smoother's sweeps read floats: aggregates, P, the Galerkin products, residuals, restriction, prolongation and the
+   * dense coarse inverse stay fp64, and the hierarchy is bit for bit the one cheb_value_bits = 64 builds.  The
+   * post-smoother then forms b - fl32(A) x in a sweep of its own (the A P shortcut holds the residual of A); on one rank
+   * that takes back what the floats save: 29.4 against 29.9 ms per solve at 100^3, 26 iterations either way. */
+  int cheb_value_bits;
 } isph_amg_params;
 void isph_amg_params_default(isph_amg_params *p);
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,
