@@ -23,8 +23,27 @@
 //              of 64-entry chunks laid out in execution order (see k_ilu_schedule).
 //
 // Pipeline per build:  k_ilu_extract [-> k x (k_iluk_merge count, write)] -> k_ilu_schedule -> k_ilu_factor
+//                      [-> k_ilu_round_stream, value_bits 32]
 // Apply:               k_ilu_solve_stream (one wave per block)
+//
+// value_bits = 32 (isph_ilu_params, "bjacobi-ilu<k>-f32"; off by default): additive.  Extraction, symbolic phase, schedule
+// and factorisation are the ones above and leave the same bits (fval, dinv, sc, si, sperm); one streaming pass behind the
+// factorisation writes svf[i] = (float)sv[i] for the chunks every block uses, and float instantiations of the two solve
+// kernels stream svf -- 6 B instead of 10 B per stream entry -- and widen each value before its fma.  The pivots dinv,
+// the vectors in LDS, the accumulator, the DPP scan and the update stay fp64: the result is exactly the fp64 triangular
+// solves with the strict-L and strict-U entries replaced by their float roundings (symmetric only up to that rounding
+// when A is symmetric: fl32(u_ij) != d_i fl32(l_ji)).  sv is GIVEN BACK to the pool once svf is written: nothing reads it
+// after set-up -- the export and isph_prec_nnz read the row-major factor fval.  Only PART 0 has a float instantiation;
+// the Gauss-Seidel streams of the AMG (PART 1 / 2) stay fp64.
+// Measured at 100^3 on the library's bricks, widths alternated in one process (profiles/ilu_f32_100cubed.txt,
+// 2026-10-18): one application 127.9 (125.4 - 134.7) against 146.4 (144.6 - 149.0) us for 0.615 of the bytes ("bjacobi-
+// ilu0"), 299.0 (293.1 - 326.2) against 331.2 (326.6 - 344.0) us for 0.607 ("bjacobi-ilu1") -- time 0.87 and 0.90: the
+// solve is bound by its per-block dependency chain, not by the stream bytes; create + solve with the benchmark's
+// protocol 37.00 against 38.02 ms (71 iterations both) and 99.47 against 100.93 ms (63 both); the rounding pass +0.03 ..
+// +0.3 ms per create.
 #pragma once
+#include <cfloat>
+#include <cmath>
 #include "core.hpp"
 #include "sell.hpp"
 
@@ -34,6 +53,8 @@ struct isph_ilu {
   isph::DevBuf<int> fcol, flen, fdiag, err;
   isph::DevBuf<double> fval;
   isph::DevBuf<double> sv;        // chunk stream values   [nchunks*64]
+  int value_bits = 64;            // 32: the solves stream svf and sv is given back once svf is written (see k_ilu_round_stream)
+  isph::DevBuf<float> svf;        // value_bits 32: fl32 of sv, position by position, same capacity (ilu_size_stream's rule)
   isph::DevBuf<unsigned short> sc;  // chunk stream words (16 bit per entry)
   isph::DevBuf<unsigned char> si;   // one byte per chunk: END | need << 1
   isph::DevBuf<unsigned short> sperm;  // [nblocks][2][B] row -> position in the solve order of the L / U direction
@@ -1048,10 +1069,12 @@ __global__ void k_sgs_pivots(int n, const long long *__restrict__ frp, const dou
 // PART (Gauss-Seidel streams only, amg.hpp): 0 = both directions; 1 = the L part alone, z = (D+L_B)^-1 r (the stream
 // leaves y = D (D+L_B)^-1 r, scaled on the way out); 2 = the U part alone on r, z = (D+U_B)^-1 r -- the forward and the
 // backward sweep of ML's "Gauss-Seidel, efficient symmetric".  The instantiation the ILU preconditioner uses is PART 0.
-template <int WAVES, int PF, int PART = 0>
+// VT = float (PART 0 only): the values of the float plane, one dword per lane and chunk, widened before the fma; the
+// vectors in LDS, the pivots, the accumulator, the scan and the update are the double kernel's, in the same order.
+template <int WAVES, int PF, int PART = 0, class VT = double>
 __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream(int n, int B, int nblocks,
                                                                  const long long *__restrict__ boff,
-                                                                 const double *__restrict__ sv,
+                                                                 const VT *__restrict__ sv,
                                                                  const unsigned short *__restrict__ sc,
                                                                  const unsigned char *__restrict__ si,
                                                                  const unsigned short *__restrict__ sperm,
@@ -1084,13 +1107,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream(int n, int B, i
   const long long base = ilu_base_chunk(boff, b, capf, slack) + (PART == 2 ? nL0 : 0);
   const int nL = PART == 2 ? 0 : nL0, nU = PART == 1 ? 0 : nU0;
   const int nsU = __builtin_amdgcn_readfirstlane(blkinfo[4 * b + 3]);  // rows the U stream completes
-  const double *__restrict__ pv = sv + base * 64 + lane;
+  const VT *__restrict__ pv = sv + base * 64 + lane;
   const unsigned short *__restrict__ pc = sc + base * 64 + lane;
   const unsigned char *__restrict__ pi = si + base;
   const unsigned long long below = (1ull << lane) - 1ull;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  double vq[PF];
+  VT vq[PF];
   unsigned cq[PF], iq[PF];
   const int ntot = nL + nU;
 #pragma unroll
@@ -1116,7 +1139,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream(int n, int B, i
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int c = c0 + u;
-      const double v = vq[u];
+      const double v = (double)vq[u];
       const unsigned cw = cq[u];
       const unsigned iw = __builtin_amdgcn_readfirstlane(iq[u]);
       vq[u] = __builtin_nontemporal_load(&pv[(long long)(c + PF) * 64]);  // stays inside the padded buffer
@@ -1177,12 +1200,46 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream(int n, int B, i
 }
 
 // ---------------------------------------------------------------------------
+// value_bits 32: the float plane of the stream.  svf[i] = (float)sv[i] (round to nearest even, subnormals kept, a value
+// that rounds to 0 is accepted) for every entry of the chunks a block USES -- blkinfo[4b] + blkinfo[4b+1] chunks from
+// ilu_base_chunk: the default stream has unwritten gaps between the blocks, and whatever lies there must neither reach
+// the range check nor be mistaken for a value.  Padding lanes hold 0.0 and stay 0.  A finite value beyond FLT_MAX raises
+// bit 64 of the error word.  One workgroup per block, a pair of entries per thread and trip: non-temporal 16-B loads
+// (sv is not read again), full 8-B stores.  The kPrefetch chunks the solves request past a block's last chunk lie in
+// svf as they lie in sv -- same element positions, same capacity -- and are as little looked at.
+typedef double ilu_d2 __attribute__((ext_vector_type(2)));
+typedef float ilu_f2 __attribute__((ext_vector_type(2)));
+constexpr int kRoundThreads = 256;
+__global__ __launch_bounds__(kRoundThreads) void k_ilu_round_stream(int nblocks, const long long *__restrict__ boff,
+                                                                    const int *__restrict__ blkinfo,
+                                                                    const double *__restrict__ sv, float *__restrict__ svf,
+                                                                    int capf, int slack, int *__restrict__ err) {
+  const int b = blockIdx.x;
+  if (b >= nblocks) return;
+  const long long first = ilu_base_chunk(boff, b, capf, slack) * 64;  // a multiple of 64 entries: 16-B aligned pairs
+  const long long pairs = ((long long)blkinfo[4 * b] + blkinfo[4 * b + 1]) * 32;
+  const ilu_d2 *__restrict__ in = reinterpret_cast<const ilu_d2 *>(sv + first);
+  ilu_f2 *__restrict__ o = reinterpret_cast<ilu_f2 *>(svf + first);
+  bool over = false;
+  for (long long i = threadIdx.x; i < pairs; i += kRoundThreads) {
+    const ilu_d2 v = __builtin_nontemporal_load(&in[i]);
+    const double ax = fabs(v.x), ay = fabs(v.y);
+    over = over || (ax > (double)FLT_MAX && ax < HUGE_VAL) || (ay > (double)FLT_MAX && ay < HUGE_VAL);
+    ilu_f2 f;
+    f.x = (float)v.x;
+    f.y = (float)v.y;
+    o[i] = f;
+  }
+  if (over) atomicOr(err, 64);
+}
+
+// ---------------------------------------------------------------------------
 inline void ilu_destroy(isph_ilu *F) {
   if (!F) return;
   F->frp.release(); F->fcol.release(); F->flen.release(); F->fdiag.release(); F->err.release(); F->fval.release();
   F->bptr.release();
   F->boff.release(); F->sboff.release(); F->flev.release();
-  F->sv.release(); F->sc.release(); F->si.release(); F->sperm.release(); F->fdst.release(); F->blkinfo.release(); F->dinv.release(); F->llev.release();
+  F->sv.release(); F->svf.release(); F->sc.release(); F->si.release(); F->sperm.release(); F->fdst.release(); F->blkinfo.release(); F->dinv.release(); F->llev.release();
   delete F;
 }
 
@@ -1196,6 +1253,9 @@ inline int ilu_check_err(isph_ctx *ctx, isph_ilu *F, const char *what, bool *ove
   if (herr & 32) return fail("matrix row with duplicate or unsorted columns: ILU pattern undefined", __FILE__, __LINE__);
   if ((herr & 16) && overflow) { *overflow = true; return ISPH_SUCCESS; }
   if (herr & 16) return fail("ILU triangular-solve stream capacity exceeded", __FILE__, __LINE__);
+  if (herr & 64)
+    return fail("ILU: a factor value exceeds the range of single precision (value_bits = 32 rounds the strict-L and strict-U "
+                "values to float)", __FILE__, __LINE__);
   if (herr) return fail(what, __FILE__, __LINE__);
   return ISPH_SUCCESS;
 }
@@ -1452,8 +1512,23 @@ inline int ilu_schedule_and_factor(isph_ctx *ctx, isph_ilu *F, const Sell &S, bo
   return rc;
 }
 
+// value_bits 32, once per create behind the factorisation: the float plane, then sv goes back to the pool -- nothing reads
+// it after set-up (the solves stream svf, the export and isph_prec_nnz read the row-major factor fval, which stays fp64
+// and bit for bit what value_bits 64 builds).  One more host check per create: the range flag.
+inline int ilu_round_stream(isph_ctx *ctx, isph_ilu *F) {
+  F->value_bits = 32;
+  if (F->n == 0 || F->nblocks == 0) return ISPH_SUCCESS;
+  ISPH_CHECK(F->svf.reserve((size_t)F->stream_chunks * 64));
+  hipLaunchKernelGGL(k_ilu_round_stream, dim3(F->nblocks), dim3(kRoundThreads), 0, ctx->stream, F->nblocks, F->stream_off(),
+                     (const int *)F->blkinfo.p, (const double *)F->sv.p, F->svf.p, F->capf, F->slack, F->err.p);
+  ISPH_CHECK(ilu_check_err(ctx, F, "ILU factorisation / rounding pass failed"));
+  F->sv.release();
+  return ISPH_SUCCESS;
+}
+
 inline int ilu_create(isph_ctx *ctx, const isph_mat *A, int block_size, isph_ilu **out, bool sgs = false, int fill = 0,
-                      int nblocks_tab = 0, const int *host_bptr = nullptr) {
+                      int nblocks_tab = 0, const int *host_bptr = nullptr, int value_bits = 64) {
+  ISPH_REQUIRE(value_bits == 64 || (value_bits == 32 && !sgs), "ILU: value_bits must be 64 or 32 (the Gauss-Seidel streams stay double)");
   const Sell &S = A->S;
   isph_ilu *F = nullptr;
   const bool var = nblocks_tab > 0;
@@ -1532,6 +1607,7 @@ inline int ilu_create(isph_ctx *ctx, const isph_mat *A, int block_size, isph_ilu
     }
     if (rc == ISPH_SUCCESS) rc = ilu_schedule_and_factor(ctx, F, S, sgs);
   }
+  if (rc == ISPH_SUCCESS && value_bits == 32) rc = ilu_round_stream(ctx, F);
   if (rc != ISPH_SUCCESS) { ilu_destroy(F); return rc; }
   *out = F;
   return ISPH_SUCCESS;
@@ -1545,10 +1621,10 @@ struct IluVecs {
   const double *r[4];
   double *z[4];
 };
-template <int WAVES, int PF, int NV>
+template <int WAVES, int PF, int NV, class VT = double>
 __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream_multi(int n, int B, int nblocks,
                                                                        const long long *__restrict__ boff,
-                                                                       const double *__restrict__ sv,
+                                                                       const VT *__restrict__ sv,
                                                                        const unsigned short *__restrict__ sc,
                                                                        const unsigned char *__restrict__ si,
                                                                        const unsigned short *__restrict__ sperm,
@@ -1575,13 +1651,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream_multi(int n, in
   const long long base = ilu_base_chunk(boff, b, capf, slack);
   const int nL = __builtin_amdgcn_readfirstlane(blkinfo[4 * b]), nU = __builtin_amdgcn_readfirstlane(blkinfo[4 * b + 1]);
   const int nsU = __builtin_amdgcn_readfirstlane(blkinfo[4 * b + 3]);
-  const double *__restrict__ pv = sv + base * 64 + lane;
+  const VT *__restrict__ pv = sv + base * 64 + lane;
   const unsigned short *__restrict__ pc = sc + base * 64 + lane;
   const unsigned char *__restrict__ pi = si + base;
   const unsigned long long below = (1ull << lane) - 1ull;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  double vq[PF];
+  VT vq[PF];
   unsigned cq[PF], iq[PF];
   const int ntot = nL + nU;
 #pragma unroll
@@ -1628,7 +1704,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream_multi(int n, in
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
       const int c = c0 + u;
-      const double v = vq[u];
+      const double v = (double)vq[u];
       const unsigned cw = cq[u];
       const unsigned iw = __builtin_amdgcn_readfirstlane(iq[u]);
       vq[u] = __builtin_nontemporal_load(&pv[(long long)(c + PF) * 64]);
@@ -1702,17 +1778,21 @@ inline int ilu_apply_multi(isph_ctx *ctx, const isph_ilu *F, int K, const double
   }
   IluVecs X;
   for (int k = 0; k < 4; ++k) { X.r[k] = rs[k < K ? k : 0]; X.z[k] = zs[k < K ? k : 0]; }
-#define ISPH_ILU_LAUNCH_MULTI(NV)                                                                                          \
+#define ISPH_ILU_LAUNCH_MULTI(NV, VT, SV)                                                                                        \
   do {                                                                                                                      \
-    ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_solve_stream_multi<WV, kPrefetch, NV>),         \
+    ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_solve_stream_multi<WV, kPrefetch, NV, VT>),     \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                              \
-    hipLaunchKernelGGL((k_ilu_solve_stream_multi<WV, kPrefetch, NV>), dim3((F->nblocks + WV - 1) / WV), dim3(WV * 64), lds, \
-                       ctx->stream, F->n, F->B, F->nblocks, F->stream_off(), F->sv.p, F->sc.p, F->si.p, F->sperm.p,               \
+    hipLaunchKernelGGL((k_ilu_solve_stream_multi<WV, kPrefetch, NV, VT>), dim3((F->nblocks + WV - 1) / WV), dim3(WV * 64), lds, \
+                       ctx->stream, F->n, F->B, F->nblocks, F->stream_off(), (const VT *)SV, F->sc.p, F->si.p, F->sperm.p,        \
                        F->blkinfo.p, F->dinv.p, X, F->capf, F->slack, F->blocks());                                         \
   } while (0)
-  if (K == 2) ISPH_ILU_LAUNCH_MULTI(2);
-  else if (K == 3) ISPH_ILU_LAUNCH_MULTI(3);
-  else ISPH_ILU_LAUNCH_MULTI(4);
+  if (F->value_bits == 32) {  // the float plane
+    if (K == 2) ISPH_ILU_LAUNCH_MULTI(2, float, F->svf.p);
+    else if (K == 3) ISPH_ILU_LAUNCH_MULTI(3, float, F->svf.p);
+    else ISPH_ILU_LAUNCH_MULTI(4, float, F->svf.p);
+  } else if (K == 2) ISPH_ILU_LAUNCH_MULTI(2, double, F->sv.p);
+  else if (K == 3) ISPH_ILU_LAUNCH_MULTI(3, double, F->sv.p);
+  else ISPH_ILU_LAUNCH_MULTI(4, double, F->sv.p);
 #undef ISPH_ILU_LAUNCH_MULTI
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
@@ -1725,21 +1805,23 @@ inline int ilu_apply(isph_ctx *ctx, const isph_ilu *F, const double *r, double *
   constexpr int WV = 4;
   const size_t lds = sizeof(double) * 3 * (size_t)F->B * WV;
   constexpr int pf = kPrefetch;
-#define ISPH_ILU_LAUNCH(PF, PART)                                                                                       \
+#define ISPH_ILU_LAUNCH(PF, PART, VT, SV)                                                                                     \
   do {                                                                                                                   \
     if (lds > 48 * 1024)                                                                                                 \
-      ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_solve_stream<WV, PF, PART>),               \
+      ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_solve_stream<WV, PF, PART, VT>),           \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                         \
-    hipLaunchKernelGGL((k_ilu_solve_stream<WV, PF, PART>), dim3((F->nblocks + WV - 1) / WV), dim3(WV * 64), lds, ctx->stream, \
-                       F->n, F->B, F->nblocks, F->stream_off(), F->sv.p, F->sc.p, F->si.p, F->sperm.p, F->blkinfo.p,          \
+    hipLaunchKernelGGL((k_ilu_solve_stream<WV, PF, PART, VT>), dim3((F->nblocks + WV - 1) / WV), dim3(WV * 64), lds, ctx->stream, \
+                       F->n, F->B, F->nblocks, F->stream_off(), (const VT *)SV, F->sc.p, F->si.p, F->sperm.p, F->blkinfo.p,   \
                        F->dinv.p, r, z, F->capf, F->slack, F->blocks(), accumulate ? 1 : 0);                            \
   } while (0)
-  if (part == 1) ISPH_ILU_LAUNCH(16, 1);
-  else if (part == 2) ISPH_ILU_LAUNCH(16, 2);
-  else if (pf == 12) ISPH_ILU_LAUNCH(12, 0);
-  else if (pf == 16) ISPH_ILU_LAUNCH(16, 0);
-  else if (pf == 24) ISPH_ILU_LAUNCH(24, 0);
-  else ISPH_ILU_LAUNCH(8, 0);
+  ISPH_REQUIRE(F->value_bits != 32 || part == 0, "ilu_apply: the float plane serves both sweeps only (the Gauss-Seidel streams stay double)");
+  if (F->value_bits == 32) ISPH_ILU_LAUNCH(kPrefetch, 0, float, F->svf.p);
+  else if (part == 1) ISPH_ILU_LAUNCH(16, 1, double, F->sv.p);
+  else if (part == 2) ISPH_ILU_LAUNCH(16, 2, double, F->sv.p);
+  else if (pf == 12) ISPH_ILU_LAUNCH(12, 0, double, F->sv.p);
+  else if (pf == 16) ISPH_ILU_LAUNCH(16, 0, double, F->sv.p);
+  else if (pf == 24) ISPH_ILU_LAUNCH(24, 0, double, F->sv.p);
+  else ISPH_ILU_LAUNCH(8, 0, double, F->sv.p);
 #undef ISPH_ILU_LAUNCH
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;

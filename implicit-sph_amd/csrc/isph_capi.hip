@@ -1220,23 +1220,68 @@ int isph_prec_create_blocks(isph_ctx *ctx, const isph_mat *A, int nblocks, const
   return isph_prec_create_blocks_fill(ctx, A, nblocks, block_ptr, 0, Mout);
 }
 
+// the three routes of the block stream: the caller's table (nblocks > 0), the matrix' own subdomains (block_size <= 0), one
+// block per block_size rows.  value_bits: 64 or 32 (checked by the caller)
+static int prec_ilu_init(isph_ctx *ctx, const isph_mat *A, int level_of_fill, int block_size, int nblocks, const int *block_ptr,
+                         int value_bits, isph_prec *M) {
+  M->type = 2;
+  if (nblocks > 0) {
+    ISPH_REQUIRE(block_ptr, "NULL argument or no subdomains");
+    ISPH_REQUIRE(level_of_fill >= 0 && level_of_fill <= 8, "level of fill must be in [0,8]");
+    ISPH_REQUIRE(!is_device_pointer(block_ptr), "block_ptr must be a host array");
+    ISPH_REQUIRE(!A->order, "the matrix was assembled in the library's own row numbering: its subdomains are the library's "
+                            "bricks (isph_prec_create with block_size 0); a table over the caller's rows needs "
+                            "isph_ctx_set_ordering(ctx, 0) before the assembly");
+    int cap = 64;
+    for (int b = 0; b < nblocks; ++b) cap = std::max(cap, block_ptr[b + 1] - block_ptr[b]);
+    cap = (cap + 63) / 64 * 64;
+    ISPH_REQUIRE(cap <= 1024, "a subdomain of the block stream holds at most 1024 rows (isph_prec_create_schwarz takes larger ones)");
+    return ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, level_of_fill, nblocks, block_ptr, value_bits);
+  }
+  if (block_size <= 0) {
+    // the matrix' own subdomains: the bricks the assembly sorted the particles into (order.hpp)
+    if (!A->order)
+      return fail("block_size 0 selects the library's own subdomains: the matrix must come from an assembly entry point "
+                  "with isph_ctx_set_ordering(ctx, 1)", __FILE__, __LINE__);
+    const std::vector<int> &bp = A->order->block_ptr;
+    int cap = 64;
+    for (size_t b = 0; b + 1 < bp.size(); ++b) cap = std::max(cap, bp[b + 1] - bp[b]);
+    cap = (cap + 63) / 64 * 64;
+    return ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, level_of_fill, (int)bp.size() - 1, bp.data(), value_bits);
+  }
+  return ilu_create(ctx, A, block_size, &M->ilu, /*sgs=*/false, level_of_fill, 0, nullptr, value_bits);
+}
+
 int isph_prec_create_blocks_fill(isph_ctx *ctx, const isph_mat *A, int nblocks, const int *block_ptr, int level_of_fill,
                                  isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && Mout && nblocks > 0 && block_ptr, "NULL argument or no subdomains");
-  ISPH_REQUIRE(level_of_fill >= 0 && level_of_fill <= 8, "level of fill must be in [0,8]");
-  ISPH_REQUIRE(!is_device_pointer(block_ptr), "block_ptr must be a host array");
-  ISPH_REQUIRE(!A->order, "the matrix was assembled in the library's own row numbering: its subdomains are the library's "
-                          "bricks (isph_prec_create with block_size 0); a table over the caller's rows needs "
-                          "isph_ctx_set_ordering(ctx, 0) before the assembly");
-  int cap = 64;
-  for (int b = 0; b < nblocks; ++b) cap = std::max(cap, block_ptr[b + 1] - block_ptr[b]);
-  cap = (cap + 63) / 64 * 64;
-  ISPH_REQUIRE(cap <= 1024, "a subdomain of the block stream holds at most 1024 rows (isph_prec_create_schwarz takes larger ones)");
   isph_prec *M = new isph_prec();
   M->n = A->S.nrow;
-  M->type = 2;
-  const int rc = ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, level_of_fill, nblocks, block_ptr);
+  const int rc = prec_ilu_init(ctx, A, level_of_fill, 0, nblocks, block_ptr, 64, M);
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
+  *Mout = M;
+  return ISPH_SUCCESS;
+}
+
+void isph_ilu_params_default(isph_ilu_params *p) {
+  p->level_of_fill = 0; p->block_size = 0; p->nblocks = 0; p->block_ptr = nullptr; p->value_bits = 64;
+}
+
+int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params *prm, isph_prec **Mout) {
+  ISPH_REQUIRE(ctx && A && Mout, "NULL argument");
+  isph_ilu_params def;
+  isph_ilu_params_default(&def);
+  if (!prm) prm = &def;
+  ISPH_REQUIRE(prm->value_bits == 0 || prm->value_bits == 64 || prm->value_bits == 32,
+               "block ILU: value_bits must be 64 (or 0: double values) or 32 (single-precision factor values in the solves)");
+  ISPH_REQUIRE(prm->level_of_fill >= 0 && prm->level_of_fill <= 8, "level of fill must be in [0,8]");
+  ISPH_REQUIRE(prm->nblocks >= 0 && (prm->nblocks == 0 || prm->block_ptr), "a table of subdomains without its offsets");
+  isph_prec *M = new isph_prec();
+  M->n = A->S.nrow;
+  const int rc = prec_ilu_init(ctx, A, prm->level_of_fill, prm->block_size, prm->nblocks, prm->block_ptr,
+                               prm->value_bits == 32 ? 32 : 64, M);
+  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
+  if (prm->nblocks == 0) M->order = A->order;  // as isph_prec_create; a table is refused for a matrix in the library's numbering
   *Mout = M;
   return ISPH_SUCCESS;
 }
@@ -1278,6 +1323,7 @@ int isph_prec_value_bits(const isph_prec *M) {
   if (!M) return 0;
   if (M->type == 6 && M->cheb) return M->cheb->value_bits;
   if (M->type == 3 && M->amg && M->amg->cheb) return M->amg->cheb_value_bits;
+  if (M->type == 2 && M->ilu && M->ilu->value_bits == 32) return 32;
   return 0;
 }
 
@@ -1308,24 +1354,9 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
                          A->S.rowlen.p, A->S.slice_off.p, A->S.col.p, A->S.val.p, M->invdiag.p);
       if (hipGetLastError() != hipSuccess) rc = fail("jacobi setup failed", __FILE__, __LINE__);
     }
-  } else if (!strncmp(type, "bjacobi-ilu", 11) && type[11] >= '0' && type[11] <= '8' && type[12] == 0) {
-    // "bjacobi-ilu<k>": "fact: level-of-fill" = k (precond_ifpack.h:35)
-    M->type = 2;
-    if (block_size <= 0) {
-      // the matrix' own subdomains: the bricks the assembly sorted the particles into (order.hpp)
-      if (!A->order) {
-        rc = fail("block_size 0 selects the library's own subdomains: the matrix must come from an assembly entry point "
-                  "with isph_ctx_set_ordering(ctx, 1)", __FILE__, __LINE__);
-      } else {
-        const std::vector<int> &bp = A->order->block_ptr;
-        int cap = 64;
-        for (size_t b = 0; b + 1 < bp.size(); ++b) cap = std::max(cap, bp[b + 1] - bp[b]);
-        cap = (cap + 63) / 64 * 64;
-        rc = ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, /*fill=*/type[11] - '0', (int)bp.size() - 1, bp.data());
-      }
-    } else {
-      rc = ilu_create(ctx, A, block_size, &M->ilu, /*sgs=*/false, /*fill=*/type[11] - '0');
-    }
+  } else if (!strncmp(type, "bjacobi-ilu", 11) && type[11] >= '0' && type[11] <= '8' && (type[12] == 0 || !strcmp(type + 12, "-f32"))) {
+    // "bjacobi-ilu<k>": "fact: level-of-fill" = k (precond_ifpack.h:35); "bjacobi-ilu<k>-f32": the same with value_bits = 32
+    rc = prec_ilu_init(ctx, A, /*fill=*/type[11] - '0', block_size, 0, nullptr, type[12] ? 32 : 64, M);
   } else if (!strncmp(type, "ilu", 3) && type[3] >= '0' && type[3] <= '8' && type[4] == 0) {
     // "ilu<k>": ILU(k) of the whole local matrix -- what Ifpack factors on one MPI rank (the overlap is a no-op there)
     M->type = 4;
@@ -1347,7 +1378,7 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
     prm.value_bits = cheb_bits;
     rc = prec_chebyshev_init(ctx, A, &prm, M);
   } else {
-    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16)", __FILE__, __LINE__);
+    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)", __FILE__, __LINE__);
   }
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;

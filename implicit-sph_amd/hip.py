@@ -30,6 +30,7 @@ EXPORTS = [
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
     "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits",
+    "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
 ]
 
@@ -228,6 +229,9 @@ def lib():
         L.isph_cheb_params_default.argtypes = [C.c_void_p]
         L.isph_prec_create_chebyshev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_value_bits.argtypes = [C.c_void_p]
+        L.isph_ilu_params_default.argtypes = [C.c_void_p]
+        L.isph_ilu_params_default.restype = None
+        L.isph_prec_create_ilu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_value_bits.restype = C.c_int
         L.isph_prec_amg_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -698,9 +702,17 @@ class Precond:
         self.h = C.c_void_p()
         self.A = A if kind.startswith("chebyshev") else None   # the polynomial applies the matrix: keep it alive
         if block_ptr is not None:
-            assert kind.startswith("bjacobi-ilu") and kind[11:].isdigit()
+            f32 = kind.endswith("-f32")   # "bjacobi-ilu<k>-f32": the table form with value_bits = 32
+            fill = kind[11:-4] if f32 else kind[11:]
+            if not (kind.startswith("bjacobi-ilu") and fill.isdigit()):
+                raise IsphError("unknown preconditioner type for a table of subdomains: %r (bjacobi-ilu<k>|bjacobi-ilu<k>-f32)" % kind)
             bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
-            _check(lib().isph_prec_create_blocks_fill(ctx.h, A.h, len(bp) - 1, _ptr(bp), int(kind[11:]), C.byref(self.h)))
+            if f32:
+                prm = IluParams(level_of_fill=int(fill), nblocks=len(bp) - 1, block_ptr=bp.ctypes.data_as(C.POINTER(C.c_int)),
+                                value_bits=32)
+                _check(lib().isph_prec_create_ilu(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
+            else:
+                _check(lib().isph_prec_create_blocks_fill(ctx.h, A.h, len(bp) - 1, _ptr(bp), int(fill), C.byref(self.h)))
         else:
             _check(lib().isph_prec_create(ctx.h, A.h, kind.encode(), block_size, C.byref(self.h)))
 
@@ -719,7 +731,8 @@ class Precond:
     @property
     def value_bits(self):
         """isph_prec_value_bits: 32 or 64 = the width of the matrix values the Chebyshev sweeps read (the Chebyshev
-        preconditioner, or an AMG with the Chebyshev smoother); 0 for every other preconditioner."""
+        preconditioner, or an AMG with the Chebyshev smoother); 32 for a block ILU with single-precision stream values
+        ("bjacobi-ilu<k>-f32"); 0 for every other preconditioner."""
         return int(lib().isph_prec_value_bits(self.h))
 
     def info(self):
@@ -745,6 +758,33 @@ class Precond:
             self.close()
         except Exception:
             pass
+
+
+class IluParams(C.Structure):
+    """Mirror of isph_ilu_params: level_of_fill 0..8; nblocks > 0 and block_ptr = the caller's table, else block_size rows
+    per block (0: the matrix' own subdomains); value_bits 64 | 32 (the solves stream the factor values rounded to float)."""
+    _fields_ = [("level_of_fill", C.c_int), ("block_size", C.c_int), ("nblocks", C.c_int), ("block_ptr", C.POINTER(C.c_int)),
+                ("value_bits", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().isph_ilu_params_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class PrecondILU(Precond):
+    """isph_prec_create_ilu: the block stream ("bjacobi-ilu<k>") from its parameter struct.  block_ptr: the caller's
+    subdomains; otherwise block_size rows per block (0: the matrix' own subdomains).  value_bits = 32: the triangular
+    solves read the strict-L / strict-U values rounded to float; the factor itself, the pivots and the vectors stay fp64."""
+
+    def __init__(self, ctx, A, level_of_fill=0, block_size=0, block_ptr=None, value_bits=64):
+        self.ctx, self.h, self.n, self.A = ctx, C.c_void_p(), A.info()["nrow"], None
+        prm = IluParams(level_of_fill=int(level_of_fill), block_size=int(block_size), value_bits=int(value_bits))
+        if block_ptr is not None:
+            bp = np.ascontiguousarray(block_ptr, dtype=np.int32)
+            prm.nblocks, prm.block_ptr = len(bp) - 1, bp.ctypes.data_as(C.POINTER(C.c_int))
+        _check(lib().isph_prec_create_ilu(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
 
 
 class SchwarzParams(C.Structure):

@@ -28,6 +28,9 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       // block stream of csrc/ilu.hpp (throughput path); 0 = one subdomain per rank = the whole local matrix, what the
       // reference factors (level-scheduled, csrc/schwarz.hpp); > 1024 = large subdomains with "Overlap Level" layers.
       _param->set("isph: block rows", 512);
+      // device-side extension (not a reference key), "Precond Type" = "ILU" only: "isph: ilu value bits" = 32 makes the
+      // triangular solves of the block stream read the strict-L / strict-U values rounded to float
+      // (isph_ilu_params::value_bits).  Not set here: absent means 64.
     } else if (_param.get() != param) {
       _param = Teuchos::rcp(param, false);
     }
@@ -63,6 +66,8 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
     // the flat copy reaches 54, so the fused form loses 5-10 ms against this one: profiles/r05_dropin.txt)
     if (_cx != nullptr) return 0;
     if (_param->get("Precond Type", "ILU") != "ILU" || _param->get("fact: level-of-fill", 1) != 0) return 0;
+    // the fused set-up builds an fp64 stream: any other width is built (or refused) in createOnDevice
+    if (_param->get("isph: ilu value bits", 64) != 64) return 0;
     if (tableUsable()) {
       int cap = 64;
       for (size_t b = 0; b + 1 < _bptr.size(); ++b) cap = std::max(cap, _bptr[b + 1] - _bptr[b]);
@@ -92,7 +97,8 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
   virtual bool orderedIngressFusable() {
     setParameters(_param.get());
     const int block = _param->get("isph: block rows", 512);
-    return _param->get("Precond Type", "ILU") == "ILU" && _param->get("fact: level-of-fill", 1) == 0 && block > 0 && block <= 1024;
+    return _param->get("Precond Type", "ILU") == "ILU" && _param->get("fact: level-of-fill", 1) == 0 && block > 0 && block <= 1024 &&
+           _param->get("isph: ilu value bits", 64) == 64;   // the fused set-up builds an fp64 stream
   }
   virtual bool fusedIngressSubdomains(int &nblocks, const int *&bptr) {
     if (_cx != nullptr || !tableUsable()) return false;   // with coordinates the library's own bricks win over a table
@@ -152,6 +158,13 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): fact: level-of-fill %d is outside [0,8]\n", fill);
       return ISPH_FAILURE;
     }
+    // device-side extension (not a reference key): 32 = the block stream's solves read the factor values rounded to float
+    // (isph_ilu_params::value_bits).  Read for this type only; honoured on the three block-Jacobi routes below.
+    const int bits = _param->get("isph: ilu value bits", 64);
+    if (bits != 64 && bits != 32) {
+      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): \"isph: ilu value bits\" = %d is not available; available: 64, 32\n", bits);
+      return ISPH_FAILURE;
+    }
     free();
     const int block = _param->get("isph: block rows", 512);
     const std::string mode = _param->get("schwarz: combine mode", "Add");
@@ -164,6 +177,17 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
     // import below is collective, so a rank without ghost columns -- an isolated subdomain -- must enter it as well,
     // with empty lists, and a failure on one rank must fail all of them.
     const int any_ghosts = _A.get() != NULL ? _comm.MaxAll(_A->NumMyCols() > _A->NumMyRows() ? 1 : 0) : 0;
+    if (bits == 32 && ((block == 0 && overlap >= 1 && any_ghosts) || (!tableUsable() && (block == 0 || block > 1024)))) {
+      // the level-scheduled Schwarz and overlap routes have no float plane: refused, never built in fp64 silently
+      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): \"isph: ilu value bits\" = 32 is not available with \"isph: block rows\" = %d "
+                           "(the Schwarz and overlap routes stream fp64 only); choose \"isph: block rows\" in 64..1024, a table of "
+                           "subdomains or coordinates, or 64 bits\n", block);
+      return ISPH_FAILURE;
+    }
+    isph_ilu_params ip;
+    isph_ilu_params_default(&ip);
+    ip.level_of_fill = fill;
+    ip.value_bits = bits;
     if (block == 0 && overlap >= 1 && any_ghosts) {
       HaloLists H, XH;
       std::vector<int> rp, ci;
@@ -201,7 +225,9 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
     }
     if (tableUsable()) {  // the caller's subdomains (setSubdomains), any level of fill
       noticeOnce(fill, 0, overlap);
-      return isph_prec_create_blocks_fill(ctx, A, (int)_bptr.size() - 1, _bptr.data(), fill, &_M);
+      ip.nblocks = (int)_bptr.size() - 1;
+      ip.block_ptr = _bptr.data();
+      return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create_blocks_fill, bit for bit
     }
     if (block == 0 || block > 1024) {
       isph_schwarz_params sp;
@@ -216,16 +242,16 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       long long oi[3] = {0, 0, 0};
       if (isph_mat_ordering_info(A, oi, NULL) == ISPH_SUCCESS && oi[0] == 1) {
         noticeOnce(fill, -1, overlap);
-        const std::string kind = "bjacobi-ilu" + std::to_string(fill);
-        return isph_prec_create(ctx, A, kind.c_str(), 0, &_M);
+        ip.block_size = 0;
+        return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create("bjacobi-ilu<fill>", 0), bit for bit
       }
     }
     // default: the throughput path -- block-Jacobi ILU(fill) on subdomains of `block` rows inside the rank, overlap 0.
     // This is NOT what the reference factors (one subdomain per rank, overlap 1): iteration counts differ (on the 100^3
     // TGV system 116 iterations against 49 for the whole-matrix ILU(0)); the notice is printed once, on every build.
     noticeOnce(fill, block, overlap);
-    const std::string kind = "bjacobi-ilu" + std::to_string(fill);
-    return isph_prec_create(ctx, A, kind.c_str(), block, &_M);
+    ip.block_size = block;
+    return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create("bjacobi-ilu<fill>", block), bit for bit
   }
   bool _warned = false, _warned_table = false;
   std::vector<int> _bptr;  // setSubdomains

@@ -199,6 +199,8 @@ int isph_spmv_time(isph_ctx *ctx, const isph_mat *A, const double *x_dev, double
  *                   "fact: level-of-fill"=k (precond_ifpack.h:35; the reference's
  *                   default is k = 1), one block per `block_size` rows
  *                   (k > 0: block_size <= 1024 and the symbolic phase runs on the device)
+ *   "bjacobi-ilu<k>-f32"  the same with value_bits = 32 (isph_ilu_params): the triangular solves stream the strict-L and
+ *                   strict-U factor values rounded to single precision
  *   "ilu<k>"        ILU(k) of the whole local matrix: Ifpack on one MPI rank (precond_ifpack.h:60-74 with
  *                   Comm.NumProc() == 1); see isph_prec_create_schwarz
  *   "sa-amg"        PrecondWrapper_ML::create() with its default parameters and no null vector
@@ -224,6 +226,38 @@ int isph_prec_create_blocks(isph_ctx *ctx, const isph_mat *A, int nblocks, const
  * the merge kernel, whatever the lengths of the subdomains. */
 int isph_prec_create_blocks_fill(isph_ctx *ctx, const isph_mat *A, int nblocks, const int *block_ptr, int level_of_fill,
                                  isph_prec **M);
+/* The block stream ("bjacobi-ilu<k>") with all its parameters in one struct: level_of_fill 0..8, and one of the three
+ * routes -- nblocks > 0: the caller's table block_ptr[0 .. nblocks] (isph_prec_create_blocks_fill); otherwise
+ * block_size > 0: one block per block_size rows, block_size 0: the matrix' own subdomains (isph_prec_create).  With
+ * value_bits 64 the call IS those calls, bit for bit.
+ * value_bits (not a reference parameter): 64 (the default; 0 means the same) or 32; any other value is refused.  With 32
+ * the factorisation is untouched -- isph_prec_export_ilu returns the fp64 factor bit for bit as value_bits 64 builds it --
+ * and one more streaming pass behind it rounds the values of the triangular-solve stream to the nearest float (ties to
+ * even, subnormals kept, a value that rounds to 0 accepted) into a plane of 4 B per entry; the fp64 stream is then given
+ * back.  The application is exactly the fp64 triangular solves z = U^-1 D^-1 L^-1 r with every strict-L and strict-U
+ * entry replaced by its float rounding: the pivots 1/d_i, the vectors (in LDS), the accumulators, the segmented scan and
+ * the update stay double, the operations and their order are those of value_bits 64.  The solves stream 6 B instead of
+ * 10 B per stream entry.  A fixed linear operator, so every Krylov solver may use it and the outer iteration works in
+ * fp64 on the true A; but it is symmetric only up to single-precision rounding when A is symmetric, because
+ * fl32(u_ij) != d_i fl32(l_ji) in general: "Block CG" sees a preconditioner that is nonsymmetric at the 1e-7 level.
+ * The create call fails when a finite factor value exceeds the range of single precision.  isph_prec_value_bits
+ * answers 32.  Off by default.
+ * Measured at 100^3 on the library's bricks, widths alternated in one process (profiles/ilu_f32_100cubed.txt,
+ * 2026-10-18): one application 127.9 (125.4 - 134.7) against 146.4 (144.6 - 149.0) us for 0.615 of the bytes ("bjacobi-
+ * ilu0"), 299.0 (293.1 - 326.2) against 331.2 (326.6 - 344.0) us for 0.607 ("bjacobi-ilu1") -- time 0.87 and 0.90: the
+ * solve is bound by its per-block dependency chain, not by the stream bytes; create + solve with the benchmark's
+ * protocol 37.00 against 38.02 ms (71 iterations both) and 99.47 against 100.93 ms (63 both); the rounding pass +0.03 ..
+ * +0.3 ms per create.
+ * Call isph_ilu_params_default FIRST and then change fields: the struct grows at its tail. */
+typedef struct {
+  int level_of_fill;    /* 0..8 */
+  int block_size;       /* rows per block; 0 = the matrix' own subdomains */
+  int nblocks;          /* > 0: the caller's table */
+  const int *block_ptr;
+  int value_bits;       /* 64 (default; 0 means the same) or 32 */
+} isph_ilu_params;
+void isph_ilu_params_default(isph_ilu_params *p);
+int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params *prm, isph_prec **M);
 /* Ifpack_AdditiveSchwarz<Ifpack_ILU> with the parameters PrecondWrapper_Ifpack sets (ref: precond_ifpack.h:30-45,
  * 60-74): "fact: level-of-fill" (default 1), "Overlap Level" (default 1), "schwarz: combine mode" (default "Add" = 0;
  * 1 = "Zero", restricted additive Schwarz).  block_size = 0: one subdomain = the whole local matrix, which is what
@@ -296,7 +330,8 @@ typedef struct {
 void isph_cheb_params_default(isph_cheb_params *p);
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **M);
 /* 32 or 64: the width of the matrix values the Chebyshev sweeps of M read (a Chebyshev preconditioner, or an AMG with
- * smoother = 2); 0 for every other preconditioner and for NULL. */
+ * smoother = 2); 32 for a block ILU whose solves stream single-precision factor values ("bjacobi-ilu<k>-f32",
+ * isph_ilu_params::value_bits = 32); 0 for every other preconditioner -- a plain "bjacobi-ilu<k>" included -- and for NULL. */
 int isph_prec_value_bits(const isph_prec *M);
 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
