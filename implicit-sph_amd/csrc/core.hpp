@@ -57,6 +57,8 @@ struct isph_ctx {
   size_t hscal_cap = 0;
   // Krylov workspaces (grow-only, reused across solves)
   isph::DevBuf<double> V, Z, wv, tv, rv, pv, nvec, xext, sendbuf, bdev, xdev;
+  isph::DevBuf<float> V32;          // the Krylov basis of basis_bits = 32 (solver.hpp gmres_t<float>)
+  isph::DevBuf<double> vcur;        // its current column, widened: what the preconditioner reads
   isph::DevBuf<double> bint, xint;  // b / x of a solve in the matrix' own row numbering (order.hpp)
   isph::DevBuf<int> imask, imask2;
   // profiling events

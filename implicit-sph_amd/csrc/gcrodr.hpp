@@ -38,7 +38,7 @@ inline int combine(isph_ctx *ctx, int n, int nin, const double *Basis, long long
   if (nin <= 0) return ISPH_SUCCESS;
   ISPH_CHECK(cbuf.reserve(128));
   ISPH_CHECK_HIP(hipMemcpyAsync(cbuf.p, coef, sizeof(double) * (size_t)nin, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(k_multi_axpy, dim3(sg), dim3(kBlock), 0, ctx->stream, n, nin, Basis, ld, (const double *)cbuf.p, out);
+  hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, ctx->stream, n, nin, Basis, ld, (const double *)cbuf.p, out);
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // the pageable source must outlive the copy
   return ISPH_SUCCESS;
 }
@@ -95,7 +95,7 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     rc = norm_of(r, &beta);
     if (rc != ISPH_SUCCESS) break;
     if (beta == 0.0) { info->converged = 1; break; }
-    hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, (const double *)r, V, 1.0 / beta, (const double *)nullptr, 0);
+    hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)r, V, 1.0 / beta, (const double *)nullptr, 0);
     g[0] = beta;
     int j = 0;
     bool conv = false;
@@ -120,7 +120,7 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
       hcol[(size_t)j + 1] = hn;
       for (int i = 0; i <= j + 1; ++i) H[(size_t)i * steps + j] = hcol[(size_t)i];
       if (hn != 0.0)
-        hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, V + (long long)(j + 1) * ld, 1.0 / hn,
+        hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, V + (long long)(j + 1) * ld, 1.0 / hn,
                            (const double *)nullptr, 0);
       // implicit residual by Givens rotations on a copy of the column
       for (int i = 0; i < j; ++i) {

@@ -637,7 +637,7 @@ void isph_ctx_destroy(isph_ctx *c) {
   (void)hipEventDestroy(c->ev1);
   if (c->ev_fetch) (void)hipEventDestroy(c->ev_fetch);
   for (hipEvent_t e : c->ev_ls) (void)hipEventDestroy(e);
-  c->partial.release(); c->dscal.release(); c->V.release(); c->Z.release(); c->wv.release(); c->tv.release();
+  c->partial.release(); c->dscal.release(); c->V.release(); c->V32.release(); c->vcur.release(); c->Z.release(); c->wv.release(); c->tv.release();
   c->rv.release(); c->pv.release(); c->nvec.release(); c->xext.release(); c->sendbuf.release();
   c->bdev.release(); c->xdev.release(); c->imask.release();
   c->bint.release(); c->xint.release(); c->imask2.release();
@@ -1649,6 +1649,7 @@ void isph_solver_params_default(isph_solver_params *p) {
   // SolverLin_Belos::setParameters(NULL), ref: solver_lin_belos.h:226-240
   p->solver_type = 0; p->flexible = 1; p->num_blocks = 50; p->max_iters = 500; p->max_restarts = 15;
   p->tol = 1.0e-8; p->ortho = 0; p->verbose = 0; p->num_recycled = 50;
+  p->basis_bits = 64;
 }
 
 int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, double *x, int nvec, int lda,
@@ -1662,6 +1663,12 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
                "preconditioner and matrix are in different row numberings (build the preconditioner from this matrix)");
   isph_solver_params prm;
   if (prm_in) prm = *prm_in; else isph_solver_params_default(&prm);
+  int basis_bits = 64;
+  ISPH_CHECK(basis_bits_of(&prm, &basis_bits));
+  if (basis_bits == 32) {  // no silent fallback to the fp64 basis
+    ISPH_REQUIRE(prm.solver_type == 0, "basis_bits = 32 is Block GMRES only (solver_type 0): CG and GCRO-DR keep basis_bits 64");
+    ISPH_REQUIRE(prm.ortho != 2, "basis_bits = 32 takes DGKS or ICGS: IMGS (ortho = 2) keeps the fp64 basis");
+  }
   memset(info, 0, sizeof(*info));
   ISPH_CHECK(ensure_scalars(ctx));
   hipStream_t st = ctx->stream;
@@ -1737,12 +1744,12 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
       hipLaunchKernelGGL(k_fill, dim3(sg), dim3(kBlock), 0, st, n, ctx->nvec.p, 1.0);
     }
     ISPH_CHECK(dot_dev(ctx, n, ctx->nvec.p, ctx->nvec.p, nullptr, nullptr, SC_MISC + 6));
-    hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, ctx->nvec.p, ctx->nvec.p, 1.0,
+    hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, ctx->nvec.p, ctx->nvec.p, 1.0,
                        ctx->dscal.p + SC_MISC + 6, 1);
     nv = ctx->nvec.p;
   }
   LinOp op{ctx, A, M, nv, n};
-  int iters = 0, restarts = 0, conv = 1;
+  int iters = 0, restarts = 0, res_restarts = 0, conv = 1;
   double worst_imp = 0.0, worst_exp = 0.0;
   // several right-hand sides of a non-singular system (the Helmholtz solve: one per velocity component) advance
   // together and share their matrix sweeps; the result is the one of solving them one after the other
@@ -1776,6 +1783,7 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
     ci.rel_res_explicit = std::sqrt(ctx->hscal[SC_MISC + 16]) / (bn == 0.0 ? 1.0 : bn);
     iters += ci.iters;
     restarts += ci.restarts;
+    res_restarts += ci.residual_restarts;
     conv = conv && ci.converged;
     worst_imp = std::max(worst_imp, ci.rel_res_implicit);
     worst_exp = std::max(worst_exp, ci.rel_res_explicit);
@@ -1815,6 +1823,7 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
   info->rel_res_implicit = worst_imp; info->rel_res_explicit = worst_exp;
   info->solve_ms = ms;
   info->reorth = ctx->stat_reorth;
+  info->residual_restarts = res_restarts;
   if (ctx->profile) {
     double tot_ms = 0.0;
     int calls = 0;
@@ -1852,6 +1861,9 @@ int isph_solve_block(isph_ctx *ctx, int dim, const isph_mat *const *blocks, cons
                "preconditioner and blocks are in different row numberings (build the preconditioner from one of the blocks)");
   isph_solver_params prm;
   if (prm_in) prm = *prm_in; else isph_solver_params_default(&prm);
+  int basis_bits = 64;
+  ISPH_CHECK(basis_bits_of(&prm, &basis_bits));
+  ISPH_REQUIRE(basis_bits == 64, "isph_solve_block keeps the fp64 Krylov basis: basis_bits = 32 is not available here");
   memset(info, 0, sizeof(*info));
   ISPH_CHECK(ensure_scalars(ctx));
   hipStream_t st = ctx->stream;

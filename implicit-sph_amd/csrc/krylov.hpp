@@ -13,6 +13,34 @@ namespace isph {
 
 constexpr int kDotBatch = 16;  // basis vectors whose partial sums a thread keeps in registers
 
+// The kernels that touch the Krylov basis are templates on its storage type BT: double, or float for the compressed
+// basis (isph_solver_params::basis_bits = 32).  A float entry is widened when it is read; every product, sum and
+// reduction is the fp64 one of the double instance, whose code the widening (a no-op there) leaves as it was.
+template <typename BT> struct BasisVec;
+// double: the column itself takes the new vector
+template <> struct BasisVec<double> {
+  typedef double2 pair;              // two adjacent rows in one load
+  typedef double *__restrict__ out;  // where a kernel writes a new basis vector
+};
+// float: the column takes the rounded values (round to nearest even, subnormals kept), cur their widened copy -- the
+// vector the preconditioner and the operator read next
+struct BasisOut32 {
+  float *col;
+  double *cur;
+};
+template <> struct BasisVec<float> {
+  typedef float2 pair;
+  typedef BasisOut32 out;
+};
+__device__ __forceinline__ bool basis_out_set(const double *o) { return o != nullptr; }
+__device__ __forceinline__ bool basis_out_set(const BasisOut32 &o) { return o.col != nullptr; }
+__device__ __forceinline__ void basis_put(double *o, long long i, double v) { o[i] = v; }
+__device__ __forceinline__ void basis_put(const BasisOut32 &o, long long i, double v) {
+  const float r = static_cast<float>(v);
+  o.col[i] = r;
+  o.cur[i] = static_cast<double>(r);
+}
+
 // partial[(k)*nblk + blockIdx] = sum over this block's rows of V_k[i]*w[i],
 // k in [0,nk); slot nk holds w.w.  V_k = V + k*ld.
 // Basis vectors are processed in batches of kDotBatch: every thread keeps one running sum per vector of the
@@ -21,7 +49,9 @@ constexpr int kDotBatch = 16;  // basis vectors whose partial sums a thread keep
 // The Gram-Schmidt form: two ADJACENT rows per thread and 16-byte load (ld is a multiple of 64 and the vectors come from the
 // pool: 16-byte aligned; the caller checks), one trip in flight -- 43.5 -> 36 us at nk ~ 27 against k_multi_dot<2> (two
 // strided rows, 8-byte loads).  The same change in the two update kernels below measured no gain (39.3 -> 40.1, 36.6 -> 37.6 us).
-__global__ __launch_bounds__(kBlock) void k_multi_dot_v2(int n, int nk, const double *__restrict__ V, long long ld,
+// (float basis: the same two rows per thread, one 8-byte load per vector)
+template <typename BT>
+__global__ __launch_bounds__(kBlock) void k_multi_dot_v2(int n, int nk, const BT *__restrict__ V, long long ld,
                                                          const double *__restrict__ w, double *__restrict__ partial) {
   __shared__ double sred[kDotBatch + 1][4];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -35,22 +65,22 @@ __global__ __launch_bounds__(kBlock) void k_multi_dot_v2(int n, int nk, const do
 #pragma unroll
     for (int u = 0; u < kDotBatch; ++u) acc[u] = 0.0;
     double ww = 0.0;
-    const double *__restrict__ vb = V + (long long)k0 * ld;
+    const BT *__restrict__ vb = V + (long long)k0 * ld;
     for (long long p = p0; p < np; p += stride) {
       const double2 wi = w2[p];
       if (last) ww = fma(wi.y, wi.y, fma(wi.x, wi.x, ww));
-      double2 v[kDotBatch];
+      typename BasisVec<BT>::pair v[kDotBatch];
 #pragma unroll
       for (int u = 0; u < kDotBatch; ++u)
-        if (u < nb) v[u] = reinterpret_cast<const double2 *>(vb + (long long)u * ld)[p];
+        if (u < nb) v[u] = reinterpret_cast<const typename BasisVec<BT>::pair *>(vb + (long long)u * ld)[p];
 #pragma unroll
       for (int u = 0; u < kDotBatch; ++u)
-        if (u < nb) acc[u] = fma(v[u].y, wi.y, fma(v[u].x, wi.x, acc[u]));
+        if (u < nb) acc[u] = fma((double)v[u].y, wi.y, fma((double)v[u].x, wi.x, acc[u]));
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // the odd last row
       const double wi = w[n - 1];
       if (last) ww = fma(wi, wi, ww);
-      for (int u = 0; u < nb; ++u) acc[u] = fma(vb[(long long)u * ld + n - 1], wi, acc[u]);
+      for (int u = 0; u < nb; ++u) acc[u] = fma((double)vb[(long long)u * ld + n - 1], wi, acc[u]);
     }
 #pragma unroll
     for (int u = 0; u < kDotBatch; ++u) {
@@ -75,8 +105,8 @@ __global__ __launch_bounds__(kBlock) void k_multi_dot_v2(int n, int nk, const do
   }
 }
 
-template <int ROWS>
-__global__ __launch_bounds__(kBlock) void k_multi_dot(int n, int nk, const double *__restrict__ V, long long ld,
+template <int ROWS, typename BT = double>
+__global__ __launch_bounds__(kBlock) void k_multi_dot(int n, int nk, const BT *__restrict__ V, long long ld,
                                                       const double *__restrict__ w,
                                                       double *__restrict__ partial) {
   __shared__ double sred[kDotBatch + 1][4];
@@ -90,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_dot(int n, int nk, const doubl
 #pragma unroll
     for (int u = 0; u < kDotBatch; ++u) acc[u] = 0.0;
     double ww = 0.0;
-    const double *__restrict__ vb = V + (long long)k0 * ld;
+    const BT *__restrict__ vb = V + (long long)k0 * ld;
     long long i = i0;
     if (ROWS == 2) {  // two rows per trip: twice the loads in flight per thread
       for (; i + stride < n; i += 2 * stride) {
@@ -99,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_dot(int n, int nk, const doubl
         double va[kDotBatch], vc[kDotBatch];
 #pragma unroll
         for (int u = 0; u < kDotBatch; ++u)
-          if (u < nb) { va[u] = vb[(long long)u * ld + i]; vc[u] = vb[(long long)u * ld + i + stride]; }
+          if (u < nb) { va[u] = (double)vb[(long long)u * ld + i]; vc[u] = (double)vb[(long long)u * ld + i + stride]; }
 #pragma unroll
         for (int u = 0; u < kDotBatch; ++u)
           if (u < nb) acc[u] = fma(vc[u], wb, fma(va[u], wa, acc[u]));
@@ -110,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void k_multi_dot(int n, int nk, const doubl
       if (last) ww = fma(wi, wi, ww);
 #pragma unroll
       for (int u = 0; u < kDotBatch; ++u)
-        if (u < nb) acc[u] = fma(vb[(long long)u * ld + i], wi, acc[u]);
+        if (u < nb) acc[u] = fma((double)vb[(long long)u * ld + i], wi, acc[u]);
     }
 #pragma unroll
     for (int u = 0; u < kDotBatch; ++u) {
@@ -169,16 +199,19 @@ __global__ __launch_bounds__(kBlock) void k_reduce_partials(int nk, int nblk, co
 // c[nk] = |w_new|^2: second pass when force (ICGS) or |w_new| < |w_old| / sqrt(2); |w_final|^2 = |w_new|^2 - |c2|^2
 // then, |w_new|^2 otherwise (Pythagoras: c2 is the projection of w_new on span V).  Workgroup 0 leaves the flag and
 // |w_final|^2 in dec_out[0..1] for the host.  Without a second pass w stays.
-// vnext != NULL: the normalised vector vnext = w_final / |w_final| is written in the same sweep, second pass or not.
-__global__ __launch_bounds__(kBlock) void k_multi_axpy_norm(int n, int nk, const double *__restrict__ V, long long ld,
+// vnext set: the normalised vector vnext = w_final / |w_final| is written in the same sweep, second pass or not (a float
+// basis: rounded into its column, and widened again into the fp64 vector the next operator application reads).
+template <typename BT>
+__global__ __launch_bounds__(kBlock) void k_multi_axpy_norm(int n, int nk, const BT *__restrict__ V, long long ld,
                                                             const double *__restrict__ c, double *__restrict__ w,
                                                             double *__restrict__ partial,
                                                             const double *__restrict__ dec_old = nullptr,
                                                             const double *__restrict__ dec_dn = nullptr, int dec_force = 0,
                                                             double *__restrict__ dec_out = nullptr,
-                                                            double *__restrict__ vnext = nullptr) {
+                                                            typename BasisVec<BT>::out vnext = {}) {
   __shared__ double sw[4];
   __shared__ double sdec[2];
+  const bool next = basis_out_set(vnext);
   bool second = true;
   double wfinal2 = 1.0;
   if (dec_old) {
@@ -197,17 +230,17 @@ __global__ __launch_bounds__(kBlock) void k_multi_axpy_norm(int n, int nk, const
     second = sdec[0] != 0.0;
     wfinal2 = sdec[1];
   }
-  if (!second && !vnext) return;
+  if (!second && !next) return;
   double a = 1.0;
-  if (vnext) a *= 1.0 / sqrt(wfinal2);
+  if (next) a *= 1.0 / sqrt(wfinal2);
   double ww = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     double s = w[i];
     if (second) {
-      for (int k = 0; k < nk; ++k) s = fma(-c[k], V[(long long)k * ld + i], s);
+      for (int k = 0; k < nk; ++k) s = fma(-c[k], (double)V[(long long)k * ld + i], s);
       w[i] = s;
     }
-    if (vnext) vnext[i] = a * s;
+    if (next) basis_put(vnext, i, a * s);
     ww = fma(s, s, ww);
   }
   ww = wave_sum(ww);
@@ -220,8 +253,8 @@ __global__ __launch_bounds__(kBlock) void k_multi_axpy_norm(int n, int nk, const
 //   w -= sum_k c[k] V_k ;  partial[k*nblk+b] = sum_rows V_k[i] * w_new[i] ;  slot nk = w_new . w_new
 // The second Gram-Schmidt pass needs V^T w_new; w_new[i] only depends on row i, so the projection is
 // accumulated while the row of V is still in registers: V is read once instead of twice per pass pair.
-template <int NK>
-__global__ __launch_bounds__(kBlock) void k_multi_axpy_dot(int n, int nk, const double *__restrict__ V, long long ld,
+template <int NK, typename BT = double>
+__global__ __launch_bounds__(kBlock) void k_multi_axpy_dot(int n, int nk, const BT *__restrict__ V, long long ld,
                                                            const double *__restrict__ c, double *__restrict__ w,
                                                            double *__restrict__ partial) {
   __shared__ double sred[NK + 1][4];
@@ -234,17 +267,61 @@ __global__ __launch_bounds__(kBlock) void k_multi_axpy_dot(int n, int nk, const 
   for (int u = 0; u < NK; ++u) acc[u] = 0.0;
   double ww = 0.0;
   const long long stride = (long long)gridDim.x * kBlock;
-  for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-    double v[NK];
+  if constexpr (sizeof(BT) == 8) {
+    for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+      double v[NK];
 #pragma unroll
-    for (int u = 0; u < NK; ++u) v[u] = u < nk ? V[(long long)u * ld + i] : 0.0;
-    double s = w[i];
+      for (int u = 0; u < NK; ++u) v[u] = u < nk ? V[(long long)u * ld + i] : 0.0;
+      double s = w[i];
 #pragma unroll
-    for (int u = 0; u < NK; ++u) s = fma(-sc[u], v[u], s);
-    w[i] = s;
-    ww = fma(s, s, ww);
+      for (int u = 0; u < NK; ++u) s = fma(-sc[u], v[u], s);
+      w[i] = s;
+      ww = fma(s, s, ww);
 #pragma unroll
-    for (int u = 0; u < NK; ++u) acc[u] = fma(v[u], s, acc[u]);
+      for (int u = 0; u < NK; ++u) acc[u] = fma(v[u], s, acc[u]);
+    }
+  } else {
+    // float basis: two ADJACENT rows per thread, so that a load is the 8 bytes per lane it is in the double instance
+    // (one row per thread, 4-byte loads: 83 us against the double instance's 39 us at nk ~ 22, measured) and the
+    // registers are the double instance's: NK float pairs + NK sums.  ld is a multiple of 64 and w comes from the
+    // pool: 8- and 16-byte aligned (ortho_enqueue checks).
+    typedef typename BasisVec<BT>::pair pair;
+    const long long np = n >> 1;
+    double2 *__restrict__ w2 = reinterpret_cast<double2 *>(w);
+    for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < np; p += stride) {
+      pair v[NK];
+#pragma unroll
+      for (int u = 0; u < NK; ++u) {
+        if (u < nk) v[u] = reinterpret_cast<const pair *>(V + (long long)u * ld)[p];
+        else v[u].x = v[u].y = 0;
+      }
+      double2 s = w2[p];
+#pragma unroll
+      for (int u = 0; u < NK; ++u) {
+        s.x = fma(-sc[u], (double)v[u].x, s.x);
+        s.y = fma(-sc[u], (double)v[u].y, s.y);
+      }
+      w2[p] = s;
+      ww = fma(s.y, s.y, fma(s.x, s.x, ww));
+      // the floats are widened a second time here: kept live across the update as doubles they double the registers
+      // and the 64-wide instance spills (364 bytes of scratch per lane); the empty statement makes them opaque
+#pragma unroll
+      for (int u = 0; u < NK; ++u) asm volatile("" : "+v"(v[u].x), "+v"(v[u].y));
+#pragma unroll
+      for (int u = 0; u < NK; ++u) acc[u] = fma((double)v[u].y, s.y, fma((double)v[u].x, s.x, acc[u]));
+    }
+    if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // the odd last row
+      const long long i = n - 1;
+      double s = w[i];
+#pragma unroll
+      for (int u = 0; u < NK; ++u)
+        if (u < nk) s = fma(-sc[u], (double)V[(long long)u * ld + i], s);
+      w[i] = s;
+      ww = fma(s, s, ww);
+#pragma unroll
+      for (int u = 0; u < NK; ++u)
+        if (u < nk) acc[u] = fma((double)V[(long long)u * ld + i], s, acc[u]);
+    }
   }
 #pragma unroll
   for (int u = 0; u < NK; ++u) {
@@ -264,11 +341,12 @@ __global__ __launch_bounds__(kBlock) void k_multi_axpy_dot(int n, int nk, const 
 }
 
 // x += sum_k c[k] Z_k   (solution update, c on device)
-__global__ void k_multi_axpy(int n, int nk, const double *__restrict__ Z, long long ld, const double *__restrict__ c,
+template <typename BT>
+__global__ void k_multi_axpy(int n, int nk, const BT *__restrict__ Z, long long ld, const double *__restrict__ c,
                              double *__restrict__ x) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
     double s = x[i];
-    for (int k = 0; k < nk; ++k) s = fma(c[k], Z[(long long)k * ld + i], s);
+    for (int k = 0; k < nk; ++k) s = fma(c[k], (double)Z[(long long)k * ld + i], s);
     x[i] = s;
   }
 }
@@ -293,13 +371,14 @@ __global__ __launch_bounds__(kBlock) void k_dot2(int n, const double *__restrict
   }
 }
 
-// y = a*x  with a = alpha_host * (inv_sqrt ? 1/sqrt(*s) : (s ? *s : 1))
-__global__ void k_scale_copy(int n, const double *__restrict__ x, double *__restrict__ y, double alpha,
+// y = a*x  with a = alpha_host * (inv_sqrt ? 1/sqrt(*s) : (s ? *s : 1));  BT = float: y is a column of the float basis
+template <typename BT>
+__global__ void k_scale_copy(int n, const double *__restrict__ x, typename BasisVec<BT>::out y, double alpha,
                              const double *__restrict__ s, int inv_sqrt) {
   double a = alpha;
   if (s) a *= inv_sqrt ? 1.0 / sqrt(*s) : *s;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = a * x[i];
+    basis_put(y, i, a * x[i]);
 }
 
 // y += (alpha * (*s)) * x       (s on device, may be NULL)

@@ -390,7 +390,7 @@ int isph_solve_poisson_boltzmann(isph_ctx *ctx, isph_mat *J, const isph_pb_param
     if (rc != ISPH_SUCCESS) break;
     ++age;
     if (n > 0) {
-      hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, (const double *)R->F.p, R->rhs.p, -1.0,
+      hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)R->F.p, R->rhs.p, -1.0,
                          (const double *)nullptr, 0);
       rc = hipMemsetAsync(R->delta.p, 0, sizeof(double) * (size_t)n, st) == hipSuccess ? ISPH_SUCCESS
                                                                                         : fail("memset failed", __FILE__, __LINE__);

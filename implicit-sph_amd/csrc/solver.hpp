@@ -7,6 +7,7 @@
 // every vector operation is a kernel from krylov.hpp / sell.hpp.
 #pragma once
 #include <cmath>
+#include <type_traits>
 
 #include "comm.hpp"
 #include "core.hpp"
@@ -277,7 +278,7 @@ inline int cgs_pass(isph_ctx *ctx, int n, int nk, const double *V, long long ld,
                      ctx->dscal.p + SC_DOT);
   ISPH_CHECK(allreduce_inplace(ctx, ctx->dscal.p + SC_DOT, nk + 1));
   const int g2 = stream_grid(n);
-  hipLaunchKernelGGL(k_multi_axpy_norm, dim3(g2), dim3(kBlock), 0, ctx->stream, n, nk, V, ld, ctx->dscal.p + SC_DOT, w,
+  hipLaunchKernelGGL(k_multi_axpy_norm<double>, dim3(g2), dim3(kBlock), 0, ctx->stream, n, nk, V, ld, ctx->dscal.p + SC_DOT, w,
                      ctx->partial.p);
   hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(kBlock), 0, ctx->stream, 1, g2, ctx->partial.p,
                      ctx->dscal.p + SC_DOT + nk + 1);
@@ -294,24 +295,30 @@ inline int cgs_pass(isph_ctx *ctx, int n, int nk, const double *V, long long ld,
 // queue the next preconditioner/operator application before it looks at the scalars.
 // Mailbox: c at SC_DOT.., |w|^2 at SC_DOT+nk; c2 at SC_Y.., |w_new|^2 at SC_Y+nk; flag, |w_final|^2 at SC_ORTHO..
 // (|w_final|^2 = |w_new|^2 - |c2|^2 when the second pass runs: see k_multi_axpy_norm)
+// BT = float: the same launches on a float basis (krylov.hpp BasisVec); vnext then names the float column and the fp64
+// vector that receives the widened rounded values.
 enum { SC_ORTHO = SC_MISC + 20 };
-inline int ortho_enqueue(isph_ctx *ctx, int n, int nk, const double *V, long long ld, double *w, int ortho, double *vnext,
-                         bool deflate = false, int mb = 0) {
+template <typename BT>
+inline int ortho_enqueue(isph_ctx *ctx, int n, int nk, const BT *V, long long ld, double *w, int ortho,
+                         typename BasisVec<BT>::out vnext, bool deflate = false, int mb = 0) {
   int g = stream_grid(n);
   // 2 workgroups per CU with two rows per thread in flight: multi-dot 53.6 -> 44.4 us, the 64-wide fused update
   // 92.8 -> 79.5 us against 4 workgroups per CU, one row (rocprofv3, bench matrix)
   if (g > 1024) g = 1024;
   ISPH_CHECK(ctx->partial.reserve((size_t)kMaxRedBlocks * 66));
   hipStream_t st = ctx->stream;
+  if (sizeof(BT) == 4)  // the float instances of the update kernels read two rows per load
+    ISPH_REQUIRE((reinterpret_cast<uintptr_t>(w) & 15) == 0 && (reinterpret_cast<uintptr_t>(V) & 7) == 0 && ld % 2 == 0,
+                 "basis_bits = 32: the Krylov vectors must be 16-byte aligned");
   double *dh1 = ctx->dscal.p + mb + SC_DOT, *dh2 = ctx->dscal.p + mb + SC_Y, *dor = ctx->dscal.p + mb + SC_ORTHO;  // mb: mailbox of this right-hand side
   constexpr int dot_grid = 512;   // (256 ... 1024 workgroups: the same 36 us for the multi-dot, the fused update slower above 512)
   if (g > dot_grid) g = dot_grid;
   {
     ProfScope prof(ctx, PROF_MULTI_DOT);
     if ((reinterpret_cast<uintptr_t>(w) & 15) == 0 && (reinterpret_cast<uintptr_t>(V) & 15) == 0)
-      hipLaunchKernelGGL(k_multi_dot_v2, dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, w, ctx->partial.p);
+      hipLaunchKernelGGL(k_multi_dot_v2<BT>, dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, w, ctx->partial.p);
     else
-      hipLaunchKernelGGL((k_multi_dot<2>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, w, ctx->partial.p);
+      hipLaunchKernelGGL((k_multi_dot<2, BT>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, w, ctx->partial.p);
   }
   hipLaunchKernelGGL(k_reduce_partials, dim3(nk + 1), dim3(kBlock), 0, st, nk + 1, g, ctx->partial.p, dh1,
                      (const double *)nullptr);
@@ -319,13 +326,13 @@ inline int ortho_enqueue(isph_ctx *ctx, int n, int nk, const double *V, long lon
   {
     ProfScope prof(ctx, PROF_MULTI_AXPY_DOT);
     if (nk <= 16)
-      hipLaunchKernelGGL((k_multi_axpy_dot<16>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
+      hipLaunchKernelGGL((k_multi_axpy_dot<16, BT>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
     else if (nk <= 32)
-      hipLaunchKernelGGL((k_multi_axpy_dot<32>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
+      hipLaunchKernelGGL((k_multi_axpy_dot<32, BT>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
     else if (nk <= 48)  // between the two: 96 + 96 registers keep two waves per SIMD where the 64-wide instance has one
-      hipLaunchKernelGGL((k_multi_axpy_dot<48>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
+      hipLaunchKernelGGL((k_multi_axpy_dot<48, BT>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
     else
-      hipLaunchKernelGGL((k_multi_axpy_dot<64>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
+      hipLaunchKernelGGL((k_multi_axpy_dot<64, BT>), dim3(g), dim3(kBlock), 0, st, n, nk, V, ld, dh1, w, ctx->partial.p);
   }
   hipLaunchKernelGGL(k_reduce_partials, dim3(nk + 1), dim3(kBlock), 0, st, nk + 1, g, ctx->partial.p, dh2,
                      (const double *)nullptr);
@@ -335,7 +342,7 @@ inline int ortho_enqueue(isph_ctx *ctx, int n, int nk, const double *V, long lon
   // basis vector (vnext = w / |w|) leave in one sweep
   {
     ProfScope prof(ctx, PROF_MULTI_AXPY_NORM);
-    hipLaunchKernelGGL(k_multi_axpy_norm, dim3(g2), dim3(kBlock), 0, st, n, nk, V, ld, (const double *)dh2, w, ctx->partial.p,
+    hipLaunchKernelGGL(k_multi_axpy_norm<BT>, dim3(g2), dim3(kBlock), 0, st, n, nk, V, ld, (const double *)dh2, w, ctx->partial.p,
                        (const double *)(dh1 + nk), deflate ? (const double *)dh1 : (const double *)nullptr, ortho == 1 ? 1 : 0,
                        dor, vnext);
   }
@@ -369,13 +376,31 @@ inline int orthogonalize(isph_ctx *ctx, int n, int j, const double *V, long long
     return ISPH_SUCCESS;
   }
   // DGKS / ICGS: device-only part, then wait for the scalars
-  ISPH_CHECK(ortho_enqueue(ctx, n, nk, V, ld, w, ortho, nullptr));
+  ISPH_CHECK(ortho_enqueue<double>(ctx, n, nk, V, ld, w, ortho, nullptr));
   ISPH_CHECK(fetch_scalars(ctx, 0, SC_COUNT));
   ortho_collect(ctx, nk, h, wnorm);
   return ISPH_SUCCESS;
 }
 
-inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_params *prm, isph_solve_info *info) {
+// isph_solver_params::basis_bits as a width: 64 (0 means the same) or 32, anything else is refused
+inline int basis_bits_of(const isph_solver_params *prm, int *bits) {
+  *bits = prm->basis_bits == 0 ? 64 : prm->basis_bits;
+  ISPH_REQUIRE(*bits == 64 || *bits == 32, "basis_bits must be 64 (0 means the same) or 32");
+  return ISPH_SUCCESS;
+}
+
+// BT = float (basis_bits = 32): the compressed basis.  Every basis vector is stored rounded to float -- v_0 = fl32(r / beta),
+// v_{j+1} = fl32(w / |w|) -- and widened wherever it is read; the sweep that writes a column also writes its widened copy
+// to vcur, which is what the preconditioner and the operator get, so that A Z_j = V_{j+1} H_j holds for the ROUNDED
+// vectors up to that one rounding per column.  Z, w, t, x, every dot, norm, the DGKS test, the Hessenberg matrix and
+// the Givens rotations stay fp64.  A singular system takes the explicit projection of op.apply (the null vector stays
+// an fp64 vector outside the float basis), as IMGS does.  Within one cycle the true residual stalls at 3-4e-8 |r0|
+// (the rounding of v_0 and of the first columns), so a recurrence residual <= tol is confirmed by the true residual
+// -- the operator application a restart makes anyway -- and the method restarts from it when it is above tol
+// (info->residual_restarts).
+template <typename BT>
+inline int gmres_t(const LinOp &op, const double *b, double *x, const isph_solver_params *prm, isph_solve_info *info) {
+  constexpr bool f32 = std::is_same<BT, float>::value;
   isph_ctx *ctx = op.ctx;
   const int n = op.n, m = prm->num_blocks;
   ISPH_REQUIRE(m >= 1 && m <= 62, "Num Blocks must be in [1,62]");
@@ -384,13 +409,29 @@ inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_
   // to n, so V^T (w - (w.n) n) = V^T w: the projection of PoissonProjection::Apply is folded into the Gram-Schmidt
   // step (n rides along as one more vector of the multi-dot / update), which saves one reduction, one all-reduce
   // and one vector pass per iteration.  IMGS keeps the explicit projection.
-  const bool deflate = op.nvec != nullptr && !op.blk && prm->ortho != 2;
-  ISPH_CHECK(ctx->V.reserve((size_t)ld * (size_t)(m + 2)));
+  const bool deflate = !f32 && op.nvec != nullptr && !op.blk && prm->ortho != 2;
+  if (f32) {  // 4 ld (m + 1) + 8 ld bytes instead of 8 ld (m + 2); the basis of the other width goes back to the pool
+    ctx->V.release();
+    ISPH_CHECK(ctx->V32.reserve((size_t)ld * (size_t)(m + 1)));
+    ISPH_CHECK(ctx->vcur.reserve((size_t)ld));
+  } else {
+    ctx->V32.release();
+    ctx->vcur.release();
+    ISPH_CHECK(ctx->V.reserve((size_t)ld * (size_t)(m + 2)));
+  }
   if (prm->flexible) ISPH_CHECK(ctx->Z.reserve((size_t)ld * (size_t)m));
   ISPH_CHECK(ctx->wv.reserve((size_t)ld));
   ISPH_CHECK(ctx->tv.reserve((size_t)ld));
-  double *Vall = ctx->V.p, *V = ctx->V.p + (deflate ? ld : 0), *Z = ctx->Z.p, *w = ctx->wv.p, *t = ctx->tv.p;
-  if (deflate)
+  BT *Vall, *V;
+  if constexpr (f32) Vall = V = ctx->V32.p;
+  else { Vall = ctx->V.p; V = ctx->V.p + (deflate ? ld : 0); }
+  double *Z = ctx->Z.p, *w = ctx->wv.p, *t = ctx->tv.p, *vcur = ctx->vcur.p;
+  auto column = [&](int col) -> typename BasisVec<BT>::out {  // where a kernel writes basis vector `col`
+    if constexpr (f32) return BasisOut32{V + (long long)col * ld, vcur};
+    else return V + (long long)col * ld;
+  };
+  if constexpr (!f32)
+    if (deflate)
     ISPH_CHECK_HIP(hipMemcpyAsync(Vall, op.nvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   std::vector<double> H((size_t)(m + 1) * (size_t)m, 0.0), cs((size_t)m), sn((size_t)m), g((size_t)m + 1), y((size_t)m);
   const int sg = stream_grid(n);
@@ -405,19 +446,21 @@ inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_
   const double scale = beta == 0.0 ? 1.0 : beta;  // Belos: zero scale -> 1
   info->iters = 0;
   info->restarts = 0;
+  info->residual_restarts = 0;
   info->converged = 0;
   info->rel_res_implicit = beta / scale;
   if (beta / scale <= prm->tol) info->converged = 1;
 
   while (!info->converged && info->iters < prm->max_iters) {
-    hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, w, V, 1.0 / beta, (const double *)nullptr, 0);
+    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, column(0), 1.0 / beta, (const double *)nullptr, 0);
     std::fill(g.begin(), g.end(), 0.0);
     g[0] = beta;
     int j = 0;
     // queue z_j = M^-1 v_j, w = Op z_j
     auto enqueue_op = [&](int col) -> int {
-      const double *zj;
-      double *vj = V + (long long)col * ld;
+      const double *zj, *vj;
+      if constexpr (f32) vj = vcur;  // the widened column `col`: the sweep that wrote the column left it there
+      else vj = V + (long long)col * ld;
       if (prm->flexible) {
         ISPH_CHECK(op.prec(vj, Z + (long long)col * ld));
         zj = Z + (long long)col * ld;
@@ -435,15 +478,17 @@ inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_
       double *h = &H[(size_t)j * (size_t)(m + 1)];
       double wn = 0.0;
       if (prm->ortho == 2) {
-        ISPH_CHECK(orthogonalize(ctx, n, j, V, ld, w, h, prm->ortho, &wn));
-        if (wn != 0.0)
-          hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, w, V + (long long)(j + 1) * ld, 1.0 / wn,
-                             (const double *)nullptr, 0);
+        if constexpr (!f32) {
+          ISPH_CHECK(orthogonalize(ctx, n, j, V, ld, w, h, prm->ortho, &wn));
+          if (wn != 0.0)
+            hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, w, V + (long long)(j + 1) * ld, 1.0 / wn,
+                               (const double *)nullptr, 0);
+        }
       } else {
         // the whole Gram-Schmidt step and v_{j+1} = w/|w| stay on the device; the host only waits for the copy of
         // the scalar mailbox, and while it does the Givens update the GPU already works on the next column
         const int nkt = j + 1 + (deflate ? 1 : 0);  // basis vectors (+ n) the step projects against
-        ISPH_CHECK(ortho_enqueue(ctx, n, nkt, Vall, ld, w, prm->ortho, V + (long long)(j + 1) * ld, deflate));
+        ISPH_CHECK(ortho_enqueue<BT>(ctx, n, nkt, Vall, ld, w, prm->ortho, column(j + 1), deflate));
         ISPH_CHECK_HIP(hipMemcpyAsync(ctx->hscal, ctx->dscal.p, sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, st));
         ISPH_CHECK_HIP(hipEventRecord(ctx->ev_fetch, st));
         if (j + 1 < m && info->iters + 1 < prm->max_iters) {  // speculative: discarded if this column converges
@@ -491,27 +536,46 @@ inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_
     for (int k = 0; k < j; ++k) ctx->hscal[SC_Y + k] = y[k];
     ISPH_CHECK_HIP(hipMemcpyAsync(ctx->dscal.p + SC_Y, ctx->hscal + SC_Y, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, st));
     if (prm->flexible) {
-      hipLaunchKernelGGL(k_multi_axpy, dim3(sg), dim3(kBlock), 0, st, n, j, Z, ld, ctx->dscal.p + SC_Y, x);
+      hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, st, n, j, Z, ld, ctx->dscal.p + SC_Y, x);
     } else {
       hipLaunchKernelGGL(k_fill, dim3(sg), dim3(kBlock), 0, st, n, w, 0.0);
-      hipLaunchKernelGGL(k_multi_axpy, dim3(sg), dim3(kBlock), 0, st, n, j, V, ld, ctx->dscal.p + SC_Y, w);
+      hipLaunchKernelGGL(k_multi_axpy<BT>, dim3(sg), dim3(kBlock), 0, st, n, j, (const BT *)V, ld, (const double *)(ctx->dscal.p + SC_Y), w);
       ISPH_CHECK(op.prec(w, t));
       hipLaunchKernelGGL(k_axpy_dev, dim3(sg), dim3(kBlock), 0, st, n, 1.0, (const double *)nullptr, t, x);
     }
     // the H2D source (hscal) must not be rewritten before the copy has run
     ISPH_CHECK_HIP(hipStreamSynchronize(st));
-    if (info->converged || info->iters >= prm->max_iters) break;
-    if (info->restarts >= prm->max_restarts) break;
-    ++info->restarts;
+    const bool confirm = f32 && info->converged;  // float basis: the recurrence says converged, the true residual decides
+    if (!confirm) {
+      if (info->converged || info->iters >= prm->max_iters) break;
+      if (info->restarts >= prm->max_restarts) break;
+      ++info->restarts;
+    }
     ISPH_CHECK(op.apply(x, w));
     hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, b, w);
     ISPH_CHECK(dot_dev(ctx, n, w, w, nullptr, nullptr, SC_MISC + 4));
     ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
     beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
+    if (confirm) {
+      if (beta / scale <= prm->tol) break;
+      info->converged = 0;  // restart from this residual
+      if (info->iters >= prm->max_iters || info->restarts >= prm->max_restarts) break;
+      ++info->restarts;
+      ++info->residual_restarts;
+    }
     if (beta == 0.0) { info->converged = 1; break; }
   }
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
+}
+
+inline int gmres(const LinOp &op, const double *b, double *x, const isph_solver_params *prm, isph_solve_info *info) {
+  int bits = 64;
+  ISPH_CHECK(basis_bits_of(prm, &bits));
+  if (bits == 64) return gmres_t<double>(op, b, x, prm, info);
+  ISPH_REQUIRE(prm->ortho != 2, "basis_bits = 32 takes DGKS or ICGS: IMGS (ortho = 2) keeps the fp64 basis");
+  ISPH_REQUIRE(!op.blk, "basis_bits = 32 is not available for the blocked operator (isph_solve_block)");
+  return gmres_t<float>(op, b, x, prm, info);
 }
 
 // K right-hand sides of one matrix (the Helmholtz system: one per velocity component, pair_isph.cpp:925-966) advanced
@@ -524,13 +588,23 @@ inline bool gmres_lockstep_ok(const LinOp &op, const isph_solver_params *prm, in
   return K >= 2 && K <= kMaxLockstep && !op.nvec && !op.blk && prm->flexible && prm->ortho != 2 && prm->solver_type == 0;
 }
 
-inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, double *const *xs, const isph_solver_params *prm,
-                          isph_solve_info *infos) {
+template <typename BT>
+inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, double *const *xs, const isph_solver_params *prm,
+                            isph_solve_info *infos) {
+  constexpr bool f32 = std::is_same<BT, float>::value;  // every system its own float basis and widened current column
   isph_ctx *ctx = op.ctx;
   const int n = op.n, m = prm->num_blocks;
   ISPH_REQUIRE(m >= 1 && m <= 62, "Num Blocks must be in [1,62]");
   const long long ld = ((long long)n + 63) / 64 * 64;
-  ISPH_CHECK(ctx->V.reserve((size_t)ld * (size_t)(m + 2) * (size_t)K));
+  if (f32) {
+    ctx->V.release();
+    ISPH_CHECK(ctx->V32.reserve((size_t)ld * (size_t)(m + 1) * (size_t)K));
+    ISPH_CHECK(ctx->vcur.reserve((size_t)ld * (size_t)K));
+  } else {
+    ctx->V32.release();
+    ctx->vcur.release();
+    ISPH_CHECK(ctx->V.reserve((size_t)ld * (size_t)(m + 2) * (size_t)K));
+  }
   ISPH_CHECK(ctx->Z.reserve((size_t)ld * (size_t)m * (size_t)K));
   ISPH_CHECK(ctx->wv.reserve((size_t)ld * (size_t)K));
   while ((int)ctx->ev_ls.size() < K) {
@@ -539,7 +613,8 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
     ctx->ev_ls.push_back(e);
   }
   struct Sys {
-    double *V, *Z, *w;
+    BT *V;
+    double *Z, *w, *vcur = nullptr;
     std::vector<double> H, cs, sn, g, y;
     double beta = 0.0, scale = 1.0;
     int j = 0;
@@ -552,12 +627,13 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
   double *yout[kMaxLockstep];
   for (int k = 0; k < K; ++k) {
     Sys &s = sys[(size_t)k];
-    s.V = ctx->V.p + (size_t)k * ld * (size_t)(m + 2);
+    if constexpr (f32) { s.V = ctx->V32.p + (size_t)k * ld * (size_t)(m + 1); s.vcur = ctx->vcur.p + (size_t)k * ld; }
+    else s.V = ctx->V.p + (size_t)k * ld * (size_t)(m + 2);
     s.Z = ctx->Z.p + (size_t)k * ld * (size_t)m;
     s.w = ctx->wv.p + (size_t)k * ld;
     s.H.assign((size_t)(m + 1) * (size_t)m, 0.0);
     s.cs.assign((size_t)m, 0.0); s.sn.assign((size_t)m, 0.0); s.g.assign((size_t)m + 1, 0.0); s.y.assign((size_t)m, 0.0);
-    infos[k].iters = 0; infos[k].restarts = 0; infos[k].converged = 0;
+    infos[k].iters = 0; infos[k].restarts = 0; infos[k].residual_restarts = 0; infos[k].converged = 0;
     xin[k] = xs[k]; yout[k] = s.w;
   }
   // r0 = b - A x for every system
@@ -572,9 +648,13 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
     infos[k].rel_res_implicit = s.beta / s.scale;
     if (s.beta / s.scale <= prm->tol) { infos[k].converged = 1; s.done = true; }
   }
+  auto column = [&](Sys &s, int col) -> typename BasisVec<BT>::out {
+    if constexpr (f32) return BasisOut32{s.V + (long long)col * ld, s.vcur};
+    else return s.V + (long long)col * ld;
+  };
   auto start_cycle = [&](int k) {
     Sys &s = sys[(size_t)k];
-    hipLaunchKernelGGL(k_scale_copy, dim3(sg), dim3(kBlock), 0, st, n, s.w, s.V, 1.0 / s.beta, (const double *)nullptr, 0);
+    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)s.w, column(s, 0), 1.0 / s.beta, (const double *)nullptr, 0);
     std::fill(s.g.begin(), s.g.end(), 0.0);
     s.g[0] = s.beta;
     s.j = 0;
@@ -592,16 +672,26 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
     }
     for (int q = 0; q < j; ++q) ctx->hscal[mb + SC_Y + q] = s.y[(size_t)q];
     ISPH_CHECK_HIP(hipMemcpyAsync(ctx->dscal.p + mb + SC_Y, ctx->hscal + mb + SC_Y, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_multi_axpy, dim3(sg), dim3(kBlock), 0, st, n, j, s.Z, ld, ctx->dscal.p + mb + SC_Y, xs[k]);
+    hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, st, n, j, s.Z, ld, ctx->dscal.p + mb + SC_Y, xs[k]);
     ISPH_CHECK_HIP(hipStreamSynchronize(st));  // the H2D source must not be rewritten before the copy has run
     s.in_cycle = false;
-    if (inf.converged || inf.iters >= prm->max_iters || inf.restarts >= prm->max_restarts) { s.done = true; return ISPH_SUCCESS; }
-    ++inf.restarts;
+    const bool confirm = f32 && inf.converged;  // as in gmres_t: the true residual decides
+    if (!confirm) {
+      if (inf.converged || inf.iters >= prm->max_iters || inf.restarts >= prm->max_restarts) { s.done = true; return ISPH_SUCCESS; }
+      ++inf.restarts;
+    }
     ISPH_CHECK(op.apply(xs[k], s.w));
     hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, bs[k], s.w);
     ISPH_CHECK(dot_dev(ctx, n, s.w, s.w, nullptr, nullptr, SC_MISC + 4));
     ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
     s.beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
+    if (confirm) {
+      if (s.beta / s.scale <= prm->tol) { s.done = true; return ISPH_SUCCESS; }
+      inf.converged = 0;
+      if (inf.iters >= prm->max_iters || inf.restarts >= prm->max_restarts) { s.done = true; return ISPH_SUCCESS; }
+      ++inf.restarts;
+      ++inf.residual_restarts;
+    }
     if (s.beta == 0.0) { inf.converged = 1; s.done = true; return ISPH_SUCCESS; }
     start_cycle(k);
     return ISPH_SUCCESS;
@@ -623,7 +713,8 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
       double *zout[kMaxLockstep];
       for (int a = 0; a < na; ++a) {
         Sys &s = sys[(size_t)act[a]];
-        vin[a] = s.V + (long long)s.j * ld;
+        if constexpr (f32) vin[a] = s.vcur;
+        else vin[a] = s.V + (long long)s.j * ld;
         zout[a] = s.Z + (long long)s.j * ld;
         xin[a] = zout[a];
         yout[a] = s.w;
@@ -637,7 +728,7 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
     for (int a = 0; a < na; ++a) {
       const int k = act[a], mb = k * SC_COUNT;
       Sys &s = sys[(size_t)k];
-      ISPH_CHECK(ortho_enqueue(ctx, n, s.j + 1, s.V, ld, s.w, prm->ortho, s.V + (long long)(s.j + 1) * ld, false, mb));
+      ISPH_CHECK(ortho_enqueue<BT>(ctx, n, s.j + 1, s.V, ld, s.w, prm->ortho, column(s, s.j + 1), false, mb));
       ISPH_CHECK_HIP(hipMemcpyAsync(ctx->hscal + mb, ctx->dscal.p + mb, sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, st));
       ISPH_CHECK_HIP(hipEventRecord(ctx->ev_ls[(size_t)k], st));
     }
@@ -677,6 +768,13 @@ inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, doubl
   }
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
+}
+
+inline int gmres_lockstep(const LinOp &op, int K, const double *const *bs, double *const *xs, const isph_solver_params *prm,
+                          isph_solve_info *infos) {
+  int bits = 64;
+  ISPH_CHECK(basis_bits_of(prm, &bits));
+  return bits == 32 ? gmres_lockstep_t<float>(op, K, bs, xs, prm, infos) : gmres_lockstep_t<double>(op, K, bs, xs, prm, infos);
 }
 
 // Belos BlockCGSolMgr, block size 1: the right-preconditioner slot is the

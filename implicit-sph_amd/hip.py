@@ -53,12 +53,15 @@ class SolverParams(C.Structure):
     (ref: solver_lin_belos.h:224-264)."""
     _fields_ = [("solver_type", C.c_int), ("flexible", C.c_int), ("num_blocks", C.c_int),
                 ("max_iters", C.c_int), ("max_restarts", C.c_int), ("tol", C.c_double),
-                ("ortho", C.c_int), ("verbose", C.c_int), ("num_recycled", C.c_int)]
+                ("ortho", C.c_int), ("verbose", C.c_int), ("num_recycled", C.c_int), ("basis_bits", C.c_int)]
 
     def __init__(self, solver_type=0, flexible=1, num_blocks=50, max_iters=500, max_restarts=15, tol=1e-8,
-                 ortho=0, verbose=0, num_recycled=50):
-        """solver_type 0 "Block GMRES", 1 "Block CG", 2 "Recycling GMRES" (GCRO-DR(num_blocks, num_recycled))"""
-        super().__init__(solver_type, flexible, num_blocks, max_iters, max_restarts, tol, ortho, verbose, num_recycled)
+                 ortho=0, verbose=0, num_recycled=50, basis_bits=0):
+        """solver_type 0 "Block GMRES", 1 "Block CG", 2 "Recycling GMRES" (GCRO-DR(num_blocks, num_recycled));
+        basis_bits 0 / 64: the fp64 Krylov basis, 32: the basis stored in single precision (GMRES only, see
+        include/isph_hip.h)"""
+        super().__init__(solver_type, flexible, num_blocks, max_iters, max_restarts, tol, ortho, verbose, num_recycled,
+                         basis_bits)
 
 
 class PBParams(C.Structure):
@@ -92,7 +95,7 @@ class SolveInfo(C.Structure):
     _fields_ = [("converged", C.c_int), ("iters", C.c_int), ("restarts", C.c_int),
                 ("rel_res_implicit", C.c_double), ("rel_res_explicit", C.c_double),
                 ("prec_setup_ms", C.c_double), ("solve_ms", C.c_double), ("spmv_ms", C.c_double),
-                ("spmv_calls", C.c_int), ("reorth", C.c_int)]
+                ("spmv_calls", C.c_int), ("reorth", C.c_int), ("residual_restarts", C.c_int)]
 
 
 class OrderGeometry(C.Structure):

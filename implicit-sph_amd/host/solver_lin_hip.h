@@ -43,6 +43,8 @@ class SolverLin_HIP : public SolverLin {
       _param->set("Output Frequency", 5);
       _param->set("Output Style", 1);
       _param->set("Verbosity", 33);
+      // device-side extension (not a reference key), "Solver Type" = "Block GMRES" only: "isph: krylov basis bits" = 32
+      // stores the Krylov basis rounded to float (isph_solver_params::basis_bits).  Not set here: absent means 64.
     } else if (_param.get() != param) {
       _param = Teuchos::rcp(param, false);
     }
@@ -66,12 +68,21 @@ class SolverLin_HIP : public SolverLin {
     const std::string ortho = _param->get("Orthogonalization", "DGKS");
     p.ortho = ortho == "ICGS" ? 1 : ortho == "IMGS" ? 2 : 0;
     p.verbose = 0;
+    p.basis_bits = _param->get("isph: krylov basis bits", 64);
     return p;
+  }
+  // "isph: krylov basis bits" other than 64 or 32 is refused here, before anything is built
+  bool basisBitsAvailable() {
+    const int bits = _param->get("isph: krylov basis bits", 64);
+    if (bits == 64 || bits == 32) return true;
+    std::fprintf(stderr, ">> SolverLin_HIP: \"isph: krylov basis bits\" = %d is not available; available: 64, 32\n", bits);
+    return false;
   }
 
   int solveProblem(PrecondWrapper *prec = NULL, const char *name = NULL) {
     if (_comm.MyPID() == 0 && name != NULL) std::cout << ">> Belos::Label - " << name << std::endl;
     setParameters(_param.get());
+    if (!basisBitsAvailable()) return LAMMPS_FAILURE;
     if (ensureContext() != ISPH_SUCCESS) return LAMMPS_FAILURE;
     if (!_A || !_x || !_b) return LAMMPS_FAILURE;
 
@@ -156,6 +167,7 @@ class SolverLin_HIP : public SolverLin {
       return LAMMPS_FAILURE;
     }
     setParameters(_param.get());
+    if (!basisBitsAvailable()) return LAMMPS_FAILURE;
     if (ensureContext() != ISPH_SUCCESS) return LAMMPS_FAILURE;
     isph_mat *blk[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     const isph_mat *cblk[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};

@@ -349,7 +349,36 @@ void isph_prec_destroy(isph_prec *M);
 /* ---- solve ------------------------------------------------------------ */
 
 /* Same keys and defaults as SolverLin_Belos::setParameters
- * (ref: solver_lin_belos.h:224-264). */
+ * (ref: solver_lin_belos.h:224-264).
+ * basis_bits (not a reference parameter): 64 (the default; 0 means the same) or 32; any other value is refused.  With 32
+ * and solver_type 0 -- flexible or not, DGKS or ICGS, one right-hand side or the lockstep solve of several -- the Krylov
+ * basis is stored in single precision (the compressed-basis GMRES of the literature): v_0 = fl32(r / beta) and
+ * v_{j+1} = fl32(w / |w|), round to nearest even, subnormals kept.  Every read widens the entry to double; the dots,
+ * updates, norms, the DGKS decision, the Hessenberg matrix and the Givens rotations are the fp64 ones, two-stage and
+ * deterministic as before.  The preconditioner and the operator get the widened ROUNDED vector (the sweep that writes
+ * a float column writes it to one fp64 buffer as well), so A Z_j = V_{j+1} H_j holds for the stored vectors up to that
+ * one rounding per column.  Z stays fp64 and x += Z y is unchanged; the non-flexible form is x += M^-1 (V y) with the
+ * float columns widened; w, x and b stay fp64.  The null vector of a singular system stays an fp64 vector: the solve
+ * takes the explicit projection y - (y.n) n after every product (what IMGS does at 64 bits) instead of carrying n as a
+ * column of the basis -- chosen because it keeps every Gram-Schmidt kernel on one storage type; the deflated form was
+ * not built, so the two were not timed against each other.  The basis takes 4 ld (m + 1) + 8 ld bytes instead of
+ * 8 ld (m + 2), ld = the rows rounded up to 64.
+ * Within one restart cycle the TRUE residual of such a solve stalls at 3-4e-8 |r0| although the recurrence residual
+ * goes on falling: the rounding of v_0 and of the first columns, whose coefficients y_j are the largest.  So when the
+ * recurrence residual reaches tol, the true residual |b - Op(x)| / scale is computed (the operator application a
+ * restart makes, same scale as the recurrence test): <= tol is convergence, otherwise the method restarts from that
+ * residual, which counts in isph_solve_info::restarts and in residual_restarts.  On the host restatement
+ * (tests/krylov_cb_reference.py) one such restart costs 0-4 iterations at tol 1e-8.  max_restarts and max_iters end
+ * the solve as before; with tol = 0 the confirmation never fails a converged solve.
+ * Measured at 100^3 (profiles/basis_f32_100cubed.txt; FGMRES(50), DGKS, tol 1e-8, 32 against 64 bits in one
+ * run): k_multi_dot 21.8 against 35.9 us and k_multi_axpy_norm 24.5 against 36.0 us per launch (0.61 and 0.68 of the time
+ * for 0.52 and 0.57 of the bytes); the fused update k_multi_axpy_dot is not faster at 32 bits, 38.5 against 39.5 us.  The
+ * solve: 33.89 against 34.28 ms with "bjacobi-ilu0" (72 against 71 iterations, one restart either way), but 15.62 against
+ * 14.97 ms with "jacobi" (45 against 43 iterations) and 18.33 against 16.53 ms with "chebyshev3" (23 against 22), where
+ * the confirmation costs one restart; pool peak 868 against 1072 MB.  Not timed on more than one rank.
+ * Refused with basis_bits = 32: solver_type 1 and 2, ortho = 2 (IMGS), isph_solve_block.  With 64 or 0 the launches, the
+ * arguments and the bits of x are those of a library without the field.
+ * Call isph_solver_params_default FIRST and then change fields: the struct grows at its tail. */
 typedef struct {
   int solver_type;   /* 0 "Block GMRES" (default), 1 "Block CG", 2 "Recycling GMRES" = GCRO-DR(num_blocks,
                         num_recycled) (solver_lin_belos.h:173-181)           */
@@ -362,6 +391,7 @@ typedef struct {
   int verbose;       /* rank-0 status lines like Belos "Verbosity"          */
   int num_recycled;  /* "Num Recycled Blocks" (50, solver_lin_belos.h:240); solver_type 2 needs
                         0 < num_recycled < num_blocks, as Belos::GCRODRSolMgr does */
+  int basis_bits;    /* storage of the Krylov basis: 64 (default; 0 means the same) or 32, see above */
 } isph_solver_params;
 void isph_solver_params_default(isph_solver_params *p);
 
@@ -376,6 +406,8 @@ typedef struct {
   int reorth;               /* Gram-Schmidt steps whose second pass was applied (DGKS: when the norm dropped below
                                1/sqrt(2) of its value before the first pass; ICGS: every step), summed over the
                                right-hand sides.  IMGS always sweeps twice and is not counted: 0, as for CG */
+  int residual_restarts;    /* basis_bits = 32: restarts (counted in `restarts` too) taken because the true residual was
+                               still above tol when the recurrence residual had reached it; 0 with basis_bits 64 */
 } isph_solve_info;
 
 /* Replaces SolverLin_Belos::solveProblem (ref: solver_lin_belos.h:130-222):
