@@ -68,22 +68,15 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     Vb.release(); Cb.release(); Ub.release(); Cn.release(); Un.release(); tb.release(); rb.release(); wb.release();
     zb.release(); cbuf.release();
   };
-  auto norm_of = [&](const double *v, double *out) -> int {
-    ISPH_CHECK(dot_dev(ctx, n, v, v, nullptr, nullptr, SC_MISC + 4));
-    ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
-    *out = std::sqrt(ctx->hscal[SC_MISC + 4]);
-    return ISPH_SUCCESS;
-  };
+  GmresCycle cyc;  // the implicit residual only: the harmonic Ritz problem needs H unrotated, kept below
 
   hipLaunchKernelGGL(k_fill, dim3(sg), dim3(kBlock), 0, st, n, t, 0.0);
   ISPH_CHECK(op.apply(x, r));
-  hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, b, r);
-  double beta = 0.0;
-  ISPH_CHECK(norm_of(r, &beta));
-  const double scale = beta == 0.0 ? 1.0 : beta;
+  ISPH_CHECK(residual_norm(ctx, n, b, r, &cyc.beta));
+  cyc.scale = cyc.beta == 0.0 ? 1.0 : cyc.beta;
   info->iters = 0; info->restarts = 0; info->converged = 0;
-  info->rel_res_implicit = beta / scale;
-  if (beta / scale <= prm->tol) info->converged = 1;
+  info->rel_res_implicit = cyc.beta / cyc.scale;
+  if (cyc.beta / cyc.scale <= prm->tol) info->converged = 1;
   int kk = 0;  // current size of the recycle space
   int rc = ISPH_SUCCESS;
 
@@ -91,15 +84,15 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     const int steps = kk == 0 ? m : m - kk;
     // ---- Arnoldi with (I - C C^T) Op
     std::vector<double> H((size_t)(steps + 1) * steps, 0.0), B((size_t)(kk > 0 ? kk : 1) * steps, 0.0);  // row-major
-    std::vector<double> cs((size_t)steps), sn((size_t)steps), g((size_t)steps + 1, 0.0);
-    rc = norm_of(r, &beta);
+    rc = norm_host(ctx, n, r, &cyc.beta);
     if (rc != ISPH_SUCCESS) break;
-    if (beta == 0.0) { info->converged = 1; break; }
-    hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)r, V, 1.0 / beta, (const double *)nullptr, 0);
-    g[0] = beta;
-    int j = 0;
+    if (cyc.beta == 0.0) { info->converged = 1; break; }
+    hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)r, V, 1.0 / cyc.beta, (const double *)nullptr, 0);
+    cyc.reset(steps);
+    cyc.start();
     bool conv = false;
-    while (j < steps && rc == ISPH_SUCCESS) {
+    while (cyc.j < steps && rc == ISPH_SUCCESS) {
+      const int j = cyc.j;
       rc = op.prec(V + (long long)j * ld, z);
       if (rc == ISPH_SUCCESS) rc = op.apply(z, w);
       if (rc != ISPH_SUCCESS) break;
@@ -108,45 +101,35 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
         if (rc != ISPH_SUCCESS) break;
         for (int i = 0; i < kk; ++i) B[(size_t)i * steps + j] = ctx->hscal[SC_DOT + i];
       }
-      std::vector<double> hcol((size_t)j + 2, 0.0);
+      double *hcol = cyc.column();  // zero since reset()
       double ww = 0.0;
       for (int pass = 0; pass < 2 && rc == ISPH_SUCCESS; ++pass) {  // two classical Gram-Schmidt passes
         rc = cgs_pass(ctx, n, j + 1, V, ld, w);
-        for (int i = 0; i <= j; ++i) hcol[(size_t)i] += ctx->hscal[SC_DOT + i];
+        for (int i = 0; i <= j; ++i) hcol[i] += ctx->hscal[SC_DOT + i];
         ww = ctx->hscal[SC_DOT + j + 2];
       }
       if (rc != ISPH_SUCCESS) break;
       const double hn = std::sqrt(ww > 0.0 ? ww : 0.0);
-      hcol[(size_t)j + 1] = hn;
-      for (int i = 0; i <= j + 1; ++i) H[(size_t)i * steps + j] = hcol[(size_t)i];
+      hcol[j + 1] = hn;
+      for (int i = 0; i <= j + 1; ++i) H[(size_t)i * steps + j] = hcol[i];
       if (hn != 0.0)
         hipLaunchKernelGGL(k_scale_copy<double>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, V + (long long)(j + 1) * ld, 1.0 / hn,
                            (const double *)nullptr, 0);
-      // implicit residual by Givens rotations on a copy of the column
-      for (int i = 0; i < j; ++i) {
-        const double a = cs[(size_t)i] * hcol[(size_t)i] + sn[(size_t)i] * hcol[(size_t)i + 1];
-        hcol[(size_t)i + 1] = -sn[(size_t)i] * hcol[(size_t)i] + cs[(size_t)i] * hcol[(size_t)i + 1];
-        hcol[(size_t)i] = a;
-      }
-      const double a = hcol[(size_t)j], bb = hcol[(size_t)j + 1], rr = std::hypot(a, bb);
-      cs[(size_t)j] = rr == 0.0 ? 1.0 : a / rr;
-      sn[(size_t)j] = rr == 0.0 ? 0.0 : bb / rr;
-      g[(size_t)j + 1] = -sn[(size_t)j] * g[(size_t)j];
-      g[(size_t)j] = cs[(size_t)j] * g[(size_t)j];
-      ++j;
+      // implicit residual by Givens rotations on that copy of the column
       ++info->iters;
-      info->rel_res_implicit = std::fabs(g[(size_t)j]) / scale;
+      info->rel_res_implicit = cyc.push() / cyc.scale;
       if (info->rel_res_implicit <= prm->tol) { conv = true; break; }
       if (info->iters >= prm->max_iters) break;
     }
     if (rc != ISPH_SUCCESS) break;
+    const int j = cyc.j;
     // ---- projected least-squares problem and the updates of t and r
     const int rows = kk + j + 1, cols = kk + j;
     std::vector<double> G((size_t)rows * cols, 0.0), dsc((size_t)(kk > 0 ? kk : 1), 1.0), rhs((size_t)rows, 0.0), y;
     if (kk > 0) {
       for (int i = 0; i < kk && rc == ISPH_SUCCESS; ++i) {
         double un = 0.0;
-        rc = norm_of(U + (long long)i * ld, &un);
+        rc = norm_host(ctx, n, U + (long long)i * ld, &un);
         dsc[(size_t)i] = un > 0.0 ? 1.0 / un : 1.0;
         G[(size_t)i * cols + i] = dsc[(size_t)i];
       }
@@ -158,7 +141,7 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     }
     for (int i = 0; i <= j; ++i)
       for (int c = 0; c < j; ++c) G[(size_t)(kk + i) * cols + kk + c] = H[(size_t)i * steps + c];
-    rhs[(size_t)kk] = beta;
+    rhs[(size_t)kk] = cyc.beta;
     dense::least_squares(rows, cols, G, rhs, y);
     std::vector<double> coef((size_t)std::max(rows, 1));
     for (int i = 0; i < kk; ++i) coef[(size_t)i] = dsc[(size_t)i] * y[(size_t)i];  // Ut = U D

@@ -3,14 +3,15 @@
 // Restates SolverLin_Belos::solveProblem (ref: solver_lin_belos.h:130-222):
 // Belos BlockGmresSolMgr (flexible, block size 1, DGKS) and BlockCGSolMgr,
 // right preconditioning, PoissonProjection for the singular pressure system
-// (ref: solver_lin.h:131-140).  Hessenberg / Givens live on the host (m<=50);
-// every vector operation is a kernel from krylov.hpp / sell.hpp.
+// (ref: solver_lin.h:131-140).  Hessenberg / Givens and the restart rule live on the host (m<=62,
+// gmres_host.hpp); every vector operation is a kernel from krylov.hpp / sell.hpp.
 #pragma once
 #include <cmath>
 #include <type_traits>
 
 #include "comm.hpp"
 #include "core.hpp"
+#include "gmres_host.hpp"
 #include "krylov.hpp"
 
 namespace isph {
@@ -258,6 +259,28 @@ inline int dot_dev(isph_ctx *ctx, int n, const double *a, const double *b, const
   return allreduce_inplace(ctx, ctx->dscal.p + slot, 2);
 }
 
+// *out = |v| (all-reduced), on the host
+inline int norm_host(isph_ctx *ctx, int n, const double *v, double *out) {
+  ISPH_CHECK(dot_dev(ctx, n, v, v, nullptr, nullptr, SC_MISC + 4));
+  ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
+  *out = std::sqrt(ctx->hscal[SC_MISC + 4]);
+  return ISPH_SUCCESS;
+}
+
+// w holds Op x: w = b - w, *out = |w|
+inline int residual_norm(isph_ctx *ctx, int n, const double *b, double *w, double *out) {
+  hipLaunchKernelGGL(k_residual, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, n, b, w);
+  return norm_host(ctx, n, w, out);
+}
+
+// y of the cycle so far to the SC_Y slots of mailbox mb.  The copy reads hscal when the stream gets there: the caller
+// synchronizes the stream before hscal is rewritten.
+inline int upload_y(isph_ctx *ctx, GmresCycle &c, int mb = 0) {
+  std::copy_n(c.solve(), c.j, ctx->hscal + mb + SC_Y);
+  ISPH_CHECK_HIP(hipMemcpyAsync(ctx->dscal.p + mb + SC_Y, ctx->hscal + mb + SC_Y, sizeof(double) * (size_t)c.j, hipMemcpyHostToDevice, ctx->stream));
+  return ISPH_SUCCESS;
+}
+
 // project v -= (v.n) n
 inline int project_dev(isph_ctx *ctx, int n, const double *nvec, double *v) {
   ISPH_CHECK(dot_dev(ctx, n, v, nvec, nullptr, nullptr, SC_MISC + 2));
@@ -433,29 +456,25 @@ inline int gmres_t(const LinOp &op, const double *b, double *x, const isph_solve
   if constexpr (!f32)
     if (deflate)
     ISPH_CHECK_HIP(hipMemcpyAsync(Vall, op.nvec, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-  std::vector<double> H((size_t)(m + 1) * (size_t)m, 0.0), cs((size_t)m), sn((size_t)m), g((size_t)m + 1), y((size_t)m);
+  GmresCycle c;
+  c.reset(m);
   const int sg = stream_grid(n);
   hipStream_t st = ctx->stream;
 
   // r0 = b - Op(x)
   ISPH_CHECK(op.apply(x, w));
-  hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, b, w);
-  ISPH_CHECK(dot_dev(ctx, n, w, w, nullptr, nullptr, SC_MISC + 4));
-  ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
-  double beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
-  const double scale = beta == 0.0 ? 1.0 : beta;  // Belos: zero scale -> 1
+  ISPH_CHECK(residual_norm(ctx, n, b, w, &c.beta));
+  c.scale = c.beta == 0.0 ? 1.0 : c.beta;  // Belos: zero scale -> 1
   info->iters = 0;
   info->restarts = 0;
   info->residual_restarts = 0;
   info->converged = 0;
-  info->rel_res_implicit = beta / scale;
-  if (beta / scale <= prm->tol) info->converged = 1;
+  info->rel_res_implicit = c.beta / c.scale;
+  if (c.beta / c.scale <= prm->tol) info->converged = 1;
 
   while (!info->converged && info->iters < prm->max_iters) {
-    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, column(0), 1.0 / beta, (const double *)nullptr, 0);
-    std::fill(g.begin(), g.end(), 0.0);
-    g[0] = beta;
-    int j = 0;
+    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)w, column(0), 1.0 / c.beta, (const double *)nullptr, 0);
+    c.start();
     // queue z_j = M^-1 v_j, w = Op z_j
     auto enqueue_op = [&](int col) -> int {
       const double *zj, *vj;
@@ -472,10 +491,11 @@ inline int gmres_t(const LinOp &op, const double *b, double *x, const isph_solve
       return deflate ? spmv_dev(ctx, op.A, zj, w, nullptr) : op.apply(zj, w);
     };
     bool op_queued = false;  // column j's operator application is already in the stream
-    while (j < m) {
+    while (c.j < m) {
+      const int j = c.j;
       if (!op_queued) ISPH_CHECK(enqueue_op(j));
       op_queued = false;
-      double *h = &H[(size_t)j * (size_t)(m + 1)];
+      double *h = c.column();
       double wn = 0.0;
       if (prm->ortho == 2) {
         if constexpr (!f32) {
@@ -505,36 +525,16 @@ inline int gmres_t(const LinOp &op, const double *b, double *x, const isph_solve
         }
       }
       h[j + 1] = wn;
-      for (int k = 0; k < j; ++k) {
-        const double a = cs[k] * h[k] + sn[k] * h[k + 1];
-        h[k + 1] = -sn[k] * h[k] + cs[k] * h[k + 1];
-        h[k] = a;
-      }
-      {
-        const double a = h[j], bb = h[j + 1], rr = std::hypot(a, bb);
-        cs[j] = rr == 0.0 ? 1.0 : a / rr;
-        sn[j] = rr == 0.0 ? 0.0 : bb / rr;
-        h[j] = rr;
-        h[j + 1] = 0.0;
-        g[j + 1] = -sn[j] * g[j];
-        g[j] = cs[j] * g[j];
-      }
-      ++j;
       ++info->iters;
-      info->rel_res_implicit = std::fabs(g[j]) / scale;
+      info->rel_res_implicit = c.push() / c.scale;
       if (prm->verbose && ctx->rank == 0 && info->iters % 10 == 0)
         printf(">> isph::gmres iter %d  rel res %.3e\n", info->iters, info->rel_res_implicit);
       if (info->rel_res_implicit <= prm->tol) { info->converged = 1; break; }
       if (info->iters >= prm->max_iters) break;
     }
-    for (int k = j - 1; k >= 0; --k) {
-      double s = g[k];
-      for (int l = k + 1; l < j; ++l) s -= H[(size_t)l * (size_t)(m + 1) + k] * y[l];
-      y[k] = s / H[(size_t)k * (size_t)(m + 1) + k];
-    }
     // x += Z y  (flexible)  or  x += M^-1 (V y)
-    for (int k = 0; k < j; ++k) ctx->hscal[SC_Y + k] = y[k];
-    ISPH_CHECK_HIP(hipMemcpyAsync(ctx->dscal.p + SC_Y, ctx->hscal + SC_Y, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, st));
+    const int j = c.j;
+    ISPH_CHECK(upload_y(ctx, c));
     if (prm->flexible) {
       hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, st, n, j, Z, ld, ctx->dscal.p + SC_Y, x);
     } else {
@@ -545,25 +545,11 @@ inline int gmres_t(const LinOp &op, const double *b, double *x, const isph_solve
     }
     // the H2D source (hscal) must not be rewritten before the copy has run
     ISPH_CHECK_HIP(hipStreamSynchronize(st));
-    const bool confirm = f32 && info->converged;  // float basis: the recurrence says converged, the true residual decides
-    if (!confirm) {
-      if (info->converged || info->iters >= prm->max_iters) break;
-      if (info->restarts >= prm->max_restarts) break;
-      ++info->restarts;
-    }
+    // float basis: the recurrence says converged, the true residual decides (gmres_host.hpp)
+    if (!gmres_after_update(f32, *info, prm->max_iters, prm->max_restarts)) break;
     ISPH_CHECK(op.apply(x, w));
-    hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, b, w);
-    ISPH_CHECK(dot_dev(ctx, n, w, w, nullptr, nullptr, SC_MISC + 4));
-    ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
-    beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
-    if (confirm) {
-      if (beta / scale <= prm->tol) break;
-      info->converged = 0;  // restart from this residual
-      if (info->iters >= prm->max_iters || info->restarts >= prm->max_restarts) break;
-      ++info->restarts;
-      ++info->residual_restarts;
-    }
-    if (beta == 0.0) { info->converged = 1; break; }
+    ISPH_CHECK(residual_norm(ctx, n, b, w, &c.beta));
+    if (!gmres_after_residual(f32, *info, prm->max_iters, prm->max_restarts, c.beta, c.scale, prm->tol)) break;
   }
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
@@ -615,9 +601,7 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
   struct Sys {
     BT *V;
     double *Z, *w, *vcur = nullptr;
-    std::vector<double> H, cs, sn, g, y;
-    double beta = 0.0, scale = 1.0;
-    int j = 0;
+    GmresCycle c;
     bool in_cycle = false, done = false;
   };
   std::vector<Sys> sys((size_t)K);
@@ -631,8 +615,7 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
     else s.V = ctx->V.p + (size_t)k * ld * (size_t)(m + 2);
     s.Z = ctx->Z.p + (size_t)k * ld * (size_t)m;
     s.w = ctx->wv.p + (size_t)k * ld;
-    s.H.assign((size_t)(m + 1) * (size_t)m, 0.0);
-    s.cs.assign((size_t)m, 0.0); s.sn.assign((size_t)m, 0.0); s.g.assign((size_t)m + 1, 0.0); s.y.assign((size_t)m, 0.0);
+    s.c.reset(m);
     infos[k].iters = 0; infos[k].restarts = 0; infos[k].residual_restarts = 0; infos[k].converged = 0;
     xin[k] = xs[k]; yout[k] = s.w;
   }
@@ -640,13 +623,10 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
   ISPH_CHECK(spmm_dev(ctx, op.A, K, xin, yout));
   for (int k = 0; k < K; ++k) {
     Sys &s = sys[(size_t)k];
-    hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, bs[k], s.w);
-    ISPH_CHECK(dot_dev(ctx, n, s.w, s.w, nullptr, nullptr, SC_MISC + 4));
-    ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
-    s.beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
-    s.scale = s.beta == 0.0 ? 1.0 : s.beta;
-    infos[k].rel_res_implicit = s.beta / s.scale;
-    if (s.beta / s.scale <= prm->tol) { infos[k].converged = 1; s.done = true; }
+    ISPH_CHECK(residual_norm(ctx, n, bs[k], s.w, &s.c.beta));
+    s.c.scale = s.c.beta == 0.0 ? 1.0 : s.c.beta;
+    infos[k].rel_res_implicit = s.c.beta / s.c.scale;
+    if (s.c.beta / s.c.scale <= prm->tol) { infos[k].converged = 1; s.done = true; }
   }
   auto column = [&](Sys &s, int col) -> typename BasisVec<BT>::out {
     if constexpr (f32) return BasisOut32{s.V + (long long)col * ld, s.vcur};
@@ -654,46 +634,27 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
   };
   auto start_cycle = [&](int k) {
     Sys &s = sys[(size_t)k];
-    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)s.w, column(s, 0), 1.0 / s.beta, (const double *)nullptr, 0);
-    std::fill(s.g.begin(), s.g.end(), 0.0);
-    s.g[0] = s.beta;
-    s.j = 0;
+    hipLaunchKernelGGL(k_scale_copy<BT>, dim3(sg), dim3(kBlock), 0, st, n, (const double *)s.w, column(s, 0), 1.0 / s.c.beta, (const double *)nullptr, 0);
+    s.c.start();
     s.in_cycle = true;
   };
   // end of a cycle of system k: x += Z y, then either done or the residual of the restart
   auto end_cycle = [&](int k) -> int {
     Sys &s = sys[(size_t)k];
     isph_solve_info &inf = infos[k];
-    const int j = s.j, mb = k * SC_COUNT;
-    for (int q = j - 1; q >= 0; --q) {
-      double acc = s.g[(size_t)q];
-      for (int l = q + 1; l < j; ++l) acc -= s.H[(size_t)l * (size_t)(m + 1) + q] * s.y[(size_t)l];
-      s.y[(size_t)q] = acc / s.H[(size_t)q * (size_t)(m + 1) + q];
-    }
-    for (int q = 0; q < j; ++q) ctx->hscal[mb + SC_Y + q] = s.y[(size_t)q];
-    ISPH_CHECK_HIP(hipMemcpyAsync(ctx->dscal.p + mb + SC_Y, ctx->hscal + mb + SC_Y, sizeof(double) * (size_t)j, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, st, n, j, s.Z, ld, ctx->dscal.p + mb + SC_Y, xs[k]);
+    const int mb = k * SC_COUNT;
+    ISPH_CHECK(upload_y(ctx, s.c, mb));
+    hipLaunchKernelGGL(k_multi_axpy<double>, dim3(sg), dim3(kBlock), 0, st, n, s.c.j, s.Z, ld, ctx->dscal.p + mb + SC_Y, xs[k]);
     ISPH_CHECK_HIP(hipStreamSynchronize(st));  // the H2D source must not be rewritten before the copy has run
     s.in_cycle = false;
-    const bool confirm = f32 && inf.converged;  // as in gmres_t: the true residual decides
-    if (!confirm) {
-      if (inf.converged || inf.iters >= prm->max_iters || inf.restarts >= prm->max_restarts) { s.done = true; return ISPH_SUCCESS; }
-      ++inf.restarts;
+    bool again = gmres_after_update(f32, inf, prm->max_iters, prm->max_restarts);  // the restart rule of gmres_t
+    if (again) {
+      ISPH_CHECK(op.apply(xs[k], s.w));
+      ISPH_CHECK(residual_norm(ctx, n, bs[k], s.w, &s.c.beta));
+      again = gmres_after_residual(f32, inf, prm->max_iters, prm->max_restarts, s.c.beta, s.c.scale, prm->tol);
     }
-    ISPH_CHECK(op.apply(xs[k], s.w));
-    hipLaunchKernelGGL(k_residual, dim3(sg), dim3(kBlock), 0, st, n, bs[k], s.w);
-    ISPH_CHECK(dot_dev(ctx, n, s.w, s.w, nullptr, nullptr, SC_MISC + 4));
-    ISPH_CHECK(fetch_scalars(ctx, SC_MISC + 4, 1));
-    s.beta = std::sqrt(ctx->hscal[SC_MISC + 4]);
-    if (confirm) {
-      if (s.beta / s.scale <= prm->tol) { s.done = true; return ISPH_SUCCESS; }
-      inf.converged = 0;
-      if (inf.iters >= prm->max_iters || inf.restarts >= prm->max_restarts) { s.done = true; return ISPH_SUCCESS; }
-      ++inf.restarts;
-      ++inf.residual_restarts;
-    }
-    if (s.beta == 0.0) { inf.converged = 1; s.done = true; return ISPH_SUCCESS; }
-    start_cycle(k);
+    if (again) start_cycle(k);
+    else s.done = true;
     return ISPH_SUCCESS;
   };
   for (int k = 0; k < K; ++k)
@@ -714,8 +675,8 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
       for (int a = 0; a < na; ++a) {
         Sys &s = sys[(size_t)act[a]];
         if constexpr (f32) vin[a] = s.vcur;
-        else vin[a] = s.V + (long long)s.j * ld;
-        zout[a] = s.Z + (long long)s.j * ld;
+        else vin[a] = s.V + (long long)s.c.j * ld;
+        zout[a] = s.Z + (long long)s.c.j * ld;
         xin[a] = zout[a];
         yout[a] = s.w;
       }
@@ -728,7 +689,7 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
     for (int a = 0; a < na; ++a) {
       const int k = act[a], mb = k * SC_COUNT;
       Sys &s = sys[(size_t)k];
-      ISPH_CHECK(ortho_enqueue<BT>(ctx, n, s.j + 1, s.V, ld, s.w, prm->ortho, column(s, s.j + 1), false, mb));
+      ISPH_CHECK(ortho_enqueue<BT>(ctx, n, s.c.j + 1, s.V, ld, s.w, prm->ortho, column(s, s.c.j + 1), false, mb));
       ISPH_CHECK_HIP(hipMemcpyAsync(ctx->hscal + mb, ctx->dscal.p + mb, sizeof(double) * SC_COUNT, hipMemcpyDeviceToHost, st));
       ISPH_CHECK_HIP(hipEventRecord(ctx->ev_ls[(size_t)k], st));
     }
@@ -737,33 +698,14 @@ inline int gmres_lockstep_t(const LinOp &op, int K, const double *const *bs, dou
       Sys &s = sys[(size_t)k];
       isph_solve_info &inf = infos[k];
       ISPH_CHECK_HIP(hipEventSynchronize(ctx->ev_ls[(size_t)k]));
-      const int j = s.j;
-      double *h = &s.H[(size_t)j * (size_t)(m + 1)];
-      double wn = 0.0;
-      for (int q = 0; q <= j; ++q) h[q] = 0.0;
-      ortho_collect(ctx, j + 1, h, &wn, mb);
-      h[j + 1] = wn;
-      for (int q = 0; q < j; ++q) {
-        const double t = s.cs[(size_t)q] * h[q] + s.sn[(size_t)q] * h[q + 1];
-        h[q + 1] = -s.sn[(size_t)q] * h[q] + s.cs[(size_t)q] * h[q + 1];
-        h[q] = t;
-      }
-      {
-        const double t = h[j], bb = h[j + 1], rr = std::hypot(t, bb);
-        s.cs[(size_t)j] = rr == 0.0 ? 1.0 : t / rr;
-        s.sn[(size_t)j] = rr == 0.0 ? 0.0 : bb / rr;
-        h[j] = rr;
-        h[j + 1] = 0.0;
-        s.g[(size_t)j + 1] = -s.sn[(size_t)j] * s.g[(size_t)j];
-        s.g[(size_t)j] = s.cs[(size_t)j] * s.g[(size_t)j];
-      }
-      ++s.j;
+      double *h = s.c.column();
+      ortho_collect(ctx, s.c.j + 1, h, &h[s.c.j + 1], mb);
       ++inf.iters;
-      inf.rel_res_implicit = std::fabs(s.g[(size_t)s.j]) / s.scale;
+      inf.rel_res_implicit = s.c.push() / s.c.scale;
       if (prm->verbose && ctx->rank == 0 && inf.iters % 10 == 0)
         printf(">> isph::gmres[%d] iter %d  rel res %.3e\n", k, inf.iters, inf.rel_res_implicit);
       if (inf.rel_res_implicit <= prm->tol) inf.converged = 1;
-      if (inf.converged || inf.iters >= prm->max_iters || s.j >= m) ISPH_CHECK(end_cycle(k));
+      if (inf.converged || inf.iters >= prm->max_iters || s.c.j >= m) ISPH_CHECK(end_cycle(k));
     }
   }
   ISPH_CHECK_HIP(hipGetLastError());
