@@ -77,6 +77,7 @@ struct isph_ctx {
   isph::DevBuf<double> xghost;
   isph::HostStager *stager = nullptr;  // created by the first host-side isph_mat_create_csr
   bool neigh_hold = false;             // isph_ctx_hold_neighbours
+  bool pattern_hold = false;           // isph_ctx_hold_pattern: matrices created from a CSR keep an entry map (pattern.hpp)
   isph_neigh_layout neigh_cache[2];    // [0] list order, [1] ordered by matrix column
   isph_table_cache tables;             // assemble.hpp stage_tables
   // row numbering of the matrices the assembly entry points build (isph_ctx_set_ordering): 1 = the library's bricks
@@ -143,6 +144,10 @@ struct isph_mat {
   // a Poisson-Boltzmann Jacobian (isph_assemble_poisson_boltzmann): row classes, Dirichlet values, diagonal positions in
   // S.val, the Laplacian's diagonal, the current shift J_ii - L_ii and the Newton workspaces, all in the matrix' rows
   isph_pb_rows *pb = nullptr;
+  // isph_ctx_hold_pattern: position in S.val of every entry of the CSR the matrix was created from, in the caller's
+  // entry order (pattern.hpp); empty when the mode was off or a row held a column twice
+  isph::DevBuf<unsigned> emap;
+  long long n_updates = 0;  // isph_mat_update_values calls taken
 };
 
 struct isph_ilu;  // ilu.hpp

@@ -70,7 +70,8 @@ struct isph_ilu {
   long long stream_entries = 0;  // exact mode: 64 x the chunks the schedule counted
   bool compact = false;          // exact mode, ILU(0) / Gauss-Seidel: the factor regions hold the in-block entries only
   const long long *stream_off() const { return exact ? sboff.p : boff.p; }
-  isph::DevBuf<unsigned char> flev;  // level of fill of every factor entry (ILU(k) symbolic phase only)
+  isph::DevBuf<unsigned char> flev;  // level of fill of every factor entry (ILU(k) symbolic phase; kept for ilu_refactor
+                                     // when the factor was built while isph_ctx_hold_pattern was on)
   long long stream_chunks = 0;
   long long total = 0;      // entries reserved for the factor (ILU(0): A's sliced-ELL size; ILU(k): sum of the blocks)
   int fill = 0;             // level of fill
@@ -97,6 +98,10 @@ __device__ __forceinline__ void ilu_block_rows(const int *__restrict__ bptr, int
 constexpr int kExtChunk = 8;  // entries of a row staged per round (dynamic LDS: waves x 64 rows x 8 x 12 B)
 constexpr int kExtAhead = 8;  // slots of a row whose loads are issued together
 
+// REFILL (ilu_refactor, ILU(0)): the same walk on a factor that is already laid out -- frp, flen, fdiag and fcol are READ
+// and compared (a row with another in-block count, diagonal slot or column raises bit 128 and reports itself in badrow),
+// only fval is written, through the same coalesced flushes.
+template <bool REFILL = false>
 __global__ __launch_bounds__(1024) void k_ilu_extract(int n, int B, const int *__restrict__ rowlen,
                                                       const long long *__restrict__ slice_off,
                                                       const int *__restrict__ scol, const double *__restrict__ sval,
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(1024) void k_ilu_extract(int n, int B, const int *_
                                                       double *__restrict__ fval, int *__restrict__ flen,
                                                       int *__restrict__ fdiag, int *__restrict__ err, int b0,
                                                       const long long *__restrict__ base_off,
-                                                      const int *__restrict__ bptr) {
+                                                      const int *__restrict__ bptr, int *__restrict__ badrow = nullptr) {
   __shared__ int wsum[16];
   extern __shared__ double ext_lds[];
   const int nwv = blockDim.x >> 6;
@@ -156,13 +161,19 @@ __global__ __launch_bounds__(1024) void k_ilu_extract(int n, int B, const int *_
   __syncthreads();
   int woff = 0;
   for (int w = 0; w < (t >> 6); ++w) woff += wsum[w];
-  const long long start = base + woff + s - cnt;
-  if (active) {
+  long long start = base + woff + s - cnt;
+  if (REFILL) {
+    if (active) {
+      start = frp[i];
+      if (flen[i] != cnt || fdiag[i] != dg) { atomicOr(err, 128); atomicMin(badrow, i); cnt = 0; }  // (nothing of it is written)
+    }
+  } else if (active) {
     frp[i] = start;
     flen[i] = cnt;
     fdiag[i] = dg;
     if (dg < 0) atomicOr(err, 1);  // structurally missing diagonal
   }
+  const bool skip_row = REFILL && active && cnt == 0;
   // copy: the wave walks its 64 rows of A column slot by column slot (every load is one coalesced wave access of the
   // sliced-ELL image); a lane keeps the in-block entries of its row in an LDS buffer of kExtChunk entries, and as soon
   // as one lane's buffer is full the wave writes all buffers out together -- kExtChunk consecutive lanes write one
@@ -190,7 +201,7 @@ __global__ __launch_bounds__(1024) void k_ilu_extract(int n, int B, const int *_
     double v = 0.0;
 #pragma unroll
     for (int u = 0; u < kExtAhead; ++u) if (u == u0) { c = cq[u]; v = vq[u]; }
-    if (k < len) {
+    if (k < len && !skip_row) {
       if (c >= blo && c < bhi) {
         stage_col[wv][ln][got] = c;
         stage_val[wv][ln][got] = v;
@@ -206,7 +217,11 @@ __global__ __launch_bounds__(1024) void k_ilu_extract(int n, int B, const int *_
       const int e = ln + 64 * it, row = e / kExtChunk, slot = e % kExtChunk;
       if (slot < scnt[row]) {
         const long long q = sstart[row] + slot;
-        fcol[q] = stage_col[wv][row][slot];
+        if (REFILL) {
+          if (fcol[q] != stage_col[wv][row][slot]) { atomicOr(err, 128); atomicMin(badrow, blo + wv * 64 + row); }
+        } else {
+          fcol[q] = stage_col[wv][row][slot];
+        }
         fval[q] = stage_val[wv][row][slot];
       }
     }
@@ -1328,7 +1343,9 @@ inline int ilu_symbolic(isph_ctx *ctx, isph_ilu *F, int K) {
     F->wmax = wmax;
   }
   nlen.release(); inoff.release(); blktot.release(); meta.release();
-  F->flev.release();  // only the symbolic sweeps need the levels
+  // only the symbolic sweeps need the levels -- unless the pattern is held (isph_ctx_hold_pattern): ilu_refactor tells a
+  // level-0 slot, which takes a value of A, from a fill slot, which starts at 0, by them (1 B per factor entry)
+  if (!ctx->pattern_hold || rc != ISPH_SUCCESS) F->flev.release();
   return rc;
 }
 
@@ -1396,7 +1413,7 @@ inline int ilu_begin(isph_ctx *ctx, const Sell &S, int block_size, bool sgs, int
   if (rc == ISPH_SUCCESS && S.nrow > 0) {
     const size_t lds_e = (size_t)(block_size / 64) * 64 * ((kExtChunk + 1) * 8 + (kExtChunk + 1) * 4);
     const size_t lds_s = sizeof(int) * (14 * (size_t)block_size + 10) + sizeof(long long) * (size_t)block_size;
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_extract), hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_extract<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_e) != hipSuccess ||
         hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_schedule<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds_s) != hipSuccess ||
@@ -1422,10 +1439,10 @@ inline int ilu_begin_fill0(isph_ctx *ctx, isph_ilu *F, const Sell &S, bool size_
 inline void ilu_launch_extract(isph_ctx *ctx, isph_ilu *F, const Sell &S, int b0, int nb, hipStream_t st = nullptr) {
   const size_t lds_e = (size_t)(F->B / 64) * 64 * ((kExtChunk + 1) * 8 + (kExtChunk + 1) * 4);
   ProfScope prof(ctx, PROF_ILU_EXTRACT, st);
-  hipLaunchKernelGGL(k_ilu_extract, dim3(nb), dim3(F->B), lds_e, st ? st : ctx->stream, S.nrow, F->B, (const int *)S.rowlen.p,
+  hipLaunchKernelGGL(k_ilu_extract<false>, dim3(nb), dim3(F->B), lds_e, st ? st : ctx->stream, S.nrow, F->B, (const int *)S.rowlen.p,
                      (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, F->frp.p, F->fcol.p,
                      F->fval.p, F->flen.p, F->fdiag.p, F->err.p, b0, F->compact ? (const long long *)F->boff.p : (const long long *)nullptr,
-                     F->blocks());
+                     F->blocks(), (int *)nullptr);
 }
 
 inline void ilu_launch_schedule(isph_ctx *ctx, isph_ilu *F, const Sell &S, int b0, int nb, bool sgs, hipStream_t st = nullptr,
@@ -1611,6 +1628,119 @@ inline int ilu_create(isph_ctx *ctx, const isph_mat *A, int block_size, isph_ilu
   if (rc != ISPH_SUCCESS) { ilu_destroy(F); return rc; }
   *out = F;
   return ISPH_SUCCESS;
+}
+
+// ---- numeric refactorisation on a kept pattern (isph_prec_refactor) ----------------------------------------------------
+// Ifpack's contract: Initialize() is the symbolic phase, Compute() the numeric one, and Compute() may be called again on
+// new values.  Of the pipeline extract [-> symbolic] -> schedule -> factor only the last stage reads values; frp, fcol,
+// flen, fdiag, fdst, llev, sc, si, sperm, blkinfo and boff are functions of the pattern and the subdomains alone.
+// The in-block entries of A's rows go back into fval -- ILU(0): the row's in-block entries in order, by the REFILL
+// instantiation of k_ilu_extract (its walk and its coalesced flushes; one thread per row walking its row-major factor row
+// was slower than the whole create call at 100^3, 5.37 against 5.25 ms); ILU(k): k_ilu_refill, a merge of the row's
+// ascending in-block columns into the ascending factor row with the fill slots set to 0, what the symbolic phase leaves
+// there -- and k_ilu_factor runs as it is: the same deterministic kernel on the same input bits, so fval, dinv and the
+// stream are bit for bit those of a fresh create.  Both check the pattern while they walk: a row whose in-block columns
+// are not exactly the level-0 columns of its factor row raises bit 128 and reports itself.
+// k_ilu_refill: one thread per row, one workgroup (B threads) per block like the extraction; flev == NULL treats every
+// slot as level 0.
+// Measured at 100^3 on the library's bricks (profiles/pattern_hold_100cubed.txt, 2026-10-19): refactor 3.81 against
+// create 5.14 ms (ILU(0)), 53.5 against 60.0 ms (ILU(1)).
+__global__ __launch_bounds__(1024) void k_ilu_refill(int n, int B, const int *__restrict__ rowlen,
+                                                     const long long *__restrict__ slice_off,
+                                                     const int *__restrict__ scol, const double *__restrict__ sval,
+                                                     const long long *__restrict__ frp, const int *__restrict__ fcol,
+                                                     double *__restrict__ fval, const int *__restrict__ flen,
+                                                     const unsigned char *__restrict__ flev, int *__restrict__ err,
+                                                     int *__restrict__ badrow, const int *__restrict__ bptr) {
+  int blo, bhi;
+  ilu_block_rows(bptr, blockIdx.x, B, n, blo, bhi);
+  const int i = blo + threadIdx.x;
+  if (i >= bhi) return;
+  const long long off = slice_off[i >> 6], rp = frp[i];
+  const int lane = i & 63, len = rowlen[i], fl = flen[i];
+  int s = 0;
+  bool bad = false;
+  for (int k = 0; k < len; ++k) {
+    const long long p = sell_pos(off, lane, k);
+    const int c = scol[p];
+    if (c < blo || c >= bhi) continue;
+    while (s < fl && fcol[rp + s] < c) {  // slots in front of c: fill (flev: levels kept, ILU(k)), which starts at 0
+      bad = bad || !flev || flev[rp + s] == 0;
+      fval[rp + s] = 0.0;
+      ++s;
+    }
+    if (s < fl && fcol[rp + s] == c && (!flev || flev[rp + s] == 0)) { fval[rp + s] = sval[p]; ++s; }
+    else bad = true;
+  }
+  for (; s < fl; ++s) {
+    bad = bad || !flev || flev[rp + s] == 0;
+    fval[rp + s] = 0.0;
+  }
+  if (bad) { atomicOr(err, 128); atomicMin(badrow, i); }
+}
+
+// value_bits 32: sv went back to the pool behind the rounding pass; the stream reserved again holds whatever the block held
+// before, and the padding lanes of the chunks a block uses -- which the schedule zeroed and the factorisation does not
+// write -- must be 0.0 again before k_ilu_round_stream reads them.  Same extent as that kernel.
+__global__ __launch_bounds__(kRoundThreads) void k_ilu_zero_stream(int nblocks, const long long *__restrict__ boff,
+                                                                   const int *__restrict__ blkinfo, double *__restrict__ sv,
+                                                                   int capf, int slack) {
+  const int b = blockIdx.x;
+  if (b >= nblocks) return;
+  const long long first = ilu_base_chunk(boff, b, capf, slack) * 64;
+  const long long cnt = ((long long)blkinfo[4 * b] + blkinfo[4 * b + 1]) * 64;
+  for (long long i = threadIdx.x; i < cnt; i += kRoundThreads) sv[first + i] = 0.0;
+}
+
+inline int ilu_refactor(isph_ctx *ctx, isph_ilu *F, const Sell &S) {
+  ISPH_REQUIRE(F->fcol.p && F->fval.p && F->fdst.p, "not a factored block ILU");
+  if (F->n != S.nrow) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "refactor: the matrix has %d rows, the preconditioner was built for %d", S.nrow, F->n);
+    return fail(msg, __FILE__, __LINE__);
+  }
+  ISPH_REQUIRE(F->fill == 0 || F->flev.p,
+               "refactor of an ILU(k > 0): the fill levels were not kept -- create the preconditioner while "
+               "isph_ctx_hold_pattern is on");
+  if (F->n == 0 || F->nblocks == 0) return ISPH_SUCCESS;
+  DevTmp<int> badrow;
+  ISPH_CHECK(badrow.reserve(1));
+  ISPH_CHECK_HIP(hipMemsetAsync(F->err.p, 0, sizeof(int), ctx->stream));
+  ISPH_CHECK_HIP(hipMemsetAsync(badrow.p, 0x7f, sizeof(int), ctx->stream));
+  if (F->fill == 0) {  // the extraction's own walk and coalesced flushes, comparing where it wrote the pattern
+    const size_t lds_e = (size_t)(F->B / 64) * 64 * ((kExtChunk + 1) * 8 + (kExtChunk + 1) * 4);
+    ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_extract<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)lds_e));
+    hipLaunchKernelGGL(k_ilu_extract<true>, dim3(F->nblocks), dim3(F->B), lds_e, ctx->stream, S.nrow, F->B, (const int *)S.rowlen.p,
+                       (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, F->frp.p, F->fcol.p,
+                       F->fval.p, F->flen.p, F->fdiag.p, F->err.p, 0, (const long long *)F->boff.p, F->blocks(), badrow.p);
+  } else {
+    hipLaunchKernelGGL(k_ilu_refill, dim3(F->nblocks), dim3(F->B), 0, ctx->stream, S.nrow, F->B, (const int *)S.rowlen.p,
+                       (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, (const long long *)F->frp.p,
+                       (const int *)F->fcol.p, F->fval.p, (const int *)F->flen.p, (const unsigned char *)F->flev.p, F->err.p, badrow.p,
+                       F->blocks());
+  }
+  int herr = 0, hrow = 0;
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(&herr, F->err.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipMemcpyAsync(&hrow, badrow.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+      hipStreamSynchronize(ctx->stream) != hipSuccess)
+    return fail("refactor: refill of the factor values failed", __FILE__, __LINE__);
+  if (herr & 128) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "refactor: the in-block columns of row %d (in the matrix' own numbering) are not the pattern "
+                               "the preconditioner was built from", hrow);
+    return fail(msg, __FILE__, __LINE__);
+  }
+  if (herr & 32) return fail("matrix row with duplicate or unsorted columns: ILU pattern undefined", __FILE__, __LINE__);
+  if (F->value_bits == 32) {
+    ISPH_CHECK(F->sv.reserve((size_t)F->stream_chunks * 64));
+    hipLaunchKernelGGL(k_ilu_zero_stream, dim3(F->nblocks), dim3(kRoundThreads), 0, ctx->stream, F->nblocks, F->stream_off(),
+                       (const int *)F->blkinfo.p, F->sv.p, F->capf, F->slack);
+  }
+  ISPH_CHECK(ilu_launch_factor(ctx, F, S, 0, F->nblocks, nullptr));
+  if (F->value_bits == 32) return ilu_round_stream(ctx, F);
+  return ilu_check_err(ctx, F, "ILU refactorisation failed");
 }
 
 // The same sweep for NV right-hand sides at once (the lockstep Helmholtz solve, solver.hpp gmres_lockstep): the stream

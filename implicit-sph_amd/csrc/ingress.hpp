@@ -32,6 +32,7 @@
 
 #include "core.hpp"
 #include "ilu.hpp"
+#include "pattern.hpp"
 
 namespace isph {
 
@@ -543,10 +544,143 @@ inline int csr_ingress_host(isph_ctx *ctx, int nrow, int ncol, const int *rowptr
     if (S.c16_state != 1) { S.col16.release(); S.wtab.release(); }
   }
   ISPH_CHECK_HIP(hipGetLastError());
+  if (ctx->pattern_hold && pattern_mappable(S)) {
+    // isph_ctx_hold_pattern: the entry map from the image, which is still resident, and the finished (sorted) rows.
+    // Gathered rows lie in the image in the library's order: where each starts in the caller's arrays travels along.
+    DevTmp<int> debase;
+    if (gat) {
+      std::vector<int> eb((size_t)nrow);
+      for (int r = 0; r < nrow; ++r) eb[(size_t)r] = gat->src_rowptr[gat->perm[r]];
+      ISPH_CHECK(debase.reserve((size_t)nrow));
+      ISPH_CHECK_HIP(hipMemcpyAsync(debase.p, eb.data(), sizeof(int) * (size_t)nrow, hipMemcpyHostToDevice, ctx->stream));
+      ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // eb leaves scope
+    }
+    ISPH_CHECK(pattern_build<int>(ctx, g.A, g.drp.p, nullptr, ck, gat ? gat->colren : nullptr, gat ? gat->nren : 0,
+                                  gat ? debase.p : nullptr));
+  }
   H->bytes_sent = sent + 4 * ((long long)nrow + 1);
   H->stats[4] = since(); H->stats[5] = wait_fill; H->stats[6] = (double)H->bytes_sent; H->stats[7] = (double)nthreads;
   *Aout = g.A;
   g.A = nullptr;
+  return ISPH_SUCCESS;
+}
+
+// isph_mat_update_values, host values: the nnz doubles travel through the ring of the ingress in its chunks (a small first
+// one, then whole slots), every chunk staged by all staging threads together and sent in ONE copy; the scatter of a chunk
+// through the matrix' entry map (pattern.hpp) is queued behind its copy, so only the last chunk's scatter is exposed.
+// 8 B per entry on the link instead of the 10 - 12 B of a full ingress, and nothing of the conversion, the row sort,
+// the column windows or the halo plan is redone.  The caller has checked A->emap and val.
+inline int mat_update_values_host(isph_ctx *ctx, isph_mat *A, const double *val) {
+  ISPH_REQUIRE(!is_device_pointer(val), "device pointer passed with on_device = 0");
+  Sell &S = A->S;
+  const long long nnz = S.nnz;
+  HostStager *H = nullptr;
+  ISPH_CHECK(stager_get(ctx, &H));
+  const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+  auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
+  double wait_fill = 0.0;
+  std::vector<long long> cstart(1, 0);
+  if (nnz > 0) cstart.push_back(std::min(nnz, (long long)HostStager::kChunk / 8));
+  while (cstart.back() < nnz) cstart.push_back(std::min(nnz, cstart.back() + (long long)HostStager::kChunk));
+  const long long nchunks = (long long)cstart.size() - 1;
+  const int P = (int)std::max<long long>(1, std::min<long long>(H->nthreads, nnz / 65536));
+  std::mutex mu;
+  std::condition_variable cv;
+  std::vector<char> filled((size_t)nchunks, 0), recorded((size_t)nchunks, 0);  // recorded: 1 event recorded, 2 nothing to wait for
+  std::vector<std::atomic<int>> parts_done((size_t)(nchunks > 0 ? nchunks : 1));
+  for (auto &a : parts_done) a.store(0);
+  std::atomic<long long> next(0);
+  std::atomic<int> hip_err(0);
+  auto worker = [&]() {
+    (void)hipSetDevice(ctx->device);
+    for (;;) {
+      const long long id = next.fetch_add(1);
+      const long long c = id / P;
+      const int part = (int)(id % P);
+      if (c >= nchunks) break;
+      const int slot = (int)(c % H->nslots);
+      if (c >= H->nslots) {  // the slot's previous chunk must have left it
+        char state = 0;
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          cv.wait(lk, [&] { return recorded[(size_t)(c - H->nslots)] != 0; });
+          state = recorded[(size_t)(c - H->nslots)];
+        }
+        if (state == 1 && hipEventSynchronize(H->ev[(size_t)slot]) != hipSuccess) hip_err.store(1);
+      }
+      const long long p0 = cstart[(size_t)c], p1 = cstart[(size_t)c + 1];
+      const long long cnt = p1 - p0;
+      char *base = H->pslot + (size_t)slot * 12 * HostStager::kChunk;
+      auto cut = [&](int k) { return k >= P ? p1 : std::min(p1, p0 + ((cnt * k / P) & ~31LL)); };
+      const long long q_lo = cut(part), q_hi = cut(part + 1);
+      if (q_hi > q_lo) stage_copy(base + 8 * (size_t)(q_lo - p0), val + q_lo, sizeof(double) * (size_t)(q_hi - q_lo));
+      if (parts_done[(size_t)c].fetch_add(1) + 1 < P) continue;
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        filled[(size_t)c] = 1;
+      }
+      cv.notify_all();
+    }
+  };
+  struct Pool {  // joins on every exit path; the workers always run to the end of the chunk list
+    std::vector<std::thread> th;
+    std::mutex &mu;
+    std::condition_variable &cv;
+    std::vector<char> &recorded;
+    hipStream_t copy_stream;
+    ~Pool() {
+      {
+        std::lock_guard<std::mutex> lk(mu);
+        for (char &r : recorded) if (r == 0) r = 2;  // nothing will be recorded any more: do not wait for it
+      }
+      cv.notify_all();
+      for (std::thread &t : th) t.join();
+      (void)hipStreamSynchronize(copy_stream);  // no copy may still read the ring when the next call refills it
+    }
+  } pool{{}, mu, cv, recorded, H->copy_stream};
+  DevTmp<double> dval;  // the values on the device in the caller's entry order, chunk behind chunk
+  ISPH_CHECK(dval.reserve((size_t)(nnz > 0 ? nnz : 1)));
+  const int nthreads = nchunks > 0 ? P : 0;
+  for (int t = 0; t < nthreads; ++t) pool.th.emplace_back(worker);
+  H->stats[0] = since();
+  int rc = ISPH_SUCCESS;
+  for (long long c = 0; c < nchunks; ++c) {
+    {
+      const double w0 = since();
+      std::unique_lock<std::mutex> lk(mu);
+      cv.wait(lk, [&] { return filled[(size_t)c] != 0; });
+      wait_fill += since() - w0;
+    }
+    const int slot = (int)(c % H->nslots);
+    const long long p0 = cstart[(size_t)c], cnt = cstart[(size_t)c + 1] - p0;
+    char state = 1;
+    if (rc == ISPH_SUCCESS) {
+      if (hipMemcpyAsync(dval.p + p0, H->pslot + (size_t)slot * 12 * HostStager::kChunk, sizeof(double) * (size_t)cnt,
+                         hipMemcpyHostToDevice, H->copy_stream) != hipSuccess ||
+          hipEventRecord(H->ev[(size_t)slot], H->copy_stream) != hipSuccess ||
+          hipStreamWaitEvent(ctx->stream, H->ev[(size_t)slot], 0) != hipSuccess)
+        rc = fail("upload of a chunk of matrix values failed", __FILE__, __LINE__);
+      else
+        hipLaunchKernelGGL(k_pattern_scatter, dim3(pattern_grid(cnt)), dim3(kBlock), 0, ctx->stream, p0, cnt,
+                           (const double *)dval.p + p0, (const unsigned *)A->emap.p, S.val.p);
+    }
+    if (rc != ISPH_SUCCESS) state = 2;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      recorded[(size_t)c] = state;
+    }
+    cv.notify_all();
+  }
+  H->stats[1] = since();
+  const bool copies_ok = hipStreamSynchronize(H->copy_stream) == hipSuccess;
+  H->stats[2] = since();
+  if ((!copies_ok || hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess || hip_err.load()) &&
+      rc == ISPH_SUCCESS)
+    rc = fail("value update of the matrix failed", __FILE__, __LINE__);
+  H->stats[3] = since();
+  ISPH_CHECK(rc);
+  H->bytes_sent = 8 * nnz;
+  H->stats[4] = since(); H->stats[5] = wait_fill; H->stats[6] = (double)H->bytes_sent; H->stats[7] = (double)nthreads;
   return ISPH_SUCCESS;
 }
 

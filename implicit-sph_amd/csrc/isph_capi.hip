@@ -512,6 +512,12 @@ int isph_ctx_hold_neighbours(isph_ctx *ctx, int on) {
   return ISPH_SUCCESS;
 }
 
+int isph_ctx_hold_pattern(isph_ctx *ctx, int on) {
+  ISPH_REQUIRE(ctx, "ctx is NULL");
+  ctx->pattern_hold = on != 0;  // later creations only: a matrix owns its map
+  return ISPH_SUCCESS;
+}
+
 int isph_ctx_set_ordering(isph_ctx *ctx, int mode) {
   ISPH_REQUIRE(ctx && (mode == ISPH_ORDER_CALLER || mode == ISPH_ORDER_BRICKS), "bad ordering mode");
   ctx->ordering = mode;
@@ -700,6 +706,10 @@ int isph_mat_create_csr(isph_ctx *ctx, int nrow, int ncol, const int *rowptr, co
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   isph_mat *A = nullptr;
   ISPH_CHECK(mat_from_device_csr(ctx, nrow, ncol, rowptr, colidx, val, (long long)last, &A));
+  if (ctx->pattern_hold) {  // the entry map from the caller's device arrays and the sorted rows (pattern.hpp)
+    const int rc = pattern_build<int>(ctx, A, rowptr, colidx, CsrChunks{}, nullptr, 0, nullptr);
+    if (rc != ISPH_SUCCESS) { isph_mat_destroy(A); return rc; }
+  }
   *Aout = A;
   return ISPH_SUCCESS;
 }
@@ -723,6 +733,7 @@ int isph_mat_create_csr_coords(isph_ctx *ctx, int nrow, int ncol, const int *row
   isph_mat *A = new isph_mat();
   int rc = sell_permute(ctx, A0->S, *O, A->S);
   if (rc == ISPH_SUCCESS && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail("permutation of the matrix failed", __FILE__, __LINE__);
+  if (rc == ISPH_SUCCESS) rc = pattern_remap(ctx, A0, O->iperm.p, A);  // the map the ingress built follows the entries
   isph_mat_destroy(A0);
   if (rc != ISPH_SUCCESS) { isph_mat_destroy(A); return rc; }
   A->order = O;
@@ -833,6 +844,31 @@ int isph_mat_create_csr_bjacobi(isph_ctx *ctx, int nrow, int ncol, const int *ro
   M->ilu = F;
   *Aout = A;
   *Mout = M;
+  return ISPH_SUCCESS;
+}
+
+int isph_mat_update_values(isph_ctx *ctx, isph_mat *A, const double *val, int on_device) {
+  ISPH_REQUIRE(ctx && A, "NULL argument");
+  ISPH_REQUIRE(val, "update of the matrix values: val is NULL");
+  ISPH_REQUIRE(A->emap.p, "update of the matrix values: the matrix carries no entry map (it was not created from a CSR while "
+                          "isph_ctx_hold_pattern was on, or a row holds a column twice)");
+  if (!on_device) {
+    ISPH_CHECK(mat_update_values_host(ctx, A, val));
+  } else {
+    hipLaunchKernelGGL(k_pattern_scatter, dim3(pattern_grid(A->S.nnz)), dim3(kBlock), 0, ctx->stream, 0LL, A->S.nnz, val,
+                       (const unsigned *)A->emap.p, A->S.val.p);
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    ISPH_CHECK_HIP(hipGetLastError());
+  }
+  ++A->n_updates;
+  return ISPH_SUCCESS;
+}
+
+int isph_mat_pattern_info(const isph_mat *A, long long info[3]) {
+  ISPH_REQUIRE(A && info, "NULL argument");
+  info[0] = A->emap.p ? 1 : 0;
+  info[1] = A->emap.p ? (long long)sizeof(unsigned) * A->S.nnz : 0;
+  info[2] = A->n_updates;
   return ISPH_SUCCESS;
 }
 
@@ -1107,6 +1143,7 @@ void isph_mat_destroy(isph_mat *A) {
   if (!A) return;
   pb_rows_destroy(A->pb);
   A->S.release();
+  A->emap.release();
   A->halo.send_idx.release();
   A->halo.list_int.release();
   A->halo.list_bnd.release();
@@ -1383,6 +1420,30 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;
   *Mout = M;
+  return ISPH_SUCCESS;
+}
+
+int isph_prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
+  ISPH_REQUIRE(ctx && M && A, "NULL argument");
+  if (M->type != 2 || !M->ilu) {
+    static const char *const names[] = {"none", "jacobi", "bjacobi-ilu<k>", "sa-amg", "ilu<k> / additive Schwarz", "overlap ILU(k)",
+                                        "chebyshev<d>"};
+    char msg[200];
+    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to the block stream \"bjacobi-ilu<k>\" only, not to a preconditioner "
+                               "of type \"%s\": rebuild it", M->type >= 0 && M->type <= 6 ? names[M->type] : "?");
+    return fail(msg, __FILE__, __LINE__);
+  }
+  // the subdomains of the library's own numbering come with the matrix: they must be the ones the factor was laid out for
+  const bool mo = (bool)M->order, ao = (bool)A->order;
+  if (mo != ao || (mo && M->order != A->order && M->order->block_ptr != A->order->block_ptr)) {
+    char msg[200];
+    snprintf(msg, sizeof(msg), "refactor: the subdomain table differs (the preconditioner has %d subdomains %s the library's "
+                               "numbering, the matrix %d)", M->ilu->nblocks, mo ? "in" : "outside",
+             ao ? A->order->nblocks() : 0);
+    return fail(msg, __FILE__, __LINE__);
+  }
+  ISPH_CHECK(ilu_refactor(ctx, M->ilu, A->S));
+  M->order = A->order;
   return ISPH_SUCCESS;
 }
 

@@ -32,6 +32,7 @@ EXPORTS = [
     "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits",
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
+    "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
 ]
 
 
@@ -287,6 +288,10 @@ def lib():
         L.isph_nlist_info.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_nlist_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_nlist_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_ctx_hold_pattern.argtypes = [C.c_void_p, C.c_int]
+        L.isph_mat_update_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_mat_pattern_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_prec_refactor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -447,6 +452,11 @@ class Context:
     def hold_neighbours(self, on):
         """isph_ctx_hold_neighbours: while held, the operator calls share one layout of the (unchanged) neighbour list"""
         _check(lib().isph_ctx_hold_neighbours(self.h, int(on)))
+
+    def hold_pattern(self, on):
+        """isph_ctx_hold_pattern: while on, a matrix created from a CSR keeps the map of its entries (Matrix.update_values)
+        and an ILU(k > 0) its fill levels (Precond.refactor)"""
+        _check(lib().isph_ctx_hold_pattern(self.h, int(on)))
 
     PROFILE_CLASSES = ("spmv", "prec_apply", "multi_dot", "multi_axpy_dot", "multi_axpy_norm", "ilu_extract", "ilu_schedule",
                        "ilu_factor")
@@ -643,6 +653,19 @@ class Matrix:
         _check(lib().isph_mat_column_bits(self.ctx.h, self.h, C.byref(b)))
         return b.value
 
+    def update_values(self, val):
+        """isph_mat_update_values: nnz new values (numpy on the host or a torch tensor on the device) in the entry order of
+        the arrays the matrix was created from; needs the map of Context.hold_pattern(True)"""
+        val = _f64(val)
+        _need(val, self.info()["nnz"], "val [nnz]")
+        _check(lib().isph_mat_update_values(self.ctx.h, self.h, _ptr(val), _on_device(val)))
+
+    def pattern_info(self):
+        """isph_mat_pattern_info: (1 when the matrix carries an entry map, bytes of the map, value updates taken)"""
+        a = (C.c_longlong * 3)()
+        _check(lib().isph_mat_pattern_info(self.h, a))
+        return int(a[0]), int(a[1]), int(a[2])
+
     def sampled_product(self, x, nsamples=64, rows_per_sample=64, seed=0):
         """(A x) on `nsamples` runs of `rows_per_sample` consecutive rows, computed ON THE HOST from exported rows: an
         operator application that shares nothing with the SpMV kernels.  Returns (row indices, values)."""
@@ -730,6 +753,11 @@ class Precond:
                 z = np.zeros(self.n)
         _check(lib().isph_prec_apply(self.ctx.h, self.h, _ptr(r), _ptr(z), _on_device(r, z)))
         return z
+
+    def refactor(self, A):
+        """isph_prec_refactor: the numeric factorisation of a "bjacobi-ilu<k>" again on the (updated) values of A; pattern,
+        schedule and layout are kept, the result is bit for bit a fresh create"""
+        _check(lib().isph_prec_refactor(self.ctx.h, self.h, A.h))
 
     @property
     def value_bits(self):

@@ -2,7 +2,12 @@
 // (ref: precond.h:17-46) so PairISPH::initializeSolvers compiles unchanged,
 // forwarding to libisph_hip through the C ABI (include/isph_hip.h).
 #pragma once
+#include <algorithm>
+#include <cstdio>
+#include <memory>
 #include <stdexcept>
+#include <string>
+#include <vector>
 
 #include "isph_compat.h"
 #include "isph_hip.h"
@@ -10,6 +15,14 @@
 namespace LAMMPS_NS {
 
 class SolverLin_HIP;
+class PrecondWrapper;
+
+// SolverLin_HIP::holdPattern: shared by the solver and the wrappers it has solved with while the pattern is held, so that
+// either side may go first (a wrapper takes itself off the list when it is destroyed)
+struct PatternHold {
+  bool on = false;
+  std::vector<PrecondWrapper *> precs;
+};
 
 class PrecondWrapper {
  protected:
@@ -27,7 +40,33 @@ class PrecondWrapper {
   virtual int fusedIngressBlockRows() { return 0; }
   // the wrapper's own table of subdomains for that fused set-up (isph_mat_create_csr_blocks), if it has one
   virtual bool fusedIngressSubdomains(int &, const int *&) { return false; }
-  void adoptDevice(isph_prec *M) { free(); _M = M; }
+  void adoptDevice(isph_prec *M) { destroyDevice(); _M = M; _block_ilu = M != nullptr; _kept_sig = deviceSignature(); }
+  // While SolverLin_HIP holds the pattern (holdPattern(true)), free() KEEPS the device object of a block-stream ILU: the next
+  // createOnDevice on the updated matrix refactors it (isph_prec_refactor: Ifpack's Compute() without Initialize()) when
+  // the wrapper's parameters are the ones it was built with.  Every other device object is released as always.
+  std::shared_ptr<PatternHold> _hold;
+  bool _block_ilu = false;   // _M is a "bjacobi-ilu<k>" (the three block-Jacobi routes of PrecondWrapper_Ifpack, or adopted)
+  bool _kept = false;        // _M was kept by free(): stale until refactored
+  bool _warned_refactor = false;
+  std::string _kept_sig;     // the parameters _M was built with
+  virtual std::string deviceSignature() { return std::string(); }
+  void destroyDevice() {
+    if (_M) { isph_prec_destroy(_M); _M = nullptr; }
+    _block_ilu = false; _kept = false;
+  }
+  // true: the kept object now holds the factorisation of A; false: nothing kept (or it did not fit and was released)
+  bool refactorKept(isph_ctx *ctx, const isph_mat *A) {
+    if (!_kept || !_M) return false;
+    if (_kept_sig == deviceSignature() && isph_prec_refactor(ctx, _M, A) == ISPH_SUCCESS) { _kept = false; return true; }
+    if (_comm.MyPID() == 0 && !_warned_refactor) {
+      std::printf(">> PrecondWrapper(HIP): the kept preconditioner could not be refactored (%s): built anew\n",
+                  _kept_sig == deviceSignature() ? isph_last_error() : "its parameters changed");
+      _warned_refactor = true;
+    }
+    destroyDevice();
+    return false;
+  }
+  void dropKept() { destroyDevice(); _hold.reset(); }
   // Coordinates of the rows, as PrecondWrapper_ML::setCoordinates receives them (ref: precond_ml.h:63-94; borrowed
   // pointers into the adapter's Epetra_MultiVector, pair_isph.cpp:1290-1303).  When a wrapper has them, SolverLin_HIP
   // brings the host matrix in through isph_mat_create_csr_coords: the library then numbers the rows itself (bricks of
@@ -49,7 +88,10 @@ class PrecondWrapper {
 
  public:
   PrecondWrapper(MPI_Comm comm) : _comm(comm) {}
-  virtual ~PrecondWrapper() { free(); }
+  virtual ~PrecondWrapper() {
+    destroyDevice();
+    if (_hold) _hold->precs.erase(std::remove(_hold->precs.begin(), _hold->precs.end(), this), _hold->precs.end());
+  }
 
   virtual void setMatrix(Epetra_CrsMatrix *A) {
     if (A != NULL) _A = Teuchos::rcp(A, false);
@@ -70,7 +112,8 @@ class PrecondWrapper {
   virtual void create() { return; }
   virtual void create(const int) { return; }
   virtual void free() {
-    if (_M) { isph_prec_destroy(_M); _M = nullptr; }
+    if (_M && _block_ilu && _hold && _hold->on) { _kept = true; return; }   // holdPattern: kept for isph_prec_refactor
+    destroyDevice();
   }
   virtual Epetra_Operator *getPrecondOperator() { return NULL; }
   // ref: precond.h:45.  No Thyra operator crosses the boundary: solveBlockProblem applies the device preconditioner to

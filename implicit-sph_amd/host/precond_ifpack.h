@@ -146,7 +146,7 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
                     cp.value_bits);
         _warned = true;
       }
-      free();
+      destroyDevice();
       return isph_prec_create_chebyshev(ctx, A, &cp, &_M);
     }
     if (type != "ILU") {
@@ -165,7 +165,10 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): \"isph: ilu value bits\" = %d is not available; available: 64, 32\n", bits);
       return ISPH_FAILURE;
     }
-    free();
+    // holdPattern: a block-stream ILU kept by free() takes the new values of the updated matrix and is done
+    if (refactorKept(ctx, A)) return ISPH_SUCCESS;
+    destroyDevice();
+    _kept_sig = deviceSignature();
     const int block = _param->get("isph: block rows", 512);
     const std::string mode = _param->get("schwarz: combine mode", "Add");
     // "isph: block rows" = 0: the reference's own decomposition -- one subdomain per rank = the whole local matrix,
@@ -227,6 +230,7 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       noticeOnce(fill, 0, overlap);
       ip.nblocks = (int)_bptr.size() - 1;
       ip.block_ptr = _bptr.data();
+      _block_ilu = true;
       return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create_blocks_fill, bit for bit
     }
     if (block == 0 || block > 1024) {
@@ -243,6 +247,7 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       if (isph_mat_ordering_info(A, oi, NULL) == ISPH_SUCCESS && oi[0] == 1) {
         noticeOnce(fill, -1, overlap);
         ip.block_size = 0;
+        _block_ilu = true;
         return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create("bjacobi-ilu<fill>", 0), bit for bit
       }
     }
@@ -251,7 +256,19 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
     // TGV system 116 iterations against 49 for the whole-matrix ILU(0)); the notice is printed once, on every build.
     noticeOnce(fill, block, overlap);
     ip.block_size = block;
+    _block_ilu = true;
     return isph_prec_create_ilu(ctx, A, &ip, &_M);   // 64 bits: isph_prec_create("bjacobi-ilu<fill>", block), bit for bit
+  }
+  // what a kept block-stream ILU was built with: any change between two held solves means a fresh build
+  virtual std::string deviceSignature() {
+    setParameters(_param.get());
+    std::string sig = _param->get("Precond Type", "ILU");
+    char buf[96];
+    std::snprintf(buf, sizeof(buf), "|%d|%d|%d|%d|%d|", _param->get("fact: level-of-fill", 1), _param->get("isph: block rows", 512),
+                  _param->get("isph: ilu value bits", 64), _param->get("Overlap Level", 1), _cx != nullptr ? _cdim : 0);
+    sig += buf;
+    for (int v : _bptr) { std::snprintf(buf, sizeof(buf), "%d,", v); sig += buf; }
+    return sig;
   }
   bool _warned = false, _warned_table = false;
   std::vector<int> _bptr;  // setSubdomains

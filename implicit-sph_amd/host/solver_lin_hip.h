@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -24,7 +25,28 @@ class SolverLin_HIP : public SolverLin {
  public:
   SolverLin_HIP(MPI_Comm &comm, int device = 0) : SolverLin(comm), _ctx(nullptr), _device(device) {}
   virtual ~SolverLin_HIP() {
+    holdPattern(false);
     if (_ctx) isph_ctx_destroy(_ctx);
+  }
+
+  // Device-side extension (not a reference method).  Between holdPattern(true) and holdPattern(false) the caller
+  // guarantees that the matrices it solves are ONE graph refilled with new values -- PairISPH::compute allocates one A.crs
+  // per call and refills it for every system of the time step (ref: pair_isph.cpp:1266-1270, :1363).  solveProblem then
+  // keeps its device matrix (with the halo plan attached to it) across calls, and a later call whose rowptr / colidx
+  // pointers, row, column and entry counts, ingress route (coordinates, table, block rows) and full row-pointer array
+  // (against a host copy, 4 B per row) match the kept ones sends the VALUES only (isph_mat_update_values: 8 B per entry on
+  // the link, no conversion, no sort, no column windows, no halo plan) and lets a PrecondWrapper_Ifpack refactor its
+  // block-stream ILU (isph_prec_refactor).  The column array is NOT compared: that is the caller's guarantee.  Any
+  // mismatch means a full ingress that replaces the kept matrix, never an error.  holdPattern(false) and the destructor
+  // release everything that was kept.  Without the call nothing changes.
+  void holdPattern(bool on) {
+    _hold->on = on;
+    if (_ctx) isph_ctx_hold_pattern(_ctx, on ? 1 : 0);
+    if (!on) {
+      releaseHeld();
+      for (PrecondWrapper *p : std::vector<PrecondWrapper *>(_hold->precs)) p->dropKept();
+      _hold->precs.clear();
+    }
   }
 
   // same keys/defaults as SolverLin_Belos::setParameters, ref: solver_lin_belos.h:224-264
@@ -104,14 +126,41 @@ class SolverLin_HIP : public SolverLin {
     const bool ordered = prec != NULL && prec->ingressCoordinates(cdim, cx, cy, cz);
     const char *fuse_env = std::getenv("ISPH_DROPIN_FUSED_ORDER");   // "1": the fused form of the ordered ingress (see precond_ifpack.h)
     const bool fuse_ordered = ordered && fuse_env && fuse_env[0] == '1' && _A->NumMyRows() > 0 && prec->orderedIngressFusable();
-    if ((fuse_ordered
+    HeldKey key;
+    key.rp = rp; key.ci = ci; key.nrow = _A->NumMyRows(); key.ncol = _A->NumMyCols(); key.nnz = rp[_A->NumMyRows()];
+    key.kind = fuse_ordered ? 4 : ordered ? 3 : table ? 2 : fused > 0 ? 1 : 0;
+    key.fused = fused; key.cdim = ordered ? cdim : 0; key.cx = ordered ? cx : nullptr; key.cy = ordered ? cy : nullptr;
+    key.cz = ordered ? cz : nullptr;
+    if (table) key.table.assign(subptr, subptr + nsub + 1);
+    // holdPattern: the kept matrix takes the new values when everything but the values is what it was built from
+    bool updated = false;
+    if (_hold->on && _heldA != nullptr && key.same(_held) &&
+        std::memcmp(_held_rp.data(), rp, sizeof(int) * ((size_t)key.nrow + 1)) == 0) {
+      if (isph_mat_update_values(_ctx, _heldA, v, 0) == ISPH_SUCCESS) { A = _heldA; updated = true; }
+    }
+    if (!updated) releaseHeld();
+    if (!updated &&
+        (fuse_ordered
              ? isph_mat_create_csr_coords_bjacobi(_ctx, _A->NumMyRows(), _A->NumMyCols(), rp, ci, v, cdim, cx, cy, cz, &A, &Mfused)
          : ordered ? isph_mat_create_csr_coords(_ctx, _A->NumMyRows(), _A->NumMyCols(), rp, ci, v, cdim, cx, cy, cz, &A)
          : table ? isph_mat_create_csr_blocks(_ctx, _A->NumMyRows(), _A->NumMyCols(), rp, ci, v, nsub, subptr, &A, &Mfused)
          : fused > 0 ? isph_mat_create_csr_bjacobi(_ctx, _A->NumMyRows(), _A->NumMyCols(), rp, ci, v, fused, &A, &Mfused)
                      : isph_mat_create_csr(_ctx, _A->NumMyRows(), _A->NumMyCols(), rp, ci, v, 0, &A)) != ISPH_SUCCESS)
       return report_failure();
-    if (attachHalo(A, *_A) != ISPH_SUCCESS) { isph_mat_destroy(A); isph_prec_destroy(Mfused); return report_failure(); }
+    if (!updated && attachHalo(A, *_A) != ISPH_SUCCESS) { isph_mat_destroy(A); isph_prec_destroy(Mfused); return report_failure(); }
+    if (!updated && _hold->on) {  // kept for the next call; a matrix without a map (a column twice in a row) is not
+      long long pi[3] = {0, 0, 0};
+      if (isph_mat_pattern_info(A, pi) == ISPH_SUCCESS && pi[0] == 1) {
+        _heldA = A;
+        _held = key;
+        _held_rp.assign(rp, rp + key.nrow + 1);
+      }
+    }
+    if (_hold->on && prec != NULL && prec->_hold != _hold) {
+      if (prec->_hold) prec->dropKept();   // it was held by another solver
+      prec->_hold = _hold;
+      _hold->precs.push_back(prec);
+    }
     const std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now();  // the ingress returns synchronised
 
     int rc = ISPH_SUCCESS;
@@ -121,8 +170,9 @@ class SolverLin_HIP : public SolverLin {
     if (prec != NULL) {
       if (_is_singular && prec->usesNullVector()) { createNullVector(); prec->setNullVector(_n->Values()); }  // :149-151
       prec->create();
-      if (fused > 0 || fuse_ordered) prec->adoptDevice(Mfused);
-      else rc = prec->createOnDevice(_ctx, A);  // Ifpack Initialize+Compute happen here (:153)
+      if (!updated && (fused > 0 || fuse_ordered)) prec->adoptDevice(Mfused);
+      else rc = prec->createOnDevice(_ctx, A);  // Ifpack Initialize+Compute happen here (:153); on an updated matrix a kept
+                                                // block ILU is refactored there, and the fused routes build what they fuse
     }
     if (_timing && rc == ISPH_SUCCESS) rc = isph_ctx_sync(_ctx);  // only to attribute the set-up; the solve queues behind it anyway
     const std::chrono::steady_clock::time_point t2 = std::chrono::steady_clock::now();
@@ -137,7 +187,8 @@ class SolverLin_HIP : public SolverLin {
       if (_is_singular && prec->usesNullVector()) prec->setNullVector(NULL);
       prec->free();  // :186-191
     }
-    isph_mat_destroy(A);
+    if (A != _heldA) isph_mat_destroy(A);
+    else if (rc != ISPH_SUCCESS) releaseHeld();
     const std::chrono::steady_clock::time_point t4 = std::chrono::steady_clock::now();
     _ms[0] = std::chrono::duration<double, std::milli>(t1 - t0).count();
     _ms[1] = std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -223,7 +274,8 @@ class SolverLin_HIP : public SolverLin {
   }
 
   const isph_solve_info &lastSolveInfo() const { return _last; }
-  // wall time of the last solveProblem in milliseconds: [0] matrix ingress (host CSR -> device), [1] preconditioner
+  // wall time of the last solveProblem in milliseconds: [0] matrix ingress (host CSR -> device; the value update of a
+  // kept matrix while holdPattern is on), [1] preconditioner
   // set-up, [2] Krylov solve incl. the transfers of b and x, [3] release.  [1] and [2] are only separated when
   // setTiming(true) put a synchronisation between them (not a reference method; diagnostics of the drop-in path)
   const double *lastTimingsMs() const { return _ms; }
@@ -244,6 +296,11 @@ class SolverLin_HIP : public SolverLin {
   }
   int ensureContext() {
     if (_ctx) return ISPH_SUCCESS;
+    const int rc = createContext();
+    if (rc == ISPH_SUCCESS && _hold->on) isph_ctx_hold_pattern(_ctx, 1);
+    return rc;
+  }
+  int createContext() {
     if (!needComm()) return isph_ctx_create(_device, nullptr, &_ctx);
 #ifdef ISPH_HAVE_MPI
     // Which transport: RCCL needs one device per rank.  Ranks that share a device (several MPI ranks of a LAMMPS run
@@ -318,6 +375,28 @@ class SolverLin_HIP : public SolverLin {
     if (_comm.MyPID() == 0) std::fprintf(stderr, ">> SolverLin_HIP: %s\n", isph_last_error());
     return LAMMPS_FAILURE;
   }
+  // holdPattern: what the kept matrix was built from
+  struct HeldKey {
+    const int *rp = nullptr, *ci = nullptr;
+    int nrow = 0, ncol = 0, kind = 0, fused = 0, cdim = 0;
+    long long nnz = 0;
+    const double *cx = nullptr, *cy = nullptr, *cz = nullptr;
+    std::vector<int> table;
+    bool same(const HeldKey &o) const {
+      return rp == o.rp && ci == o.ci && nrow == o.nrow && ncol == o.ncol && nnz == o.nnz && kind == o.kind && fused == o.fused &&
+             cdim == o.cdim && cx == o.cx && cy == o.cy && cz == o.cz && table == o.table;
+    }
+  };
+  void releaseHeld() {
+    if (_heldA) isph_mat_destroy(_heldA);
+    _heldA = nullptr;
+    _held = HeldKey();
+    _held_rp.clear();
+  }
+  std::shared_ptr<PatternHold> _hold = std::make_shared<PatternHold>();
+  isph_mat *_heldA = nullptr;
+  HeldKey _held;
+  std::vector<int> _held_rp;
   isph_ctx *_ctx;
   int _device;
   isph_solve_info _last{};

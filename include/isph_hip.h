@@ -142,6 +142,32 @@ int isph_mat_create_csr_coords_bjacobi(isph_ctx *ctx, int nrow, int ncol, const 
  * column differences where the rows allow them: 10 instead of 12 per entry)  [7] staging threads.
  * No reference counterpart. */
 int isph_ingress_info(const isph_ctx *ctx, double info[8]);
+/* KEEPING A MATRIX' PATTERN.  Within one time step the reference refills ONE Epetra matrix -- one graph -- with new values
+ * and solves it several times (ref: pair_isph.cpp:1266-1270 allocates A.crs; :589 :636 :812 :925 :988-1011 refill it);
+ * Epetra's ReplaceMyValues keeps the graph, and Ifpack's Compute() may be called again after one Initialize().
+ * While isph_ctx_hold_pattern(ctx, 1) is in force, a matrix created from a CSR -- isph_mat_create_csr (host or device
+ * arrays), _bjacobi, _blocks, _coords, _coords_bjacobi -- also keeps an ENTRY MAP: a device array that gives, for every
+ * entry of the caller's CSR in the caller's entry order, its position in the sliced-ELL image (32 bits per entry, built on
+ * the device from the image the ingress leaves there).  The map goes through whatever the ingress did to the entry: the
+ * row sort of unsorted rows, and on the _coords routes the library's row permutation, the column renaming and the sort
+ * by the new column.  The matrix owns its map; switching the mode off only affects later creations.  A matrix with a row
+ * that holds the same column twice is created as without the mode, without a map.  Off by default: every call is then
+ * what it was, launch for launch, and no map is reserved.
+ * While the mode is on, an ILU(k > 0) created by isph_prec_create* also keeps the fill level of its entries (1 B per factor
+ * entry), which isph_prec_refactor needs.  No reference counterpart as a call (Epetra keeps its graph by construction). */
+int isph_ctx_hold_pattern(isph_ctx *ctx, int on);
+/* New values for a matrix that carries a map: val holds nnz doubles in the entry order of the arrays A was created from.
+ * Afterwards A is bit for bit the matrix a fresh create of the same route gives from (same rowptr, same colidx, val) --
+ * the values are moved, not computed with; padding stays 0; row numbering, halo plan, 16-bit column windows and slice
+ * offsets are untouched.  Host values travel through the pinned ring and the staging threads of the ingress in its chunks,
+ * one copy per chunk, 8 B per entry on the link, with the scatter of a chunk queued behind its copy; device values take
+ * one scatter launch.  isph_ingress_info then reports this call ([6] = 8 nnz).  Fails WITHOUT touching A when A has no
+ * map or val is NULL.  Preconditioners built from A before the call are stale: those that apply A itself (Chebyshev, AMG)
+ * and the float plane of a value_bits = 32 Chebyshev must be rebuilt by the caller; a block ILU can be refactored.
+ * Replaces Epetra_CrsMatrix::ReplaceMyValues on a FillComplete'd matrix. */
+int isph_mat_update_values(isph_ctx *ctx, isph_mat *A, const double *val /*[h|d]*/, int on_device);
+/* [0] 1 when A carries a map  [1] bytes of the map  [2] value updates A has taken */
+int isph_mat_pattern_info(const isph_mat *A, long long info[3]);
 /* Halo plan = what Epetra builds inside FillComplete (column map + Import,
  * ref: functor_graph.h:97).  For peer p: send x[send_idx[send_ptr[p]..send_ptr[p+1])]
  * and receive the ghost columns nrow+recv_ptr[p] .. nrow+recv_ptr[p+1]. */
@@ -258,6 +284,19 @@ typedef struct {
 } isph_ilu_params;
 void isph_ilu_params_default(isph_ilu_params *p);
 int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params *prm, isph_prec **M);
+/* Numeric refactorisation of a block-stream ILU ("bjacobi-ilu<k>", k = 0..8, every subdomain route and both value_bits of
+ * isph_ilu_params, preconditioners returned by the fused ingress calls included) on the new values of A: Ifpack's
+ * Compute() after one Initialize() (ref: precond_ifpack.h:60-74 runs both per solve).  KEPT: the row layout of the factor,
+ * its columns and diagonal slots, the levels, the triangular-solve schedule (words, step bytes, row order) and the block
+ * offsets.  REDONE: one kernel refills the factor values from the in-block entries of A's rows (ILU(k): merged into the
+ * factor row, fill slots 0), then the factorisation kernel of the create call runs as it is (value_bits 32: the fp64 stream
+ * is reserved again first, and the rounding pass and its release follow).  BIT FOR BIT what a fresh isph_prec_create_ilu on
+ * A gives: isph_prec_export_ilu, the pivots, the stream, isph_prec_info and the application.  REFUSED: a row whose
+ * in-block columns are not exactly the level-0 columns of its factor row (the message names the first such row), another
+ * row count or subdomain table -- M is then valid only for isph_prec_destroy or another isph_prec_refactor; every other
+ * preconditioner type (the message names it); an ILU(k > 0) created while isph_ctx_hold_pattern was off (its fill levels
+ * were not kept).  A zero pivot shows exactly as after the create call. */
+int isph_prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A);
 /* Ifpack_AdditiveSchwarz<Ifpack_ILU> with the parameters PrecondWrapper_Ifpack sets (ref: precond_ifpack.h:30-45,
  * 60-74): "fact: level-of-fill" (default 1), "Overlap Level" (default 1), "schwarz: combine mode" (default "Add" = 0;
  * 1 = "Zero", restricted additive Schwarz).  block_size = 0: one subdomain = the whole local matrix, which is what
