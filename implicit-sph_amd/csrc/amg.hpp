@@ -61,7 +61,11 @@ struct AmgLevel {
   Cheb *cheb = nullptr;      // isph_amg_params::smoother == 2: the Chebyshev polynomial of this level (chebyshev.hpp)
   DevBuf<int> agg;
   DevBuf<double> nv, x, b, r, z;
+  // which branch of every ladder the set-up took on this level (isph_prec_amg_path): host integers, filled as it goes
+  long long path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+enum { AMG_PATH_MIS_ROUNDS = 0, AMG_PATH_MIS_LIST_ROUNDS, AMG_PATH_PROLONG, AMG_PATH_AP, AMG_PATH_GALERKIN, AMG_PATH_SMOOTHER,
+       AMG_PATH_COARSE, AMG_PATH_PREP };
 
 }  // namespace isph
 
@@ -696,6 +700,7 @@ __global__ void k_low32(long long nnz, const unsigned long long *__restrict__ ke
 // builds of one matrix give the same bits.  With four waves per row the additions to a slot interleaved in the order
 // the waves happened to arrive and the last bits of every coarse operator changed from build to build.
 constexpr int kSpgemmAhead = 8;
+constexpr int kGalerkinTable = 4096;   // table of the Galerkin product R (A P): direct-addressed up to this many coarse columns
 template <int TABLE, int BS, bool FILL>
 __global__ __launch_bounds__(BS) void k_spgemm(int n, int ycols, int yrows, const rp_t *__restrict__ xrp,
                                                const int *__restrict__ xci, const double *__restrict__ xv,
@@ -1009,13 +1014,18 @@ __global__ __launch_bounds__(256) void k_gj_step(int n, int k, double *__restric
   __syncthreads();
   if (t == 0 && k + 1 < n) next[r] = row[k + 1];
 }
-__global__ void k_gj_pivots(int n, const double *__restrict__ aug, const int *__restrict__ pivrow, double *__restrict__ pv) {
+// (err bit 4, a singular operator: the steps ended early, pivrow[k] of the remaining steps was never written and there is no
+// inverse to form -- both kernels leave at once instead of reading the matrix through those words)
+__global__ void k_gj_pivots(int n, const double *__restrict__ aug, const int *__restrict__ pivrow, double *__restrict__ pv,
+                            const int *__restrict__ err) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (*err & 4) return;
   if (k < n) pv[k] = aug[(size_t)pivrow[k] * 2 * n + k];
 }
 __global__ __launch_bounds__(256) void k_gj_finish(int n, double *__restrict__ aug, const int *__restrict__ pivrow,
-                                                   const double *__restrict__ pv) {
+                                                   const double *__restrict__ pv, const int *__restrict__ err) {
   const int k = blockIdx.x, w = 2 * n;
+  if (*err & 4) return;
   const double *src = aug + (size_t)pivrow[k] * w + n;
   const double d = 1.0 / pv[k];
   for (int c = threadIdx.x; c < n; c += 256) aug[(size_t)k * w + c] = src[c] * d;
@@ -1282,19 +1292,26 @@ inline int amg_spgemm_rows(isph_ctx *ctx, const DCsr &X, const DCsr &Y, DCsr &C,
   return ISPH_SUCCESS;   // (the scratch rows go back to the pool, which hands a block out again only after a device synchronisation)
 }
 
-inline int amg_spgemm_ap(isph_ctx *ctx, const DCsr &A, const DCsr &P, DCsr &AP, DevBuf<char> &tmp, int *derr) {
+// *stage: the kernel whose product was kept -- 1 k_spgemm_rows<64>, 2 k_spgemm_rows<256>, 3 k_spgemm<256>, 4 k_spgemm<1024>,
+// 5 k_spgemm<4096>
+inline int amg_spgemm_ap(isph_ctx *ctx, const DCsr &A, const DCsr &P, DCsr &AP, DevBuf<char> &tmp, int *derr, long long *stage) {
   bool overflow = false;
   const char *two = getenv("ISPH_AMG_SPGEMM_TWO_PASS");   // the kernels of rounds 2-4, kept for comparisons
   if (!(two && two[0] == '1')) {
+    *stage = 1;
     ISPH_CHECK(amg_spgemm_rows<64>(ctx, A, P, AP, tmp, derr, &overflow));
     if (!overflow) return ISPH_SUCCESS;
+    *stage = 2;
     ISPH_CHECK(amg_spgemm_rows<256>(ctx, A, P, AP, tmp, derr, &overflow));
     if (!overflow) return ISPH_SUCCESS;
   }
+  *stage = 3;
   ISPH_CHECK(amg_spgemm_try<256>(ctx, A, P, AP, tmp, derr, &overflow));
   if (!overflow) return ISPH_SUCCESS;
+  *stage = 4;
   ISPH_CHECK(amg_spgemm_try<1024>(ctx, A, P, AP, tmp, derr, &overflow));
   if (!overflow) return ISPH_SUCCESS;
+  *stage = 5;
   return amg_spgemm_t<4096, 64>(ctx, A, P, AP, tmp, derr);
 }
 
@@ -1351,6 +1368,7 @@ inline int amg_aggregate(isph_ctx *ctx, AmgLevel *L, double *dg, unsigned long l
   const int *ci = A.ci.p;
   const double *v = A.v.p;
   if (rc == ISPH_SUCCESS) {
+    L->path[AMG_PATH_PREP] = prepared ? 1 : (th2 == 0.0 ? 2 : 3);
     if (prepared) {
     } else if (th2 == 0.0) {
       if (hipMemsetAsync(rho, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
@@ -1367,7 +1385,9 @@ inline int amg_aggregate(isph_ctx *ctx, AmgLevel *L, double *dg, unsigned long l
       int *nlist = round == 0 ? listA.p : (cur ? listA.p : listB.p);
       const int *ccnt = cnt.p + cur;
       int *ncnt = cnt.p + (round == 0 ? 0 : 1 - cur);
+      ++L->path[AMG_PATH_MIS_ROUNDS];
       if (clist && (long long)und * 4 <= n) {
+        ++L->path[AMG_PATH_MIS_LIST_ROUNDS];
         if (hipMemsetAsync(cnt.p + 2, 0, sizeof(int), ctx->stream) != hipSuccess) { rc = fail("memset failed", __FILE__, __LINE__); break; }
         hipLaunchKernelGGL(k_mis_mark, dim3(std::min(kMisGrid, (und + 31) / 32)), dim3(256), 0, ctx->stream, ccnt, clist, rp,
                            (const int *)scp, stamp.p, round, list1.p, cnt.p + 2);
@@ -1505,6 +1525,7 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
         rc = fail("copy failed", __FILE__, __LINE__);
     } else if (rc == ISPH_SUCCESS) {
       one_pass = true;
+      L->path[AMG_PATH_PROLONG] = lpr;
       P.nnz = nnz;
       rc = P.ci.reserve((size_t)(nnz > 0 ? nnz : 1));
       if (rc == ISPH_SUCCESS) rc = P.v.reserve((size_t)(nnz > 0 ? nnz : 1));
@@ -1516,6 +1537,7 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
     }
   }
   if (rc == ISPH_SUCCESS && !one_pass) {
+    L->path[AMG_PATH_PROLONG] = 2;   // the two passes
     if (hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)n + 1), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
     hipLaunchKernelGGL((k_prolong<0>), dim3(gw), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
                        cnt.p, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
@@ -1755,8 +1777,9 @@ inline int amg_dense_invert(isph_ctx *ctx, double *aug, int n, int *derr) {
   for (int k = 0; k < n; ++k)
     hipLaunchKernelGGL(k_gj_step, dim3(n), dim3(256), 0, ctx->stream, n, k, aug, (const double *)((k & 1) ? c1 : c0), (k & 1) ? c0 : c1,
                        usedat, pivrow, derr);
-  hipLaunchKernelGGL(k_gj_pivots, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, (const double *)aug, (const int *)pivrow, pv);
-  hipLaunchKernelGGL(k_gj_finish, dim3(n), dim3(256), 0, ctx->stream, n, aug, (const int *)pivrow, (const double *)pv);
+  hipLaunchKernelGGL(k_gj_pivots, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, (const double *)aug, (const int *)pivrow, pv,
+                     (const int *)derr);
+  hipLaunchKernelGGL(k_gj_finish, dim3(n), dim3(256), 0, ctx->stream, n, aug, (const int *)pivrow, (const double *)pv, (const int *)derr);
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;   // (col / idx go back to the pool, which hands them out again only after a device synchronisation)
 }
@@ -1855,7 +1878,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       identity = stop && h[0] != 0.0 && rc == ISPH_SUCCESS;
       stop = h[0] == 0.0 || rc != ISPH_SUCCESS;
     }
-    if (stop) { L->agg.release(); break; }
+    if (stop) { L->agg.release(); L->path[AMG_PATH_MIS_ROUNDS] = L->path[AMG_PATH_MIS_LIST_ROUNDS] = L->path[AMG_PATH_PREP] = 0; break; }
     AmgLevel *Lc = new AmgLevel();
     if (identity) { nagg = n; rc = amg_identity_prolongator(ctx, L, Lc->nv); }
     else rc = amg_prolongator(ctx, L, dg.p, rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, tmp, derr.p);
@@ -1890,8 +1913,11 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       }
     }
     if (rc == ISPH_SUCCESS) rc = amg_transpose(ctx, L->P, R, tmp);
-    if (rc == ISPH_SUCCESS) rc = amg_spgemm_ap(ctx, L->A, extended ? Pext : L->P, AP, tmp, derr.p);
-    if (rc == ISPH_SUCCESS) rc = amg_spgemm_t<4096, 64>(ctx, R, AP, Lc->A, tmp, derr.p);
+    if (rc == ISPH_SUCCESS) rc = amg_spgemm_ap(ctx, L->A, extended ? Pext : L->P, AP, tmp, derr.p, &L->path[AMG_PATH_AP]);
+    if (rc == ISPH_SUCCESS) {
+      L->path[AMG_PATH_GALERKIN] = AP.m <= kGalerkinTable ? 1 : 2;   // k_spgemm's ycols <= TABLE: direct-addressed / open addressing
+      rc = amg_spgemm_t<kGalerkinTable, 64>(ctx, R, AP, Lc->A, tmp, derr.p);
+    }
     Pext.release();
     int herr = 0;
     if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr.p, &herr);
@@ -1948,8 +1974,10 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     AmgLevel *L = G->L[(size_t)l];
     if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L);
     const bool last = l == G->nlev - 1;
+    if (last) L->path[AMG_PATH_COARSE] = G->coarse_smooth ? 2 : 1;
     if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
       if (!last || G->coarse_smooth) {
+        L->path[AMG_PATH_SMOOTHER] = 3;
         const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, 0.0, 0.0, /*empty_ok=*/l > 0, /*collective=*/dist,
                                   /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits);
         if (rc == ISPH_SUCCESS) rc = r2;
@@ -1961,6 +1989,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       const char *env_stream = getenv("ISPH_AMG_COARSE_STREAM");   // the chunk-stream sweeps on every level (rounds 2-4)
       if (l > 0 && L->A.n > 0 && L->A.n <= kSgsDenseMaxRows && kAmgCoarseBlock == 64 && !(env_stream && env_stream[0] == '1')) {
         const int nb = (L->A.n + 63) / 64;
+        L->path[AMG_PATH_SMOOTHER] = 1;
         // symmetric sweeps: always on a coarsest level the smoother solves, otherwise unless the cycle uses the one-directional sweeps
         const bool need_sym = last || !G->gs_eff, need_dir = G->gs_eff && !last;
         auto build = [&](DevBuf<double> &W, int mode) {
@@ -1974,6 +2003,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
         if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wfwd, 1);
         if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wbwd, 2);
       } else {
+        L->path[AMG_PATH_SMOOTHER] = 2;
         rc = ilu_create(ctx, L->Am, l == 0 ? G->block : kAmgCoarseBlock, &L->sgs, /*sgs=*/true);
       }
     }

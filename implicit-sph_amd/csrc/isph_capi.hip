@@ -1704,6 +1704,14 @@ int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *
   return ISPH_SUCCESS;
 }
 
+int isph_prec_amg_path(isph_ctx *ctx, const isph_prec *M, int level, long long out[8]) {
+  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && out, "not an AMG preconditioner");
+  ISPH_REQUIRE(level >= 0 && level < M->amg->nlev, "level out of range");
+  const AmgLevel *L = M->amg->L[(size_t)level];
+  for (int k = 0; k < 8; ++k) out[k] = L->path[k];
+  return ISPH_SUCCESS;
+}
+
 /* ---- solve ------------------------------------------------------------ */
 
 void isph_solver_params_default(isph_solver_params *p) {

@@ -24,7 +24,7 @@ EXPORTS = [
     "isph_ctx_set_profile", "isph_ctx_hold_neighbours", "isph_ctx_profile_read", "isph_ctx_set_ordering", "isph_ctx_set_periodic_box", "isph_mat_ordering_info", "isph_mat_ordering", "isph_mat_ordering_faces", "isph_ctx_halo_profile_read", "isph_ctx_comm_info", "isph_device_identity", "isph_assemble_poisson", "isph_assemble_helmholtz", "isph_assemble_solute_transport", "isph_assemble_applied_potential", "isph_compute_volumes", "isph_compute_pnd", "isph_compute_corrections", "isph_gradient", "isph_divergence", "isph_correct_velocity_pressure",
     "isph_advance_begin", "isph_advance_end", "isph_compute_shift", "isph_apply_shift", "isph_shift_particles",
     "isph_solve_block", "isph_assemble_block_helmholtz", "isph_amg_params_default", "isph_prec_create_amg", "isph_prec_amg_levels", "isph_prec_amg_info",
-    "isph_prec_amg_export", "isph_prec_amg_aggregates",
+    "isph_prec_amg_export", "isph_prec_amg_aggregates", "isph_prec_amg_path",
     "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
@@ -240,6 +240,7 @@ def lib():
         L.isph_prec_amg_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_aggregates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_prec_amg_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_compute_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int]
         L.isph_apply_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int]
@@ -944,6 +945,14 @@ class PrecondAMG(Precond):
         a = np.zeros(self.level_info(l)["rows"], dtype=np.int32)
         _check(lib().isph_prec_amg_aggregates(self.ctx.h, self.h, l, _ptr(a)))
         return a
+
+    PATH_KEYS = ("mis_rounds", "mis_list_rounds", "prolong", "ap", "galerkin", "smoother", "coarse", "prep")
+
+    def path(self, l):
+        """isph_prec_amg_path: which branch of every ladder the set-up took on level l (see include/isph_hip.h)"""
+        a = (C.c_longlong * 8)()
+        _check(lib().isph_prec_amg_path(self.ctx.h, self.h, l, a))
+        return dict(zip(self.PATH_KEYS, (int(x) for x in a)))
 
 
 def solve(ctx, A, b, x, prec=None, singular=False, null_mask=None, params=None, nvec=1, lda=None):

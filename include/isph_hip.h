@@ -723,6 +723,20 @@ int isph_prec_amg_levels(const isph_prec *M);
 int isph_prec_amg_info(isph_ctx *ctx, const isph_prec *M, int level, long long info[3]);
 int isph_prec_amg_export(isph_ctx *ctx, const isph_prec *M, int level, int what, int *rowptr, int *colidx, double *val);
 int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *agg);
+/* which branch of every ladder the set-up took on `level` (read-only; host integers the set-up counted as it went):
+ *   out[0] MIS rounds of the aggregation, out[1] how many of them ran on work lists (0 / 0 on the coarsest level);
+ *   out[2] prolongator: 16 or 64 = one pass with that many lanes per row, 2 = the two passes;
+ *   out[3] the kernel that gave A P: 1 rows<64>, 2 rows<256>, 3 table<256>, 4 table<1024>, 5 table<4096>;
+ *   out[4] Galerkin product R (A P): 1 direct-addressed table, 2 hashed (more than 4096 coarse columns);
+ *   out[5] smoother: 0 none (coarsest level, direct solve), 1 dense 64-row blocks, 2 chunk stream, 3 Chebyshev;
+ *   out[6] coarsest level only: 1 dense direct solve, 2 the smoother;
+ *   out[7] preparation of the aggregation: 1 inside the SELL -> CSR sweep, 2 one sweep over the CSR copy (threshold 0),
+ *          3 separate kernels (threshold > 0).
+ * Entries 0, 1, 2, 3, 4 and 7 are 0 on the coarsest level (and on a level whose coarsening was given up).  With several
+ * ranks, a level that a rank passes on unchanged (it cannot coarsen while others can: P = I) keeps out[2] = 0 on that
+ * rank while out[3] and out[4] name the kernels of its products; out[0], out[1] and out[7] describe the aggregation it
+ * tried. */
+int isph_prec_amg_path(isph_ctx *ctx, const isph_prec *M, int level, long long out[8]);
 
 /* ---- nonlinear Poisson-Boltzmann: PairISPH::computePoissonBoltzmann (ref: pair_isph.cpp:573-600, every step when
  * enabled, :1312-1313) and the NOX solve it drives through SolverNOX_Stratimikos (pair_isph.h:78).

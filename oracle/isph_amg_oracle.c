@@ -66,8 +66,9 @@ static uint64_t mkkey(int state, int i) {
 
 /* distance-2 MIS roots + "root and its neighbours" aggregates; returns the number of aggregates */
 static double diag_of(const csr_t *A, int i);
-/* ML's strength test: a_ij is strong iff a_ij^2 > theta^2 |a_ii a_jj| (theta = "aggregation: threshold", default 0) */
-#define STRONG(p, i, j) ((j) < n && (j) != (i) && A->v[p] * A->v[p] > th2 * fabs(dg[i] * dg[j]))
+/* ML's strength test: a_ij is strong iff a_ij^2 > theta^2 |a_ii a_jj| (theta = "aggregation: threshold", default 0);
+ * threshold 0: every non-zero off-diagonal entry is strong, whatever its square underflows to (AMG_STRONG, csrc/amg.hpp) */
+#define STRONG(p, i, j) ((j) < n && (j) != (i) && (th2 == 0.0 ? A->v[p] != 0.0 : A->v[p] * A->v[p] > th2 * fabs(dg[i] * dg[j])))
 static int aggregate(const csr_t *A, double theta, int *agg) {
   const int n = A->n;
   const double th2 = theta * theta;
