@@ -11,7 +11,8 @@
 //     (Bell/Dalton/Olson 2012) instead of ML's sequential greedy sweep: same "root + all neighbours" aggregates;
 //   * Gauss-Seidel local to blocks of `block` rows (ML: local to the processor), one residual per sweep:
 //     x += M_B^-1 (b - A x), M_B = blockdiag[(D+L_B) D^-1 (D+U_B)], run through the ILU chunk stream (k_ilu_schedule in Gauss-Seidel mode);
-//   * damping from rho = ||D^-1 A||_inf ("eigen-analysis: type" Anorm).
+//   * damping from rho = ||D^-1 A||_inf ("eigen-analysis: type" Anorm); isph_amg_params::eig_type = 1: from the Arnoldi
+//     estimate of every level (eig_estimate.hpp; ML's "cg"), which also sets the Chebyshev intervals.
 // isph_amg_params::smoother = 2 replaces the Gauss-Seidel sweeps by ML's "Chebyshev" ("MLS") smoother: a polynomial of
 // degree `sweeps` in D^-1 A with the same rho per level (chebyshev.hpp) -- no factor, no dense block inverses, not local
 // to blocks, a symmetric operator; the hierarchy is built by the same code whatever the smoother.
@@ -63,6 +64,8 @@ struct AmgLevel {
   DevBuf<double> nv, x, b, r, z;
   // which branch of every ladder the set-up took on this level (isph_prec_amg_path): host integers, filled as it goes
   long long path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // isph_amg_params::eig_type == 1: the estimate of lambda_max(D^-1 A_l) of this level's fp64 operator (eig_estimate.hpp)
+  EigResult eig;
 };
 enum { AMG_PATH_MIS_ROUNDS = 0, AMG_PATH_MIS_LIST_ROUNDS, AMG_PATH_PROLONG, AMG_PATH_AP, AMG_PATH_GALERKIN, AMG_PATH_SMOOTHER,
        AMG_PATH_COARSE, AMG_PATH_PREP };
@@ -74,6 +77,7 @@ struct isph_amg {
   int gs_eff = 0;         // isph_amg_params::smoother == 1: forward sweeps before, backward sweeps after the coarse correction
   int cheb_value_bits = 64;   // smoother == 2: 32 = every level's polynomial sweeps a float plane of its operator (chebyshev.hpp)
   int cheb = 0;           // isph_amg_params::smoother == 2: Chebyshev polynomial of degree `sweeps` in D^-1 A, before and after
+  int eig_type = 0, eig_iters = 10;   // isph_amg_params: 1 = damping and Chebyshev intervals from the Arnoldi estimate of every level
   int coarse_smooth = 0;  // coarsest level solved by the smoother: singular system (precond_ml.h:97-127) or a level too
                           // large for the dense inverse (no coarsening possible: isolated / Dirichlet rows dominate)
   std::vector<isph::AmgLevel *> L;
@@ -1441,8 +1445,9 @@ inline int amg_aggregate(isph_ctx *ctx, AmgLevel *L, double *dg, unsigned long l
 
 // P = (I - omega/rho D^-1 A) P_tent and the coarse null vector
 // rho_ready: the device word already holds rho (amg_aggregate with threshold 0)
+// lambda > 0 (isph_amg_params::eig_type == 1): the damping is omega / lambda, the level's clipped eigenvalue estimate
 inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigned long long *rho_dev, bool rho_ready, int nagg, double omega,
-                           DevBuf<double> &nvc, DevBuf<char> &tmp, int *derr) {
+                           DevBuf<double> &nvc, DevBuf<char> &tmp, int *derr, double lambda = 0.0) {
   const DCsr &A = L->A;
   const int n = A.n;
   DevTmp<unsigned long long> k0, k1;
@@ -1486,7 +1491,7 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
          hipStreamSynchronize(ctx->stream) != hipSuccess))
       rc = fail("rho read-back failed", __FILE__, __LINE__);
   }
-  const double damp = rho_h > 0.0 ? omega / rho_h : 0.0;
+  const double damp = lambda > 0.0 ? omega / lambda : rho_h > 0.0 ? omega / rho_h : 0.0;
   DCsr &P = L->P;
   P.n = n; P.m = nagg;
   if (rc == ISPH_SUCCESS) rc = P.rp.reserve((size_t)n + 1);
@@ -1793,6 +1798,22 @@ inline int amg_level_buffers(AmgLevel *L) {
   return ISPH_SUCCESS;
 }
 
+// isph_amg_params::eig_type == 1: the estimate of lambda_max(D^-1 A_l) for the fp64 operator of level `level` into L->eig
+// (the diagonal and the bound rho from the level's SELL matrix).  dist: collective, rho is the all-reduced maximum.
+inline int amg_level_estimate(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int level, bool dist) {
+  DevTmp<double> dinv;
+  double rho = 0.0;
+  int rc = cheb_diag_rho(ctx, L->Am, dinv, &rho);
+  if (dist) {
+    double h[2] = {rc == ISPH_SUCCESS ? rho : 0.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
+    if (comm_host_allreduce(ctx, h, 2, /*max*/ 1) != ISPH_SUCCESS) return fail("AMG: the all-reduce of rho failed", __FILE__, __LINE__);
+    if (h[1] != 0.0) return rc != ISPH_SUCCESS ? rc : fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
+    rho = h[0];
+  }
+  if (rc != ISPH_SUCCESS) return rc;
+  return eig_estimate(ctx, L->Am, nullptr, dinv.p, rho, G->eig_iters, level, eig_unfused_env(), dist, &L->eig);
+}
+
 inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
                       isph_amg **out) {
   ISPH_REQUIRE(prm->max_levels >= 1 && prm->max_levels <= 8, "max_levels must be in [1,8]");
@@ -1805,7 +1826,11 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_ratio > 1.0, "Chebyshev smoother: cheb_ratio (\"smoother: Chebyshev alpha\") must be > 1");
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_value_bits == 0 || prm->cheb_value_bits == 64 || prm->cheb_value_bits == 32,
                "Chebyshev smoother: cheb_value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
+  ISPH_REQUIRE(prm->eig_type == 0 || prm->eig_type == 1,
+               "eig_type must be 0 (the bound rho = ||D^-1 A||_inf, \"Anorm\") or 1 (the Arnoldi estimate, ML's \"cg\")");
+  ISPH_REQUIRE(prm->eig_iters >= 1 && prm->eig_iters <= kEigMaxIters, "eig_iters (\"eigen-analysis: iterations\") must be in [1,50]");
   isph_amg *G = new isph_amg();
+  G->eig_type = prm->eig_type; G->eig_iters = prm->eig_iters;
   G->cheb_value_bits = (prm->smoother == 2 && prm->cheb_value_bits == 32) ? 32 : 64;
   G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
   G->gs_eff = prm->smoother == 1;
@@ -1879,9 +1904,13 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       stop = h[0] == 0.0 || rc != ISPH_SUCCESS;
     }
     if (stop) { L->agg.release(); L->path[AMG_PATH_MIS_ROUNDS] = L->path[AMG_PATH_MIS_LIST_ROUNDS] = L->path[AMG_PATH_PREP] = 0; break; }
+    // eig_type 1: the damping is omega / lambda of this level (dist: all ranks are here together and none has failed;
+    // a rank that passes its level on unchanged still takes part in the collective estimate)
+    if (G->eig_type == 1) rc = amg_level_estimate(ctx, G, L, G->nlev - 1, dist);
     AmgLevel *Lc = new AmgLevel();
-    if (identity) { nagg = n; rc = amg_identity_prolongator(ctx, L, Lc->nv); }
-    else rc = amg_prolongator(ctx, L, dg.p, rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, tmp, derr.p);
+    if (rc == ISPH_SUCCESS && identity) { nagg = n; rc = amg_identity_prolongator(ctx, L, Lc->nv); }
+    else if (rc == ISPH_SUCCESS) rc = amg_prolongator(ctx, L, dg.p, rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, tmp, derr.p,
+                              G->eig_type == 1 ? L->eig.lambda_used : 0.0);
     DCsr AP, Pext;
     DCsr &R = L->R;
     const isph_halo &H = L->Am->halo;
@@ -1964,6 +1993,9 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     nc_glob = tot > 2.0e9 ? 2000000000 : (int)tot;
     G->coarse_smooth = G->singular || nc_glob > kAmgDenseMax;
   }
+  // eig_type 1: the coarsest level has no prolongator but its estimate serves the polynomial that "solves" it and
+  // isph_prec_eig_estimate (dist: rc is agreed between the ranks here)
+  if (G->eig_type == 1 && rc == ISPH_SUCCESS) rc = amg_level_estimate(ctx, G, G->L.back(), G->nlev - 1, dist);
   // Chebyshev across ranks: rho of a level is all-reduced, one collective call per level.  The walk is entered only
   // when the set-up has succeeded so far -- after the consensus above that is all ranks or none, and with success on all
   // ranks every rank has gone through the same coarsening steps, so nlev is agreed here (a rank that failed in a step
@@ -1978,8 +2010,12 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
       if (!last || G->coarse_smooth) {
         L->path[AMG_PATH_SMOOTHER] = 3;
-        const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, 0.0, 0.0, /*empty_ok=*/l > 0, /*collective=*/dist,
-                                  /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits);
+        // eig_type 1: the interval [lambda / cheb_ratio, 1.1 lambda] from the level's estimate -- the one the damping used
+        // for double values, a second one on the float plane for cheb_value_bits 32 (the interval comes from fl32(A_l))
+        const bool reuse = G->eig_type == 1 && G->cheb_value_bits != 32;
+        const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, reuse ? L->eig.lambda_used : 0.0, 0.0, /*empty_ok=*/l > 0,
+                                  /*collective=*/dist, /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits,
+                                  reuse ? 0 : G->eig_type, G->eig_iters, l);
         if (rc == ISPH_SUCCESS) rc = r2;
       }
       continue;

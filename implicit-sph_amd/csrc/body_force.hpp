@@ -22,6 +22,7 @@
 // Like the gradient / divergence operators these sweeps work in the caller's particle numbering; one lane per particle,
 // the lane-interleaved neighbour list, pair_rsq for every cut test.
 #pragma once
+#include "philox.hpp"
 #include "surface_tension.hpp"
 
 namespace isph {
@@ -120,24 +121,6 @@ __global__ __launch_bounds__(kBlock) void k_ek_force(AsmTables T, OpArgs a, EkAr
       e.f[3 * (size_t)i + k] -= c * (-e.psiref * gpsi[k] + ek);
     }
   }
-}
-
-// Philox4x32-10 (Salmon, Moraes, Dror, Shaw: Parallel random numbers: as easy as 1, 2, 3, SC'11)
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned out[4]) {
-  for (int round = 0; round < 10; ++round) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// two 32-bit words -> a uniform in (0, 1]: the upper 53 bits, centred in their cell
-__device__ __forceinline__ double philox_uniform(unsigned hi, unsigned lo) {
-  const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-  return ((double)(w >> 11) + 0.5) * 0x1.0p-53;
 }
 
 // the packed slot of T[a][b], a <= b: (0,0), (0,1), (1,1), (0,2), (1,2), (2,2) -- the order of Lc

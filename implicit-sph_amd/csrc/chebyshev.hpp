@@ -3,7 +3,8 @@
 //
 // The recurrence is Ifpack_Chebyshev::ApplyInverse / ML_Cheby restated from the packages' algorithm (Trilinos is not
 // vendored: unpinned against them):
-//     lambda = rho = ||D^-1 A||_inf (all-reduced maximum on several ranks), beta = 1.1 lambda, alpha = lambda / ratio,
+//     lambda = rho = ||D^-1 A||_inf (all-reduced maximum on several ranks; eig_type 1: min(rho, the Arnoldi estimate of
+//     eig_estimate.hpp)), beta = 1.1 lambda, alpha = lambda / ratio,
 //     theta = (beta + alpha) / 2, delta = (beta - alpha) / 2, sigma = theta / delta, rho_0 = 1 / sigma
 //     step 1:        w = (1/theta) D^-1 (b - A y),                              y += w
 //     step k = 2..d: rho_k = 1 / (2 sigma - rho_{k-1}),
@@ -25,6 +26,7 @@
 // 100^3: 147.8 against 207.1 us per step for 0.62 of the bytes -- no longer HBM-bound.
 #pragma once
 #include <cfloat>
+#include "eig_estimate.hpp"
 #include "solver.hpp"
 
 namespace isph {
@@ -34,6 +36,8 @@ constexpr int kChebMaxDegree = 16;
 struct Cheb {
   int n = 0, degree = 1, unfused = 0, value_bits = 64;
   double lambda = 0.0, alpha = 0.0, beta = 0.0;
+  double rho = 0.0;                                  // ||D^-1 A||_inf (all-reduced), whatever lambda came from
+  int eig_type = 0, eig_steps = 0;                   // eig_type 1: lambda = min(Arnoldi estimate, rho) after eig_steps steps
   double c1[kChebMaxDegree], c2[kChebMaxDegree];   // step k (0-based): w = c1[k] w + c2[k] D^-1 (b - A y)
   DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
   DevBuf<float> val32;                               // value_bits 32: fl32 of S.val, position by position (padding 0)
@@ -272,12 +276,34 @@ __global__ __launch_bounds__(kBlock) void k_cheby_update(int n, double c1, doubl
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
+// 1 / a_ii of every row into dinv and the rank's own rho = max_i sum_j |a_ij| / |a_ii| (k_cheby_setup on the double values,
+// rows without a diagonal: dinv = 0): what the eigenvalue estimate of an AMG level needs before any polynomial exists.
+inline int cheb_diag_rho(isph_ctx *ctx, const isph_mat *A, DevBuf<double> &dinv, double *rho) {
+  const Sell &S = A->S;
+  DevTmp<unsigned long long> flag;
+  ISPH_CHECK(flag.reserve(3));
+  ISPH_CHECK(dinv.reserve((size_t)(S.nrow > 0 ? S.nrow : 1) + 64));
+  ISPH_CHECK_HIP(hipMemsetAsync(flag.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  if (S.nslices > 0)
+    hipLaunchKernelGGL((k_cheby_setup<double>), dim3((S.nslices + 3) / 4), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices,
+                       (const long long *)S.slice_off.p, (const int *)S.col.p, (const double *)S.val.p, 1, dinv.p, flag.p);
+  unsigned long long hb = 0ull;
+  ISPH_CHECK_HIP(hipMemcpyAsync(&hb, flag.p, sizeof(hb), hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  memcpy(rho, &hb, sizeof(double));
+  return ISPH_SUCCESS;
+}
+
 // collective: every rank of the context calls this together (stand-alone: a context with a communicator; AMG: a
 // hierarchy across ranks) -- rho is the all-reduced maximum and a failure on one rank is a failure on all.
 // prior_failure: this rank has already failed and only takes part in the collective step.
 // value_bits: 64, or 32 = the polynomial of fl32(A) (the caller has checked the value).
+// eig_type 1 (with lambda_max <= 0): lambda is the clipped Arnoldi estimate of eig_estimate.hpp after eig_iters steps on
+// the operator the sweeps apply (the float plane with value_bits 32), start vector of `eig_level`; collective like rho.
 inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio, double lambda_max, double lambda_min,
-                      bool empty_ok, bool collective, bool prior_failure, Cheb **out, int value_bits = 64) {
+                      bool empty_ok, bool collective, bool prior_failure, Cheb **out, int value_bits = 64, int eig_type = 0,
+                      int eig_iters = 10, int eig_level = 0) {
   const Sell &S = A->S;
   int rc = ISPH_SUCCESS;
   Cheb *C = new Cheb();
@@ -327,7 +353,18 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
     else if (h[1] != 0.0 && rc == ISPH_SUCCESS) rc = fail("Chebyshev: set-up failed on another rank", __FILE__, __LINE__);
   }
   if (rc != ISPH_SUCCESS || prior_failure) { cheb_destroy(C); return rc != ISPH_SUCCESS ? rc : ISPH_FAILURE; }
+  C->rho = h[0];
   C->lambda = lambda_max > 0.0 ? lambda_max : h[0];
+  if (eig_type == 1 && !(lambda_max > 0.0)) {
+    // (every rank is here or none: a failure above has been all-reduced)
+    EigResult e;
+    rc = eig_estimate(ctx, A, f32 ? (const float *)C->val32.p : nullptr, C->dinv.p, C->rho, eig_iters, eig_level, eig_unfused_env(),
+                      collective, &e);
+    if (rc != ISPH_SUCCESS) { cheb_destroy(C); return rc; }
+    C->eig_type = 1;
+    C->eig_steps = e.steps;
+    C->lambda = e.lambda_used;
+  }
   if (!(C->lambda > 0.0)) C->lambda = 1.0;   // a level without entries: D^-1 A is empty, any interval does
   C->beta = 1.1 * C->lambda;
   C->alpha = lambda_min > 0.0 ? lambda_min : C->lambda / ratio;

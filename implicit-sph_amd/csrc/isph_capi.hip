@@ -1328,6 +1328,7 @@ int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params
 void isph_cheb_params_default(isph_cheb_params *p) {
   // Ifpack_Chebyshev's defaults: "chebyshev: degree" 1, "chebyshev: ratio eigenvalue" 30; the eigenvalues from rho
   p->degree = 1; p->ratio = 30.0; p->lambda_max = 0.0; p->lambda_min = 0.0; p->value_bits = 64;
+  p->eig_type = 0; p->eig_iters = 10;  // the bound rho ("Anorm"); ML's "eigen-analysis: iterations" for eig_type 1
 }
 
 static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec *M) {
@@ -1335,11 +1336,14 @@ static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb
   ISPH_REQUIRE(prm->ratio > 1.0, "Chebyshev: ratio (\"chebyshev: ratio eigenvalue\") must be > 1");
   ISPH_REQUIRE(prm->value_bits == 0 || prm->value_bits == 64 || prm->value_bits == 32,
                "Chebyshev: value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
+  ISPH_REQUIRE(prm->eig_type == 0 || prm->eig_type == 1,
+               "Chebyshev: eig_type must be 0 (the bound rho = ||D^-1 A||_inf) or 1 (the Arnoldi estimate)");
+  ISPH_REQUIRE(prm->eig_iters >= 1 && prm->eig_iters <= kEigMaxIters, "Chebyshev: eig_iters must be in [1,50]");
   M->type = 6;
   M->cheb_A = A;
   return cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
                     /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb,
-                    prm->value_bits == 32 ? 32 : 64);
+                    prm->value_bits == 32 ? 32 : 64, prm->eig_type, prm->eig_iters, /*eig_level=*/0);
 }
 
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **Mout) {
@@ -1353,6 +1357,32 @@ int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;
   *Mout = M;
+  return ISPH_SUCCESS;
+}
+
+int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double out[3]) {
+  ISPH_REQUIRE(ctx && M && out, "NULL argument");
+  ISPH_REQUIRE((M->type == 6 && M->cheb) || (M->type == 3 && M->amg),
+               "isph_prec_eig_estimate: not a Chebyshev or an AMG preconditioner");
+  if (M->type == 6) {
+    ISPH_REQUIRE(level == 0, "level out of range");
+    const Cheb *C = M->cheb;
+    out[0] = C->eig_type == 1 ? C->lambda : C->rho; out[1] = C->rho; out[2] = (double)C->eig_steps;
+    return ISPH_SUCCESS;
+  }
+  const isph_amg *G = M->amg;
+  ISPH_REQUIRE(level >= 0 && level < G->nlev, "level out of range");
+  const AmgLevel *L = G->L[(size_t)level];
+  if (G->eig_type == 1) {
+    out[0] = L->eig.lambda_used; out[1] = L->eig.rho; out[2] = (double)L->eig.steps;
+    return ISPH_SUCCESS;
+  }
+  // eig_type 0 keeps no number per level (the set-up launches nothing for this call): rho of the level's operator, now
+  DevTmp<double> dinv;
+  double h[1] = {0.0};
+  ISPH_CHECK(cheb_diag_rho(ctx, L->Am, dinv, &h[0]));
+  if (G->dist) ISPH_CHECK(comm_host_allreduce(ctx, h, 1, /*max*/ 1));
+  out[0] = h[0]; out[1] = h[0]; out[2] = 0.0;
   return ISPH_SUCCESS;
 }
 
@@ -1601,6 +1631,7 @@ void isph_amg_params_default(isph_amg_params *p) {
   p->smoother = 0;
   p->cheb_ratio = 20.0;  // ML's "smoother: Chebyshev alpha"
   p->cheb_value_bits = 64;
+  p->eig_type = 0; p->eig_iters = 10;  // "eigen-analysis: type" Anorm (the wrapper's rule); ML's "eigen-analysis: iterations"
 }
 
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,

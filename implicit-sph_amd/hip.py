@@ -30,6 +30,7 @@ EXPORTS = [
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
     "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits",
+    "isph_prec_eig_estimate",
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
     "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
@@ -40,7 +41,7 @@ class AmgParams(C.Structure):
     """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55)."""
     _fields_ = [("max_levels", C.c_int), ("coarse_max", C.c_int), ("omega", C.c_double), ("block", C.c_int),
                 ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double),
-                ("cheb_value_bits", C.c_int)]
+                ("cheb_value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -233,6 +234,7 @@ def lib():
         L.isph_cheb_params_default.argtypes = [C.c_void_p]
         L.isph_prec_create_chebyshev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_value_bits.argtypes = [C.c_void_p]
+        L.isph_prec_eig_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_ilu_params_default.argtypes = [C.c_void_p]
         L.isph_ilu_params_default.restype = None
         L.isph_prec_create_ilu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -767,6 +769,13 @@ class Precond:
         ("bjacobi-ilu<k>-f32"); 0 for every other preconditioner."""
         return int(lib().isph_prec_value_bits(self.h))
 
+    def eig_estimate(self, level=0):
+        """isph_prec_eig_estimate: lambda_used, rho = ||D^-1 A||_inf and the Arnoldi steps taken, for a Chebyshev
+        preconditioner or level `level` of an AMG ({rho, rho, 0} with eig_type 0)"""
+        a = (C.c_double * 3)()
+        _check(lib().isph_prec_eig_estimate(self.ctx.h, self.h, int(level), a))
+        return dict(lambda_used=float(a[0]), rho=float(a[1]), steps=int(a[2]))
+
     def info(self):
         a = (C.c_longlong * 4)()
         _check(lib().isph_prec_info(self.ctx.h, self.h, a))
@@ -870,9 +879,10 @@ class PrecondOverlap(Precond):
 
 class ChebParams(C.Structure):
     """Mirror of isph_cheb_params: Ifpack's "chebyshev: degree", "chebyshev: ratio eigenvalue", "chebyshev: max eigenvalue",
-    "chebyshev: min eigenvalue" (<= 0: from rho = ||D^-1 A||_inf); value_bits 64 | 32 (the polynomial of fl32(A))."""
+    "chebyshev: min eigenvalue" (<= 0: from rho = ||D^-1 A||_inf); value_bits 64 | 32 (the polynomial of fl32(A));
+    eig_type 0 | 1 (lambda_max <= 0: from rho | from eig_iters Arnoldi steps, clipped by rho)."""
     _fields_ = [("degree", C.c_int), ("ratio", C.c_double), ("lambda_max", C.c_double), ("lambda_min", C.c_double),
-                ("value_bits", C.c_int)]
+                ("value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -884,12 +894,13 @@ class ChebParams(C.Structure):
 class PrecondChebyshev(Precond):
     """isph_prec_create_chebyshev: Chebyshev polynomial in D^-1 A ("Precond Type" = "Chebyshev").  The matrix is applied,
     not copied: it is kept alive here.  value_bits = 32: the sweeps read the matrix values rounded to float (a plane the
-    preconditioner owns); the result is the fp64 recurrence on fl32(A)."""
+    preconditioner owns); the result is the fp64 recurrence on fl32(A).  eig_type = 1: lambda from eig_iters Arnoldi steps
+    on D^-1 A (clipped by rho) where lambda_max <= 0; .eig_estimate() reads it back."""
 
-    def __init__(self, ctx, A, degree=1, ratio=30.0, lambda_max=0.0, lambda_min=0.0, value_bits=64):
+    def __init__(self, ctx, A, degree=1, ratio=30.0, lambda_max=0.0, lambda_min=0.0, value_bits=64, eig_type=0, eig_iters=10):
         self.ctx, self.h, self.n, self.A = ctx, C.c_void_p(), A.info()["nrow"], A
         prm = ChebParams(degree=int(degree), ratio=float(ratio), lambda_max=float(lambda_max), lambda_min=float(lambda_min),
-                         value_bits=int(value_bits))
+                         value_bits=int(value_bits), eig_type=int(eig_type), eig_iters=int(eig_iters))
         _check(lib().isph_prec_create_chebyshev(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
 
 
@@ -913,12 +924,20 @@ def solve_block(ctx, blocks, b, x, prec=None, params=None, lda=None):
 
 
 class PrecondAMG(Precond):
-    """isph_prec_create_amg == PrecondWrapper_ML::create() (with setNullVector when nullvec is given)."""
+    """isph_prec_create_amg == PrecondWrapper_ML::create() (with setNullVector when nullvec is given).  eig_type / eig_iters
+    (when given) replace the fields of params: 1 = every level's damping and Chebyshev interval from the Arnoldi estimate;
+    .eig_estimate(level) reads the numbers back."""
 
-    def __init__(self, ctx, A, nullvec=None, params=None):
+    def __init__(self, ctx, A, nullvec=None, params=None, eig_type=None, eig_iters=None):
         self.ctx, self.n = ctx, A.info()["nrow"]
         self.h = C.c_void_p()
         prm = params or AmgParams()
+        if eig_type is not None or eig_iters is not None:
+            prm = AmgParams(**{k: getattr(prm, k) for k, _ in AmgParams._fields_})
+            if eig_type is not None:
+                prm.eig_type = int(eig_type)
+            if eig_iters is not None:
+                prm.eig_iters = int(eig_iters)
         nv = None if nullvec is None else _f64(nullvec)
         _check(lib().isph_prec_create_amg(ctx.h, A.h, C.byref(prm), _ptr(nv), int(nv is not None and _is_torch(nv)),
                                           C.byref(self.h)))

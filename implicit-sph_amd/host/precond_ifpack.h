@@ -140,6 +140,17 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
                      cp.value_bits);
         return ISPH_FAILURE;
       }
+      // device-side extensions (not reference keys): where "chebyshev: max eigenvalue" is not given, "Anorm" (the default)
+      // takes lambda_max = rho = ||D^-1 A||_inf, "arnoldi" the estimate after "... iterations" Arnoldi steps, clipped by rho
+      // (isph_cheb_params::eig_type)
+      const std::string eig = _param->get("isph: chebyshev eigen-analysis", "Anorm");
+      if (eig != "Anorm" && eig != "arnoldi") {
+        std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): \"isph: chebyshev eigen-analysis\" = '%s' is not available; available: "
+                             "\"Anorm\", \"arnoldi\"\n", eig.c_str());
+        return ISPH_FAILURE;
+      }
+      cp.eig_type = eig == "arnoldi" ? 1 : 0;
+      cp.eig_iters = _param->get("isph: chebyshev eigen-analysis iterations", cp.eig_iters);
       if (_comm.MyPID() == 0 && !_warned) {
         std::printf(">> PrecondWrapper_Ifpack(HIP): Chebyshev polynomial of degree %d in D^-1 A (%d-bit matrix values); "
                     "\"Overlap Level\" and \"isph: block rows\" mean nothing for this type and are ignored\n", cp.degree,

@@ -78,6 +78,17 @@ class PrecondWrapper_ML : public PrecondWrapper {
                    prm.cheb_value_bits);
       return ISPH_FAILURE;
     }
+    // ML's own keys.  "Anorm" -- the bound rho = ||D^-1 A||_inf -- is this wrapper's default and a kept departure (ML's
+    // default is "cg"); "cg" asks for the estimate after "eigen-analysis: iterations" steps, which the device takes with
+    // Arnoldi (isph_amg_params::eig_type = 1: correct for the nonsymmetric matrices too, the same projection otherwise)
+    const std::string eig = _param->get("eigen-analysis: type", "Anorm");
+    if (eig != "Anorm" && eig != "cg") {
+      std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): \"eigen-analysis: type\" = '%s' is not available; available: \"Anorm\", \"cg\"\n",
+                   eig.c_str());
+      return ISPH_FAILURE;
+    }
+    prm.eig_type = eig == "cg" ? 1 : 0;
+    prm.eig_iters = _param->get("eigen-analysis: iterations", 10);
     // (ml.xml of the benchmark protocol asks for 10 levels; the device hierarchy holds 8, and 3-4 are reached at 10^6 rows)
     prm.max_levels = _param->get("max levels", 5) > 8 ? 8 : _param->get("max levels", 5);
     prm.coarse_max = _param->get("coarse: max size", 128);

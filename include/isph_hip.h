@@ -360,11 +360,29 @@ int isph_prec_create_overlap(isph_ctx *ctx, const isph_mat *Aext, int nlocal, in
  * to 0.  A must still outlive the preconditioner (columns and slice offsets are A's).  Any other value is refused.
  * Measured at 100^3 (profiles/chebyshev_f32_100cubed.txt): one step 147.8 against 207.1 us, "chebyshev3"
  * 13.8 against 16.4 ms per solve with 22 iterations either way; not measured on more than one rank.
+ * eig_type (ML's "eigen-analysis: type"): 0 (the default, "Anorm") is the rule above; 1 (ML's "cg") takes, where
+ * lambda_max <= 0, lambda = min(lambda_est, rho) with lambda_est the largest real part of the Ritz values after eig_iters
+ * (ML's "eigen-analysis: iterations", default 10, 1..50; at most the global row count) Arnoldi steps on D^-1 A of the
+ * operator the sweeps apply -- across the halo on several ranks, the float plane with value_bits = 32.  An explicit
+ * lambda_max > 0 still wins, and the 1.1 boost stays.  Departures from ML, declared: Arnoldi (classical
+ * Gram-Schmidt twice per step) instead of ML's CG/Lanczos, which is meaningless for the nonsymmetric matrices of particle
+ * shifting and wall rows and the same projection for a symmetric one; a deterministic start vector (first word of
+ * Philox4x32-10, key (0x15B4, 0), counter (global row in the caller's numbering, level, 0, 0), u = (w + 0.5) / 2^31 - 1)
+ * instead of ML's random one, so that the estimate depends neither on the library's row numbering nor on the rank count
+ * up to summation rounding; and clipping by the rigorous bound rho (rho also stands when lambda_est is not finite or
+ * <= 0).  The estimate stops early at an invariant subspace (h_{j+1,j} <= 1e-14 |h_00|).  Its product is one sweep with
+ * the scaling in the epilogue; ISPH_EIG_UNFUSED=1 at create time runs a product and a scaling kernel instead (cross-
+ * checks).  Measured at 100^3 (profiles/eig_estimate_100cubed.txt): lambda = 1.1128 where rho = 2.0000, the
+ * estimate takes 2.7 ms of the create call, "chebyshev3" 17 against 22 iterations and 15.0 against 15.7 ms for create plus
+ * solve; on small systems the iteration count of the stand-alone polynomial moves both ways; not timed on more than one
+ * rank.  Any other eig_type or eig_iters is refused.  The string form "chebyshev<d>" keeps eig_type 0.
  * Call isph_cheb_params_default FIRST and then change fields: the struct grows at its tail. */
 typedef struct {
   int degree;
   double ratio, lambda_max, lambda_min;
   int value_bits;
+  int eig_type;  /* 0 = lambda from rho (default), 1 = from the Arnoldi estimate */
+  int eig_iters; /* eig_type 1: Arnoldi steps, 1..50 (default 10) */
 } isph_cheb_params;
 void isph_cheb_params_default(isph_cheb_params *p);
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **M);
@@ -372,6 +390,12 @@ int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb
  * smoother = 2); 32 for a block ILU whose solves stream single-precision factor values ("bjacobi-ilu<k>-f32",
  * isph_ilu_params::value_bits = 32); 0 for every other preconditioner -- a plain "bjacobi-ilu<k>" included -- and for NULL. */
 int isph_prec_value_bits(const isph_prec *M);
+/* out = {lambda_used, rho, Arnoldi steps taken} of a Chebyshev preconditioner (level 0) or of level `level` of an AMG
+ * (the estimate of the level's fp64 operator: the one that damps the prolongator; with cheb_value_bits = 32 the
+ * smoother's own estimate on fl32(A_l) is not reported).  With eig_type 0 -- or an explicit lambda_max -- it returns
+ * {rho, rho, 0}.  Collective for a hierarchy across ranks.  Any other preconditioner, or a level out of range, is an
+ * error. */
+int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double out[3]);
 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r /*[h|d]*/,
@@ -704,7 +728,9 @@ typedef struct {
    * polynomial of one level depends neither on the row order nor on the rank count (rho is all-reduced); the AMG result
    * as a whole still does, because the Uncoupled aggregates, and with them the cycle, follow the decomposition.  The
    * cycle is a fixed linear operator, symmetric for a symmetric matrix: "Block CG" may use it.  With a null vector the coarsest level is "solved" by the same polynomial.
-   * Departures from ML: lambda_max is the Anorm bound rho, not ML's 10 CG steps, and the 1.1 boost is kept on top. */
+   * Departures from ML: by default (eig_type 0) lambda_max is the Anorm bound rho, not ML's 10 CG steps; eig_type 1 gives
+   * ML's rule with Arnoldi in place of CG, a deterministic start vector and clipping by rho (see eig_type below and
+   * isph_cheb_params).  The 1.1 boost is kept on top either way. */
   int smoother;
   double cheb_ratio; /* smoother 2: "smoother: Chebyshev alpha", lambda_max / lambda_min of the interval; default 20 */
   /* smoother 2 only (not read otherwise): 64 (default; 0 means the same) or 32 = the polynomial of every level (the
@@ -714,6 +740,16 @@ typedef struct {
    * post-smoother then forms b - fl32(A) x in a sweep of its own (the A P shortcut holds the residual of A); on one rank
    * that takes back what the floats save: 29.4 against 29.9 ms per solve at 100^3, 26 iterations either way. */
   int cheb_value_bits;
+  /* "eigen-analysis: type" / "eigen-analysis: iterations".  eig_type 0 (default, "Anorm"): rho as above.  1 (ML's "cg"):
+   * EVERY level l uses lambda_l = min(lambda_est, rho) of its own operator (isph_cheb_params::eig_type; the start vector's
+   * counter carries the level, and on coarse levels the level's own row index plus the rank offset) for the prolongator
+   * damping omega / lambda_l, whatever the smoother, and for the Chebyshev interval [lambda_l / cheb_ratio, 1.1 lambda_l]
+   * of smoother 2.  With cheb_value_bits = 32 the damping uses the estimate of A_l (the hierarchy stays fp64) and the
+   * smoother the estimate of fl32(A_l).  eig_iters: 1..50, default 10.  isph_prec_eig_estimate reads the numbers back.
+   * "sa-amg" keeps eig_type 0.  Measured at 100^3 (profiles/eig_estimate_100cubed.txt; lambda 1.11 / 1.28 / 1.32 where rho is
+   * 2.00 / 2.23 / 2.10): smoother 2 of degree 2 needs 17 against 26 iterations, 33.1 against 38.4 ms for create plus solve
+   * (create 14.6 against 10.3 ms); smoother 0 needs 27 against 33 iterations, 41.6 against 43.1 ms. */
+  int eig_type, eig_iters;
 } isph_amg_params;
 void isph_amg_params_default(isph_amg_params *p);
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,
