@@ -16,6 +16,9 @@
 // isph_amg_params::smoother = 2 replaces the Gauss-Seidel sweeps by ML's "Chebyshev" ("MLS") smoother: a polynomial of
 // degree `sweeps` in D^-1 A with the same rho per level (chebyshev.hpp) -- no factor, no dense block inverses, not local
 // to blocks, a symmetric operator; the hierarchy is built by the same code whatever the smoother.
+// isph_amg_params::cycle_bits = 32 (smoother 2 only): the whole V cycle in single-precision STORAGE -- float planes of A_l, P_l,
+// P_l^T and A_l P_l, float level vectors, fp64 arithmetic with one rounding per stored element (amg_vcycle_t<float>,
+// include/isph_hip.h states the arithmetic); the hierarchy stays the fp64 one.  Not a linear operator: flexible GMRES only.
 // Set-up kernels work on device CSR copies, one wave per row (rows hold ~100 entries on the fine level); the
 // cycle itself uses the SELL SpMV and the chunk-stream triangular solves of the rest of the library.
 #pragma once
@@ -62,6 +65,10 @@ struct AmgLevel {
   Cheb *cheb = nullptr;      // isph_amg_params::smoother == 2: the Chebyshev polynomial of this level (chebyshev.hpp)
   DevBuf<int> agg;
   DevBuf<double> nv, x, b, r, z;
+  // isph_amg_params::cycle_bits == 32: the level vectors are float (x, b, r are then not reserved) and every operator the
+  // cycle applies has a float plane -- A~_l is cheb->val32; p32 = fl32 of Pm's values, ap32 = fl32 of APm's (position by
+  // position; APm's doubles go back to the pool), rv32 = fl32 of R.v = P~^T
+  DevBuf<float> x32, b32, r32, p32, ap32, rv32;
   // which branch of every ladder the set-up took on this level (isph_prec_amg_path): host integers, filled as it goes
   long long path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // isph_amg_params::eig_type == 1: the estimate of lambda_max(D^-1 A_l) of this level's fp64 operator (eig_estimate.hpp)
@@ -76,6 +83,7 @@ struct isph_amg {
   int nlev = 0, block = 512, sweeps = 1, singular = 0;
   int gs_eff = 0;         // isph_amg_params::smoother == 1: forward sweeps before, backward sweeps after the coarse correction
   int cheb_value_bits = 64;   // smoother == 2: 32 = every level's polynomial sweeps a float plane of its operator (chebyshev.hpp)
+  int cycle_bits = 64;        // smoother == 2: 32 = the whole V cycle in float storage (amg_vcycle_t<float>); sets cheb_value_bits 32
   int cheb = 0;           // isph_amg_params::smoother == 2: Chebyshev polynomial of degree `sweeps` in D^-1 A, before and after
   int eig_type = 0, eig_iters = 10;   // isph_amg_params: 1 = damping and Chebyshev intervals from the Arnoldi estimate of every level
   int coarse_smooth = 0;  // coarsest level solved by the smoother: singular system (precond_ml.h:97-127) or a level too
@@ -938,15 +946,17 @@ __global__ void k_rows_compact(int n, int cap_shift, const rp_t *__restrict__ rp
 }
 
 // y = R x for a CSR matrix with long rows: one wave per row, coalesced reads of the row, fixed-order wave sum
+// VT = XT = float (the cycle_bits = 32 V cycle): float values and vectors, widened; the sum is fp64 and rounded once
+template <class VT = double, class XT = double>
 __global__ __launch_bounds__(256) void k_csr_spmv_wave(int n, const rp_t *__restrict__ rp, const int *__restrict__ ci,
-                                                       const double *__restrict__ v, const double *__restrict__ x,
-                                                       double *__restrict__ y) {
+                                                       const VT *__restrict__ v, const XT *__restrict__ x,
+                                                       XT *__restrict__ y) {
   const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= n) return;
   double s = 0.0;
-  for (rp_t p = rp[i] + lane; p < rp[i + 1]; p += 64) s = fma(v[p], x[ci[p]], s);
+  for (rp_t p = rp[i] + lane; p < rp[i + 1]; p += 64) s = fma((double)v[p], (double)x[ci[p]], s);
   s = wave_sum(s);
-  if (lane == 0) y[i] = s;
+  if (lane == 0) y[i] = (XT)s;
 }
 
 constexpr int kAmgDenseMax = 2048;  // largest coarsest level the dense inverse is formed for
@@ -1034,14 +1044,16 @@ __global__ __launch_bounds__(256) void k_gj_finish(int n, double *__restrict__ a
   const double d = 1.0 / pv[k];
   for (int c = threadIdx.x; c < n; c += 256) aug[(size_t)k * w + c] = src[c] * d;
 }
-__global__ __launch_bounds__(256) void k_dense_apply(int n, const double *__restrict__ aug, const double *__restrict__ b,
-                                                     double *__restrict__ x) {
+// XT = float: the fp64 inverse applied to a float right-hand side, the fp64 sum rounded once into the float x
+template <class XT = double>
+__global__ __launch_bounds__(256) void k_dense_apply(int n, const double *__restrict__ aug, const XT *__restrict__ b,
+                                                     XT *__restrict__ x) {
   const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= n) return;
   double s = 0.0;
-  for (int c = lane; c < n; c += 64) s += aug[(size_t)i * 2 * n + c] * b[c];   // the inverse: left half (k_gj_finish)
+  for (int c = lane; c < n; c += 64) s += aug[(size_t)i * 2 * n + c] * (double)b[c];   // the inverse: left half (k_gj_finish)
   s = wave_sum(s);
-  if (lane == 0) x[i] = s;
+  if (lane == 0) x[i] = (XT)s;
 }
 
 // ---- the smoother of small coarse levels as dense block inverses ---------------------------------------------------
@@ -1329,6 +1341,7 @@ inline void amg_level_destroy(AmgLevel *L) {
   L->wsgs.release(); L->wfwd.release(); L->wbwd.release();
   if (L->cheb) cheb_destroy(L->cheb);
   L->agg.release(); L->nv.release(); L->x.release(); L->b.release(); L->r.release(); L->z.release();
+  L->x32.release(); L->b32.release(); L->r32.release(); L->p32.release(); L->ap32.release(); L->rv32.release();
   delete L;
 }
 
@@ -1735,14 +1748,16 @@ __global__ void k_amg_gid(int n, int off, const int *__restrict__ idx, double *_
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) out[k] = (double)(off + idx[k]);
 }
+// XT = float: b is still the all-reduced double right-hand side (doubles that hold floats), x the rank's float rows
+template <class XT = double>
 __global__ __launch_bounds__(256) void k_dense_apply_rows(int nloc, int N, int off, const double *__restrict__ aug,
-                                                          const double *__restrict__ b, double *__restrict__ x) {
+                                                          const double *__restrict__ b, XT *__restrict__ x) {
   const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= nloc) return;
   double s = 0.0;
   for (int c = lane; c < N; c += 64) s += aug[(size_t)(off + i) * 2 * N + c] * b[c];   // the inverse: left half (k_gj_finish)
   s = wave_sum(s);
-  if (lane == 0) x[i] = s;
+  if (lane == 0) x[i] = (XT)s;
 }
 
 // A rank that cannot coarsen any further while others still can (few rows, an empty rank) passes its level on unchanged:
@@ -1789,8 +1804,14 @@ inline int amg_dense_invert(isph_ctx *ctx, double *aug, int n, int *derr) {
   return ISPH_SUCCESS;   // (col / idx go back to the pool, which hands them out again only after a device synchronisation)
 }
 
-inline int amg_level_buffers(AmgLevel *L) {
+inline int amg_level_buffers(AmgLevel *L, bool f32 = false) {
   const size_t m = (size_t)(L->A.n > 0 ? L->A.n : 1) + 64;
+  if (f32) {   // the cycle_bits = 32 V cycle: float vectors from the pool, none of the double ones
+    ISPH_CHECK(L->x32.reserve(m));
+    ISPH_CHECK(L->b32.reserve(m));
+    ISPH_CHECK(L->r32.reserve(m));
+    return ISPH_SUCCESS;
+  }
   ISPH_CHECK(L->x.reserve(m));
   ISPH_CHECK(L->b.reserve(m));
   ISPH_CHECK(L->r.reserve(m));
@@ -1814,6 +1835,36 @@ inline int amg_level_estimate(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int
   return eig_estimate(ctx, L->Am, nullptr, dinv.p, rho, G->eig_iters, level, eig_unfused_env(), dist, &L->eig);
 }
 
+// isph_amg_params::cycle_bits == 32: every stored value of P_l, of R_l = P_l^T and of the A_l P_l the set-up kept, rounded
+// once into a float plane at the same position (k_cheby_round); a value beyond FLT_MAX fails the create call.  The fp64
+// values of the A P SELL are given back: the float cycle never reads them.
+inline int amg_float_planes(isph_ctx *ctx, isph_amg *G) {
+  DevTmp<unsigned long long> flag;
+  ISPH_CHECK(flag.reserve(3));
+  ISPH_CHECK_HIP(hipMemsetAsync(flag.p, 0, 3 * sizeof(unsigned long long), ctx->stream));
+  for (int l = 0; l + 1 < G->nlev; ++l) {
+    AmgLevel *L = G->L[(size_t)l];
+    const Sell &SP = L->Pm->S;
+    ISPH_CHECK(L->p32.reserve((size_t)(SP.stored > 0 ? SP.stored : 1)));
+    cheb_round_plane(ctx, SP.stored, (const double *)SP.val.p, L->p32.p, flag.p);
+    ISPH_CHECK(L->rv32.reserve((size_t)(L->R.nnz > 0 ? L->R.nnz : 1)));
+    cheb_round_plane(ctx, L->R.nnz, (const double *)L->R.v.p, L->rv32.p, flag.p);
+    if (L->APm) {
+      const Sell &SA = L->APm->S;
+      ISPH_CHECK(L->ap32.reserve((size_t)(SA.stored > 0 ? SA.stored : 1)));
+      cheb_round_plane(ctx, SA.stored, (const double *)SA.val.p, L->ap32.p, flag.p);
+    }
+  }
+  unsigned long long hb[3] = {0ull, 0ull, 0ull};
+  ISPH_CHECK_HIP(hipMemcpyAsync(hb, flag.p, sizeof(hb), hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  ISPH_REQUIRE(hb[2] == 0ull, "AMG: a value of P or A P exceeds the range of single precision (cycle_bits = 32 rounds the cycle's operators to float)");
+  for (int l = 0; l + 1 < G->nlev; ++l)
+    if (G->L[(size_t)l]->APm) G->L[(size_t)l]->APm->S.val.release();
+  return ISPH_SUCCESS;
+}
+
 inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
                       isph_amg **out) {
   ISPH_REQUIRE(prm->max_levels >= 1 && prm->max_levels <= 8, "max_levels must be in [1,8]");
@@ -1826,12 +1877,18 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_ratio > 1.0, "Chebyshev smoother: cheb_ratio (\"smoother: Chebyshev alpha\") must be > 1");
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_value_bits == 0 || prm->cheb_value_bits == 64 || prm->cheb_value_bits == 32,
                "Chebyshev smoother: cheb_value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
+  ISPH_REQUIRE(prm->cycle_bits == 0 || prm->cycle_bits == 64 || prm->cycle_bits == 32,
+               "cycle_bits must be 64 (or 0: the fp64 V cycle) or 32 (the V cycle in single-precision storage)");
+  ISPH_REQUIRE(prm->cycle_bits != 32 || prm->smoother == 2,
+               "cycle_bits = 32 needs the Chebyshev smoother (smoother 2): the Gauss-Seidel smoothers keep fp64 vectors");
   ISPH_REQUIRE(prm->eig_type == 0 || prm->eig_type == 1,
                "eig_type must be 0 (the bound rho = ||D^-1 A||_inf, \"Anorm\") or 1 (the Arnoldi estimate, ML's \"cg\")");
   ISPH_REQUIRE(prm->eig_iters >= 1 && prm->eig_iters <= kEigMaxIters, "eig_iters (\"eigen-analysis: iterations\") must be in [1,50]");
   isph_amg *G = new isph_amg();
   G->eig_type = prm->eig_type; G->eig_iters = prm->eig_iters;
-  G->cheb_value_bits = (prm->smoother == 2 && prm->cheb_value_bits == 32) ? 32 : 64;
+  G->cycle_bits = (prm->smoother == 2 && prm->cycle_bits == 32) ? 32 : 64;
+  // (cycle_bits 32: the float plane of every level operator is the one cheb_value_bits 32 makes, whatever that field says)
+  G->cheb_value_bits = (prm->smoother == 2 && (prm->cheb_value_bits == 32 || G->cycle_bits == 32)) ? 32 : 64;
   G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
   G->gs_eff = prm->smoother == 1;
   G->cheb = prm->smoother == 2;
@@ -1958,7 +2015,8 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     // (a fifth of A's entries) instead of a second sweep over A
     // (not on a rank that sends to neighbours: the product it saves is also this rank's part of their exchange)
     // (not with cheb_value_bits 32 either: the post-smoother is the polynomial of fl32(A) and forms b - fl32(A) x itself)
-    if (rc == ISPH_SUCCESS && G->cheb_value_bits != 32 &&
+    // (cycle_bits 32 keeps it: every operator of that cycle is a float plane, fl32(A P) among them)
+    if (rc == ISPH_SUCCESS && (G->cheb_value_bits != 32 || G->cycle_bits == 32) &&
         ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
       rc = mat_from_device_csr(ctx, AP.n, AP.m, AP.rp.p, AP.ci.p, AP.v.p, AP.nnz, &L->APm, /*rows_sorted=*/true);
       if (rc == ISPH_SUCCESS) L->APm->local = true;
@@ -2004,7 +2062,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   const bool walk = dist && G->cheb && rc == ISPH_SUCCESS;
   for (int l = 0; l < G->nlev && (rc == ISPH_SUCCESS || walk); ++l) {
     AmgLevel *L = G->L[(size_t)l];
-    if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L);
+    if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L, G->cycle_bits == 32);
     const bool last = l == G->nlev - 1;
     if (last) L->path[AMG_PATH_COARSE] = G->coarse_smooth ? 2 : 1;
     if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
@@ -2015,7 +2073,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
         const bool reuse = G->eig_type == 1 && G->cheb_value_bits != 32;
         const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, reuse ? L->eig.lambda_used : 0.0, 0.0, /*empty_ok=*/l > 0,
                                   /*collective=*/dist, /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits,
-                                  reuse ? 0 : G->eig_type, G->eig_iters, l);
+                                  reuse ? 0 : G->eig_type, G->eig_iters, l, G->cycle_bits);
         if (rc == ISPH_SUCCESS) rc = r2;
       }
       continue;
@@ -2044,6 +2102,8 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       }
     }
   }
+  // cycle_bits 32: the float planes of P, P^T and A P (A_l's is the smoother's); rank-local, agreed on just below
+  if (rc == ISPH_SUCCESS && G->cycle_bits == 32) rc = amg_float_planes(ctx, G);
   if (dist) {   // the smoothers are built per rank: a failure there must keep every rank out of the collective steps below
     double h = rc == ISPH_SUCCESS ? 0.0 : 1.0;
     if (comm_host_allreduce(ctx, &h, 1, 1) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
@@ -2119,67 +2179,137 @@ inline int amg_smooth(isph_ctx *ctx, const isph_amg *G, int l, const double *b, 
   return amg_sgs_apply(ctx, L, L->r.p, x, true, part);
 }
 
-inline int amg_vcycle(isph_ctx *ctx, const isph_amg *G, int l, const double *b, double *x) {
+// ---- the operators of the cycle by vector type: double = the fp64 cycle, float = isph_amg_params::cycle_bits 32, where
+// every operator is its float plane, every vector a float one, all arithmetic fp64 and every stored element rounded once
+template <class T> struct AmgVecs;
+template <> struct AmgVecs<double> {
+  static double *x(AmgLevel *L) { return L->x.p; }
+  static double *b(AmgLevel *L) { return L->b.p; }
+  static double *r(AmgLevel *L) { return L->r.p; }
+};
+template <> struct AmgVecs<float> {
+  static float *x(AmgLevel *L) { return L->x32.p; }
+  static float *b(AmgLevel *L) { return L->b32.p; }
+  static float *r(AmgLevel *L) { return L->r32.p; }
+};
+// r = b - A x
+inline int amg_residual(isph_ctx *ctx, AmgLevel *L, const double *x, double *r, const double *b) {
+  return spmv_dev(ctx, L->Am, x, r, nullptr, b, -1.0);
+}
+inline int amg_residual(isph_ctx *ctx, AmgLevel *L, const float *x, float *r, const float *b) {
+  return spmv_dev_f32<float>(ctx, L->Am, (const float *)L->cheb->val32.p, x, r, b, -1.0);
+}
+// bc = R r
+inline void amg_restrict(isph_ctx *ctx, AmgLevel *L, const double *r, double *bc) {
+  hipLaunchKernelGGL((k_csr_spmv_wave<double, double>), dim3(amg_wave_grid(L->R.n)), dim3(256), 0, ctx->stream, L->R.n, (const rp_t *)L->R.rp.p,
+                     (const int *)L->R.ci.p, (const double *)L->R.v.p, r, bc);
+}
+inline void amg_restrict(isph_ctx *ctx, AmgLevel *L, const float *r, float *bc) {
+  hipLaunchKernelGGL((k_csr_spmv_wave<float, float>), dim3(amg_wave_grid(L->R.n)), dim3(256), 0, ctx->stream, L->R.n, (const rp_t *)L->R.rp.p,
+                     (const int *)L->R.ci.p, (const float *)L->rv32.p, r, bc);
+}
+// x += P e
+inline int amg_prolong(isph_ctx *ctx, AmgLevel *L, const double *e, double *x) { return spmv_dev(ctx, L->Pm, e, x, nullptr, x, 1.0); }
+inline int amg_prolong(isph_ctx *ctx, AmgLevel *L, const float *e, float *x) {
+  return spmv_dev_f32<float>(ctx, L->Pm, (const float *)L->p32.p, e, x, x, 1.0);
+}
+// r -= (A P) e
+inline int amg_residual_update(isph_ctx *ctx, AmgLevel *L, const double *e, double *r) { return spmv_dev(ctx, L->APm, e, r, nullptr, r, -1.0); }
+inline int amg_residual_update(isph_ctx *ctx, AmgLevel *L, const float *e, float *r) {
+  return spmv_dev_f32<float>(ctx, L->APm, (const float *)L->ap32.p, e, r, r, -1.0);
+}
+// the coarsest right-hand side of this rank into its rows of bglob (float: widened, the all-reduce stays fp64)
+inline int amg_coarse_rhs(isph_ctx *ctx, const isph_amg *G, int n, const double *b) {
+  ISPH_CHECK_HIP(hipMemcpyAsync(G->bglob.p + G->nc_off, b, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+  return ISPH_SUCCESS;
+}
+inline int amg_coarse_rhs(isph_ctx *ctx, const isph_amg *G, int n, const float *b) {
+  hipLaunchKernelGGL(k_cheby_widen, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, b, G->bglob.p + G->nc_off);
+  return ISPH_SUCCESS;
+}
+
+// The V cycle, stated once for both vector types.  T = float never meets the Gauss-Seidel branches (amg_create refuses
+// cycle_bits 32 without the Chebyshev smoother).
+template <class T>
+inline int amg_vcycle_t(isph_ctx *ctx, const isph_amg *G, int l, const T *b, T *x) {
+  constexpr bool fp64 = std::is_same<T, double>::value;
   AmgLevel *L = G->L[(size_t)l];
   const int n = L->A.n;
   if (l == G->nlev - 1) {
     if (G->coarse_smooth && G->cheb) {
       ISPH_CHECK(cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/true));   // the level is "solved" by the same polynomial
     } else if (G->coarse_smooth) {
-      ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true));
-      for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false));
+      if constexpr (fp64) {
+        ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true));
+        for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false));
+      }
     } else if (G->dist && G->nlev > 1) {
       // the right-hand side of all ranks, then this rank's rows of the inverse
       const int N = G->nc;
       if (N > 0) {
         ISPH_CHECK_HIP(hipMemsetAsync(G->bglob.p, 0, sizeof(double) * (size_t)N, ctx->stream));
-        if (n > 0) ISPH_CHECK_HIP(hipMemcpyAsync(G->bglob.p + G->nc_off, b, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+        if (n > 0) ISPH_CHECK(amg_coarse_rhs(ctx, G, n, b));
         ISPH_CHECK(comm_allreduce(ctx, G->bglob.p, N, 0, ctx->stream));
         if (n > 0)
-          hipLaunchKernelGGL(k_dense_apply_rows, dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, N, G->nc_off, (const double *)G->cinv.p,
+          hipLaunchKernelGGL((k_dense_apply_rows<T>), dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, N, G->nc_off, (const double *)G->cinv.p,
                              (const double *)G->bglob.p, x);
       }
     } else if (n > 0) {
-      hipLaunchKernelGGL(k_dense_apply, dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, (const double *)G->cinv.p, b, x);
+      hipLaunchKernelGGL((k_dense_apply<T>), dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, (const double *)G->cinv.p, b, x);
     }
     return ISPH_SUCCESS;
   }
   AmgLevel *Lc = G->L[(size_t)l + 1];
+  T *r = AmgVecs<T>::r(L), *bc = AmgVecs<T>::b(Lc), *xc = AmgVecs<T>::x(Lc);
   const int pre = G->gs_eff ? 1 : 0, post = G->gs_eff ? 2 : 0;
   if (G->cheb) {
     ISPH_CHECK(cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/true));
-  } else {
+  } else if constexpr (fp64) {
     ISPH_CHECK(amg_smooth(ctx, G, l, b, x, true, pre));
     for (int s = 1; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false, pre));
   }
-  ISPH_CHECK(spmv_dev(ctx, L->Am, x, L->r.p, nullptr, b, -1.0));   // r = b - A x
+  ISPH_CHECK(amg_residual(ctx, L, x, r, b));   // r = b - A x
   if (L->R.n > 0)   // (a rank without rows still walks the cycle: its neighbours' exchanges and the all-reduces count on it)
-    hipLaunchKernelGGL(k_csr_spmv_wave, dim3(amg_wave_grid(L->R.n)), dim3(256), 0, ctx->stream, L->R.n, (const rp_t *)L->R.rp.p,
-                       (const int *)L->R.ci.p, (const double *)L->R.v.p, (const double *)L->r.p, Lc->b.p);
-  ISPH_CHECK(amg_vcycle(ctx, G, l + 1, Lc->b.p, Lc->x.p));
-  ISPH_CHECK(spmv_dev(ctx, L->Pm, Lc->x.p, x, nullptr, x, 1.0));   // x += P e
-  int first = 0;
+    amg_restrict(ctx, L, r, bc);
+  ISPH_CHECK(amg_vcycle_t<T>(ctx, G, l + 1, bc, xc));
+  ISPH_CHECK(amg_prolong(ctx, L, xc, x));   // x += P e
   if (G->cheb) {
     // r still holds b - A x of before the correction: r -= (A P) e is the residual the polynomial's first step needs
     // (cheb_value_bits 32: that residual is the one of A, and the smoother is the polynomial of fl32(A) -- its first step
-    // forms b - fl32(A) x itself, one more sweep of the float plane, or the cycle would be neither operator)
-    const bool shortcut = L->APm != nullptr && G->cheb_value_bits != 32;
-    if (shortcut) ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));
-    return cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/false, shortcut ? (const double *)L->r.p : nullptr);
+    // forms b - fl32(A) x itself, one more sweep of the float plane, or the cycle would be neither operator; cycle_bits 32
+    // has the shortcut back: its residual and its A P are float planes like the smoother's operator)
+    const bool shortcut = L->APm != nullptr && (G->cheb_value_bits != 32 || G->cycle_bits == 32);
+    if (shortcut) ISPH_CHECK(amg_residual_update(ctx, L, xc, r));
+    return cheb_apply(ctx, L->Am, L->cheb, b, x, /*zero_guess=*/false, shortcut ? (const T *)r : (const T *)nullptr);
   }
-  if (L->APm) {
-    // r still holds b - A x of before the correction: r -= (A P) e, then the first post-smoothing sweep uses it
-    ISPH_CHECK(spmv_dev(ctx, L->APm, Lc->x.p, L->r.p, nullptr, L->r.p, -1.0));
-    ISPH_CHECK(amg_sgs_apply(ctx, L, L->r.p, x, true, post));
-    first = 1;
+  if constexpr (fp64) {
+    int first = 0;
+    if (L->APm) {
+      // r still holds b - A x of before the correction: r -= (A P) e, then the first post-smoothing sweep uses it
+      ISPH_CHECK(amg_residual_update(ctx, L, xc, r));
+      ISPH_CHECK(amg_sgs_apply(ctx, L, r, x, true, post));
+      first = 1;
+    }
+    for (int s = first; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false, post));
   }
-  for (int s = first; s < G->sweeps; ++s) ISPH_CHECK(amg_smooth(ctx, G, l, b, x, false, post));
   return ISPH_SUCCESS;
 }
 
+// z = the cycle applied to r.  cycle_bits 32: b_0 = fl32(r) on the way in, z = the float result widened on the way out.
 inline int amg_apply(isph_ctx *ctx, const isph_amg *G, const double *r, double *z) {
   ISPH_REQUIRE(G != nullptr, "AMG hierarchy is NULL");
-  ISPH_CHECK(amg_vcycle(ctx, G, 0, r, z));
+  if (G->cycle_bits == 32) {
+    AmgLevel *L0 = G->L[0];
+    const int n = L0->Am->S.nrow;
+    if (n > 0)
+      hipLaunchKernelGGL(k_cheby_narrow, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, r, L0->b32.p,
+                         (unsigned long long *)nullptr);
+    ISPH_CHECK(amg_vcycle_t<float>(ctx, G, 0, (const float *)L0->b32.p, L0->x32.p));
+    if (n > 0)
+      hipLaunchKernelGGL(k_cheby_widen, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, (const float *)L0->x32.p, z);
+  } else {
+    ISPH_CHECK(amg_vcycle_t<double>(ctx, G, 0, r, z));
+  }
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }

@@ -24,8 +24,14 @@
 // entry, convert to double and run the fma chain of the double kernel in the same order.  Vectors, accumulators and
 // the update stay double: the result is the fp64 recurrence on A~, a fixed linear operator like the one on A.
 // 100^3: 147.8 against 207.1 us per step for 0.62 of the bytes -- no longer HBM-bound.
+//
+// vec_bits = 32 (the smoother of the cycle_bits = 32 V cycle of amg.hpp; implies value_bits 32): the vectors are float too --
+// y, b, w and D^-1 = fl32(1 / a~_ii).  Every kernel widens its operands, does the arithmetic of the double kernel in fp64
+// (a product of two floats is exact there) and rounds once per stored element: w = fl32(wn), yout = fl32(y + wn) with the
+// unrounded increment wn.  The gather of y is a 4-byte load; ghost values arrive as doubles that hold floats.
 #pragma once
 #include <cfloat>
+#include <type_traits>
 #include "eig_estimate.hpp"
 #include "solver.hpp"
 
@@ -35,18 +41,34 @@ constexpr int kChebMaxDegree = 16;
 
 struct Cheb {
   int n = 0, degree = 1, unfused = 0, value_bits = 64;
+  int vec_bits = 64;                                 // 32: float vectors (dinv32, w32, t32); dinv, w, t are then not kept
   double lambda = 0.0, alpha = 0.0, beta = 0.0;
   double rho = 0.0;                                  // ||D^-1 A||_inf (all-reduced), whatever lambda came from
   int eig_type = 0, eig_steps = 0;                   // eig_type 1: lambda = min(Arnoldi estimate, rho) after eig_steps steps
   double c1[kChebMaxDegree], c2[kChebMaxDegree];   // step k (0-based): w = c1[k] w + c2[k] D^-1 (b - A y)
   DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
   DevBuf<float> val32;                               // value_bits 32: fl32 of S.val, position by position (padding 0)
+  DevBuf<float> dinv32, w32, t32;                    // vec_bits 32: fl32(1 / a~_ii), the increment, the second y
+};
+
+// the vectors of the polynomial by their type
+template <class XT> struct ChebVecs;
+template <> struct ChebVecs<double> {
+  static const double *dinv(const Cheb *C) { return C->dinv.p; }
+  static double *w(const Cheb *C) { return C->w.p; }
+  static double *t(const Cheb *C) { return C->t.p; }
+};
+template <> struct ChebVecs<float> {
+  static const float *dinv(const Cheb *C) { return C->dinv32.p; }
+  static float *w(const Cheb *C) { return C->w32.p; }
+  static float *t(const Cheb *C) { return C->t32.p; }
 };
 
 
 inline void cheb_destroy(Cheb *C) {
   if (!C) return;
   C->dinv.release(); C->w.release(); C->t.release(); C->r.release(); C->val32.release();
+  C->dinv32.release(); C->w32.release(); C->t32.release();
   delete C;
 }
 
@@ -138,14 +160,17 @@ __global__ __launch_bounds__(kBlock) void k_cheby_setup(int nrow, int nslices, c
 // XCD remap; then  w_i = c1 w_i + c2 dinv_i (b_i - (A y)_i),  yout_i = y_i + w_i.
 // yout must NOT alias y: other waves still gather y.  c1 == 0 (first step): w is not read.
 // VT = float: sval is the float plane (64 x float2 = 512 B per wave load), each value widened before its fma.
-template <bool C16, bool LIST, bool GHOST, class VT>
+// XT = float (with VT = float): y, b, dinv, w and yout are float vectors, the ghost values yg doubles that hold floats.  The
+// gather is a 4-byte load, the fma chain and the update are the fp64 ones, and w and yout are rounded once each in the
+// store -- yout from y + wn with the unrounded increment.
+template <bool C16, bool LIST, bool GHOST, class VT, class XT = double>
 __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslices, int nblocks_padded,
                                                             const long long *__restrict__ slice_off,
                                                             const void *__restrict__ cols, const int *__restrict__ wtab,
-                                                            const VT *__restrict__ sval, const double *__restrict__ y,
-                                                            const double *__restrict__ yg, const double *__restrict__ b,
-                                                            const double *__restrict__ dinv, double *__restrict__ w,
-                                                            double *__restrict__ yout, double c1, double c2,
+                                                            const VT *__restrict__ sval, const XT *__restrict__ y,
+                                                            const double *__restrict__ yg, const XT *__restrict__ b,
+                                                            const XT *__restrict__ dinv, XT *__restrict__ w,
+                                                            XT *__restrict__ yout, double c1, double c2,
                                                             const int *__restrict__ slice_list) {
   constexpr int UNROLL = 8;
   typedef typename SellPair<VT>::type VT2;
@@ -219,10 +244,10 @@ __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslice
   }
   const int row = slice * kSlice + lane;
   if (row < nrow) {
-    const double r = b[row] - (acc0 + acc1);
-    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? w[row] : 0.0, dinv[row], r);
-    w[row] = wn;
-    yout[row] = y[row] + wn;
+    const double r = (double)b[row] - (acc0 + acc1);
+    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? (double)w[row] : 0.0, (double)dinv[row], r);
+    w[row] = (XT)wn;
+    yout[row] = (XT)((double)y[row] + wn);
   }
 }
 
@@ -264,15 +289,87 @@ __global__ __launch_bounds__(kBlock) void k_cheby_first(int n, double c2, const 
   }
 }
 
-// ISPH_CHEB_UNFUSED=1: the update behind a separate r = b - A y
-__global__ __launch_bounds__(kBlock) void k_cheby_update(int n, double c1, double c2, const double *__restrict__ dinv,
-                                                         const double *__restrict__ r, double *__restrict__ w,
-                                                         const double *yin, double *yout) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? w[i] : 0.0, dinv[i], r[i]);
-    w[i] = wn;
-    yout[i] = yin[i] + wn;
+// ... of float vectors (vec_bits 32): the same step with every operand widened, fp64 arithmetic, w and yout rounded once.
+// VEC: 16-byte loads and stores carry 4 floats per lane; the up to 3 elements behind the last quad go one by one.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void k_cheby_first_f32(int n, double c2, const float *__restrict__ dinv,
+                                                            const float *__restrict__ r, const float *yin,
+                                                            float *__restrict__ w, float *yout) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (VEC) {
+    const long long n4 = n >> 2;
+    const float4 *d4 = reinterpret_cast<const float4 *>(dinv), *r4 = reinterpret_cast<const float4 *>(r);
+    const float4 *y4 = reinterpret_cast<const float4 *>(yin);
+    float4 *w4 = reinterpret_cast<float4 *>(w), *o4 = reinterpret_cast<float4 *>(yout);
+    for (long long i = t0; i < n4; i += stride) {
+      const float4 d = d4[i], rr = r4[i];
+      const double wx = cheb_increment(0.0, c2, 0.0, (double)d.x, (double)rr.x);
+      const double wy = cheb_increment(0.0, c2, 0.0, (double)d.y, (double)rr.y);
+      const double wz = cheb_increment(0.0, c2, 0.0, (double)d.z, (double)rr.z);
+      const double ww = cheb_increment(0.0, c2, 0.0, (double)d.w, (double)rr.w);
+      float4 wn, yo;
+      wn.x = (float)wx; wn.y = (float)wy; wn.z = (float)wz; wn.w = (float)ww;
+      yo = wn;
+      if (yin) {
+        const float4 yy = y4[i];
+        yo.x = (float)((double)yy.x + wx); yo.y = (float)((double)yy.y + wy);
+        yo.z = (float)((double)yy.z + wz); yo.w = (float)((double)yy.w + ww);
+      }
+      w4[i] = wn;
+      o4[i] = yo;
+    }
+    const int i = (n & ~3) + (int)t0;
+    if (t0 < 3 && i < n) {
+      const double wn = cheb_increment(0.0, c2, 0.0, (double)dinv[i], (double)r[i]);
+      w[i] = (float)wn;
+      yout[i] = yin ? (float)((double)yin[i] + wn) : (float)wn;
+    }
+  } else {
+    for (long long i = t0; i < n; i += stride) {
+      const double wn = cheb_increment(0.0, c2, 0.0, (double)dinv[i], (double)r[i]);
+      w[i] = (float)wn;
+      yout[i] = yin ? (float)((double)yin[i] + wn) : (float)wn;
+    }
   }
+}
+
+// ISPH_CHEB_UNFUSED=1: the update behind a separate r = b - A y (r is a double vector for either XT: the product's
+// residual is not rounded on its way here, as it is not inside the fused step)
+template <class XT = double>
+__global__ __launch_bounds__(kBlock) void k_cheby_update(int n, double c1, double c2, const XT *__restrict__ dinv,
+                                                         const double *__restrict__ r, XT *__restrict__ w,
+                                                         const XT *yin, XT *yout) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const double wn = cheb_increment(c1, c2, c1 != 0.0 ? (double)w[i] : 0.0, (double)dinv[i], r[i]);
+    w[i] = (XT)wn;
+    yout[i] = (XT)((double)yin[i] + wn);
+  }
+}
+
+// float vectors in and out of the fp64 world: out = fl32(in) (round to nearest even; the residual that enters the
+// cycle_bits = 32 V cycle, the float D^-1; flag != NULL: flag[2] = 1 when a magnitude exceeds FLT_MAX) and out = in widened
+// (the cycle's result, the coarsest right-hand side of several ranks)
+__global__ __launch_bounds__(kBlock) void k_cheby_narrow(long long n, const double *__restrict__ in, float *__restrict__ out,
+                                                         unsigned long long *__restrict__ flag) {
+  bool over = false;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const double v = in[i];
+    over = over || fabs(v) > (double)FLT_MAX;
+    out[i] = (float)v;
+  }
+  if (flag != nullptr && over) atomicMax(&flag[2], 1ull);
+}
+__global__ __launch_bounds__(kBlock) void k_cheby_widen(long long n, const float *__restrict__ in, double *__restrict__ out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    out[i] = (double)in[i];
+}
+
+// the float plane of `count` doubles (count even: k_cheby_round, a pair per trip; an odd last element: k_cheby_narrow)
+inline void cheb_round_plane(isph_ctx *ctx, long long count, const double *val, float *v32, unsigned long long *flag) {
+  if (count >= 2)
+    hipLaunchKernelGGL(k_cheby_round, dim3(stream_grid(count / 2)), dim3(kBlock), 0, ctx->stream, count / 2, val, v32, flag);
+  if (count & 1)
+    hipLaunchKernelGGL(k_cheby_narrow, dim3(1), dim3(kBlock), 0, ctx->stream, 1LL, val + (count - 1), v32 + (count - 1), flag);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
@@ -301,16 +398,20 @@ inline int cheb_diag_rho(isph_ctx *ctx, const isph_mat *A, DevBuf<double> &dinv,
 // value_bits: 64, or 32 = the polynomial of fl32(A) (the caller has checked the value).
 // eig_type 1 (with lambda_max <= 0): lambda is the clipped Arnoldi estimate of eig_estimate.hpp after eig_iters steps on
 // the operator the sweeps apply (the float plane with value_bits 32), start vector of `eig_level`; collective like rho.
+// vec_bits 32 (takes value_bits 32 with it): float vectors.  The plane, rho, the estimate and the scalars are those of
+// value_bits 32; then D^-1 is rounded into dinv32 (a quotient beyond FLT_MAX fails like a value beyond it) and the double
+// one goes back to the pool.  w, t of the double polynomial are never reserved.
 inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio, double lambda_max, double lambda_min,
                       bool empty_ok, bool collective, bool prior_failure, Cheb **out, int value_bits = 64, int eig_type = 0,
-                      int eig_iters = 10, int eig_level = 0) {
+                      int eig_iters = 10, int eig_level = 0, int vec_bits = 64) {
   const Sell &S = A->S;
   int rc = ISPH_SUCCESS;
   Cheb *C = new Cheb();
   C->n = S.nrow;
   C->degree = degree;
-  C->value_bits = value_bits == 32 ? 32 : 64;
-  const bool f32 = C->value_bits == 32;
+  C->vec_bits = vec_bits == 32 ? 32 : 64;
+  C->value_bits = (value_bits == 32 || C->vec_bits == 32) ? 32 : 64;
+  const bool f32 = C->value_bits == 32, v32 = C->vec_bits == 32;
   const char *env = getenv("ISPH_CHEB_UNFUSED");
   C->unfused = env && env[0] == '1';
   DevTmp<unsigned long long> flag;
@@ -320,8 +421,11 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
     rc = flag.reserve(3);
     if (rc == ISPH_SUCCESS) rc = C->dinv.reserve(m);
     if (rc == ISPH_SUCCESS && f32) rc = C->val32.reserve((size_t)(S.stored > 0 ? S.stored : 1));
-    if (rc == ISPH_SUCCESS) rc = C->w.reserve(m);
-    if (rc == ISPH_SUCCESS) rc = C->t.reserve(m);
+    if (rc == ISPH_SUCCESS && !v32) rc = C->w.reserve(m);
+    if (rc == ISPH_SUCCESS && !v32) rc = C->t.reserve(m);
+    if (rc == ISPH_SUCCESS && v32) rc = C->dinv32.reserve(m);
+    if (rc == ISPH_SUCCESS && v32) rc = C->w32.reserve(m);
+    if (rc == ISPH_SUCCESS && v32) rc = C->t32.reserve(m);
     if (rc == ISPH_SUCCESS && C->unfused) rc = C->r.reserve(m);
     if (rc == ISPH_SUCCESS && hipMemsetAsync(flag.p, 0, 3 * sizeof(unsigned long long), ctx->stream) != hipSuccess)
       rc = fail("memset failed", __FILE__, __LINE__);
@@ -370,61 +474,90 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
   C->alpha = lambda_min > 0.0 ? lambda_min : C->lambda / ratio;
   if (!(C->alpha < C->beta)) { cheb_destroy(C); return fail("Chebyshev: lambda_min must be below 1.1 lambda_max", __FILE__, __LINE__); }
   cheb_coefficients(C);
+  if (v32) {   // (rank-local and after the last collective step: a failure here is agreed on by the caller's own consensus)
+    unsigned long long hb[3] = {0ull, 0ull, 0ull};
+    if (hipMemsetAsync(flag.p, 0, 3 * sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
+    if (rc == ISPH_SUCCESS && S.nrow > 0)
+      hipLaunchKernelGGL(k_cheby_narrow, dim3(stream_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, (long long)S.nrow,
+                         (const double *)C->dinv.p, C->dinv32.p, flag.p);
+    if (rc == ISPH_SUCCESS && (hipMemcpyAsync(hb, flag.p, sizeof(hb), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+                               hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess))
+      rc = fail("Chebyshev set-up failed", __FILE__, __LINE__);
+    if (rc == ISPH_SUCCESS && hb[2] != 0ull)
+      rc = fail("Chebyshev: the inverse of a diagonal entry exceeds the range of single precision (cycle_bits = 32 stores D^-1 as float)", __FILE__, __LINE__);
+    if (rc != ISPH_SUCCESS) { cheb_destroy(C); return rc; }
+    C->dinv.release();
+  }
   *out = C;
   return ISPH_SUCCESS;
 }
 
-template <bool LIST, bool GHOST, class VT>
+template <bool LIST, bool GHOST, class VT, class XT>
 inline void cheb_step_launch(isph_ctx *ctx, const Sell &S, bool c16, int nsl, const int *list, const Cheb *C, const VT *val,
-                             const double *b, const double *y, const double *yg, double *yout, double c1, double c2) {
+                             const XT *b, const XT *y, const double *yg, XT *yout, double c1, double c2) {
   if (nsl <= 0) return;
   int nbp = 0;
   const int grid = spmv_grid(nsl, &nbp);
   if (c16)
-    hipLaunchKernelGGL((k_sell_cheby_step<true, LIST, GHOST, VT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+    hipLaunchKernelGGL((k_sell_cheby_step<true, LIST, GHOST, VT, XT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
                        (const long long *)S.slice_off.p, (const void *)S.col16.p, (const int *)S.wtab.p, val, y, yg,
-                       b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
+                       b, ChebVecs<XT>::dinv(C), ChebVecs<XT>::w(C), yout, c1, c2, list);
   else
-    hipLaunchKernelGGL((k_sell_cheby_step<false, LIST, GHOST, VT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+    hipLaunchKernelGGL((k_sell_cheby_step<false, LIST, GHOST, VT, XT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
                        (const long long *)S.slice_off.p, (const void *)S.col.p, (const int *)nullptr, val, y, yg,
-                       b, (const double *)C->dinv.p, C->w.p, yout, c1, c2, list);
+                       b, ChebVecs<XT>::dinv(C), ChebVecs<XT>::w(C), yout, c1, c2, list);
 }
 
 // the fused sweep over the double values of the matrix or over the float plane of the preconditioner
-template <class VT>
-inline int cheb_step_fused(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const VT *val, bool halo, bool c16, const double *b,
-                           const double *y, double *yout, double c1, double c2) {
+template <class VT, class XT>
+inline int cheb_step_fused(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const VT *val, bool halo, bool c16, const XT *b,
+                           const XT *y, XT *yout, double c1, double c2) {
   const Sell &S = A->S;
   if (!halo) {
-    cheb_step_launch<false, false, VT>(ctx, S, c16, S.nslices, nullptr, C, val, b, y, nullptr, yout, c1, c2);
+    cheb_step_launch<false, false, VT, XT>(ctx, S, c16, S.nslices, nullptr, C, val, b, y, nullptr, yout, c1, c2);
   } else {
     const isph_halo &H = A->halo;
     ISPH_CHECK(halo_begin(ctx, A, y));
-    cheb_step_launch<true, false, VT>(ctx, S, c16, H.n_int, H.list_int.p, C, val, b, y, nullptr, yout, c1, c2);
+    cheb_step_launch<true, false, VT, XT>(ctx, S, c16, H.n_int, H.list_int.p, C, val, b, y, nullptr, yout, c1, c2);
     ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
-    cheb_step_launch<true, true, VT>(ctx, S, c16, H.n_bnd, H.list_bnd.p, C, val, b, y, ctx->xghost.p, yout, c1, c2);
+    cheb_step_launch<true, true, VT, XT>(ctx, S, c16, H.n_bnd, H.list_bnd.p, C, val, b, y, ctx->xghost.p, yout, c1, c2);
   }
   return ISPH_SUCCESS;
 }
 
+// r = b - A y of the unfused step, a double vector whatever the vectors are (float vectors: the product of the float plane
+// with the float y, the fp64 row sum subtracted from the widened b and stored unrounded)
+inline int cheb_unfused_residual(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const double *b, const double *y) {
+  return spmv_dev(ctx, A, y, C->r.p, nullptr, b, -1.0, C->value_bits == 32 ? (const float *)C->val32.p : nullptr);
+}
+inline int cheb_unfused_residual(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const float *b, const float *y) {
+  return spmv_dev_f32<double>(ctx, A, (const float *)C->val32.p, y, C->r.p, b, -1.0);
+}
+
 // one step with a matrix product: yout = y + w, w = c1 w + c2 D^-1 (b - A y); yout != y.  With a halo plan the exchange
-// of y overlaps the interior slices exactly as in spmv_dev.
-inline int cheb_step(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const double *b, const double *y, double *yout, double c1,
+// of y overlaps the interior slices exactly as in spmv_dev.  XT = float: the polynomial of float vectors (vec_bits 32).
+template <class XT>
+inline int cheb_step(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const XT *b, const XT *y, XT *yout, double c1,
                      double c2) {
   const Sell &S = A->S;
+  constexpr bool v32 = std::is_same<XT, float>::value;
   if (C->unfused) {
     // r = b - A y (value_bits 32: the product reads the float plane)
-    ISPH_CHECK(spmv_dev(ctx, A, y, C->r.p, nullptr, b, -1.0, C->value_bits == 32 ? (const float *)C->val32.p : nullptr));
-    hipLaunchKernelGGL(k_cheby_update, dim3(stream_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, S.nrow, c1, c2,
-                       (const double *)C->dinv.p, (const double *)C->r.p, C->w.p, y, yout);
+    ISPH_CHECK(cheb_unfused_residual(ctx, A, C, b, y));
+    hipLaunchKernelGGL((k_cheby_update<XT>), dim3(stream_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, S.nrow, c1, c2,
+                       ChebVecs<XT>::dinv(C), (const double *)C->r.p, ChebVecs<XT>::w(C), y, yout);
     ISPH_CHECK_HIP(hipGetLastError());
     return ISPH_SUCCESS;
   }
   ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);   // a sweep of the caller's operator, like spmv_dev's
   const bool halo = !A->local && (S.ncol != S.nrow || A->halo.nsend > 0);
   const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
-  if (C->value_bits == 32) ISPH_CHECK(cheb_step_fused<float>(ctx, A, C, (const float *)C->val32.p, halo, c16, b, y, yout, c1, c2));
-  else ISPH_CHECK(cheb_step_fused<double>(ctx, A, C, (const double *)S.val.p, halo, c16, b, y, yout, c1, c2));
+  if constexpr (v32) {   // (float vectors only ever meet the float plane)
+    ISPH_CHECK((cheb_step_fused<float, XT>(ctx, A, C, (const float *)C->val32.p, halo, c16, b, y, yout, c1, c2)));
+  } else {
+    if (C->value_bits == 32) ISPH_CHECK((cheb_step_fused<float, XT>(ctx, A, C, (const float *)C->val32.p, halo, c16, b, y, yout, c1, c2)));
+    else ISPH_CHECK((cheb_step_fused<double, XT>(ctx, A, C, (const double *)S.val.p, halo, c16, b, y, yout, c1, c2)));
+  }
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }
@@ -440,23 +573,37 @@ inline void cheb_first_launch(isph_ctx *ctx, const Cheb *C, const double *r, con
     hipLaunchKernelGGL((k_cheby_first<false>), dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, n, C->c2[0],
                        (const double *)C->dinv.p, r, yin, C->w.p, yout);
 }
+inline void cheb_first_launch(isph_ctx *ctx, const Cheb *C, const float *r, const float *yin, float *yout) {
+  const int n = C->n;
+  if (n <= 0) return;
+  const uintptr_t bits = reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(yin) | reinterpret_cast<uintptr_t>(yout);
+  if ((bits & 15) == 0)   // (dinv32 and w32 are buffers of the pool)
+    hipLaunchKernelGGL((k_cheby_first_f32<true>), dim3(stream_grid((n + 3) / 4)), dim3(kBlock), 0, ctx->stream, n, C->c2[0],
+                       (const float *)C->dinv32.p, r, yin, C->w32.p, yout);
+  else
+    hipLaunchKernelGGL((k_cheby_first_f32<false>), dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, n, C->c2[0],
+                       (const float *)C->dinv32.p, r, yin, C->w32.p, yout);
+}
 
 // y <- y + p(D^-1 A) D^-1 (b - A y), p of degree C->degree.
 //   zero_guess: y is not read (y = p(D^-1 A) D^-1 b); the first step makes no matrix product.
 //   r0 != NULL (with a guess): b - A y is already there (the AMG cycle's A P shortcut); again no product in step 1.
 // The steps ping-pong between y and C->t; the result is in y for every degree.
-inline int cheb_apply(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const double *b, double *y, bool zero_guess,
-                      const double *r0 = nullptr) {
+// XT = float: a polynomial set up with vec_bits 32, on float vectors (t32 is the second y).
+template <class XT>
+inline int cheb_apply(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const XT *b, XT *y, bool zero_guess,
+                      const XT *r0 = nullptr) {
   ISPH_REQUIRE(C != nullptr && C->n == A->S.nrow, "Chebyshev: not set up for this matrix");
+  ISPH_REQUIRE(C->vec_bits == (int)(8 * sizeof(XT)), "Chebyshev: set up for vectors of the other precision");
   const int d = C->degree;
-  const size_t nbytes = sizeof(double) * (size_t)(C->n > 0 ? C->n : 0);
-  double *T = C->t.p;
-  const double *cur;
+  const size_t nbytes = sizeof(XT) * (size_t)(C->n > 0 ? C->n : 0);
+  XT *T = ChebVecs<XT>::t(C);
+  const XT *cur;
   int k0;   // first step that needs a product
   if (zero_guess || r0) {
     // d - 1 products follow: an even number ends where it starts
-    double *first = ((d - 1) % 2 == 0) ? y : T;
-    cheb_first_launch(ctx, C, zero_guess ? b : r0, zero_guess ? nullptr : y, first);
+    XT *first = ((d - 1) % 2 == 0) ? y : T;
+    cheb_first_launch(ctx, C, zero_guess ? b : r0, zero_guess ? (const XT *)nullptr : (const XT *)y, first);
     cur = first;
     k0 = 1;
   } else {
@@ -464,7 +611,7 @@ inline int cheb_apply(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const dou
     k0 = 0;
   }
   for (int k = k0; k < d; ++k) {
-    double *nxt = cur == y ? T : y;
+    XT *nxt = cur == y ? T : y;
     ISPH_CHECK(cheb_step(ctx, A, C, b, cur, nxt, C->c1[k], C->c2[k]));
     cur = nxt;
   }

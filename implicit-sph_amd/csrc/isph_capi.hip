@@ -1394,6 +1394,19 @@ int isph_prec_value_bits(const isph_prec *M) {
   return 0;
 }
 
+int isph_prec_cycle_bits(const isph_prec *M) {
+  return (M && M->type == 3 && M->amg && M->amg->cheb && M->amg->cycle_bits == 32) ? 32 : 64;
+}
+
+// a cycle_bits = 32 AMG is not a linear operator: only flexible GMRES keeps what it was applied to (Z); the other
+// drivers form x += M^-1 (V y), the rounded cycle of a vector it never saw
+static int check_cycle_bits_solver(const isph_prec *M, const isph_solver_params *prm) {
+  if (isph_prec_cycle_bits(M) != 32) return ISPH_SUCCESS;
+  ISPH_REQUIRE(prm->solver_type == 0, "a preconditioner with cycle_bits = 32 needs flexible Block GMRES: solver_type 1 and 2 are not available with it");
+  ISPH_REQUIRE(prm->flexible != 0, "a preconditioner with cycle_bits = 32 needs flexible = 1: the rounded cycle is not a linear operator");
+  return ISPH_SUCCESS;
+}
+
 // "chebyshev<d>" or "chebyshev<d>-f32", d = 1..16; *bits = 64 or 32
 static bool parse_chebyshev_type(const char *type, int *degree, int *bits) {
   if (strncmp(type, "chebyshev", 9) != 0 || type[9] < '1' || type[9] > '9') return false;
@@ -1632,6 +1645,7 @@ void isph_amg_params_default(isph_amg_params *p) {
   p->cheb_ratio = 20.0;  // ML's "smoother: Chebyshev alpha"
   p->cheb_value_bits = 64;
   p->eig_type = 0; p->eig_iters = 10;  // "eigen-analysis: type" Anorm (the wrapper's rule); ML's "eigen-analysis: iterations"
+  p->cycle_bits = 64;
 }
 
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,
@@ -1769,6 +1783,7 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
     ISPH_REQUIRE(prm.solver_type == 0, "basis_bits = 32 is Block GMRES only (solver_type 0): CG and GCRO-DR keep basis_bits 64");
     ISPH_REQUIRE(prm.ortho != 2, "basis_bits = 32 takes DGKS or ICGS: IMGS (ortho = 2) keeps the fp64 basis");
   }
+  ISPH_CHECK(check_cycle_bits_solver(M, &prm));
   memset(info, 0, sizeof(*info));
   ISPH_CHECK(ensure_scalars(ctx));
   hipStream_t st = ctx->stream;
@@ -1964,6 +1979,7 @@ int isph_solve_block(isph_ctx *ctx, int dim, const isph_mat *const *blocks, cons
   int basis_bits = 64;
   ISPH_CHECK(basis_bits_of(&prm, &basis_bits));
   ISPH_REQUIRE(basis_bits == 64, "isph_solve_block keeps the fp64 Krylov basis: basis_bits = 32 is not available here");
+  ISPH_CHECK(check_cycle_bits_solver(M, &prm));
   memset(info, 0, sizeof(*info));
   ISPH_CHECK(ensure_scalars(ctx));
   hipStream_t st = ctx->stream;

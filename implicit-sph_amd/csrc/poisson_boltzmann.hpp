@@ -185,6 +185,8 @@ inline int pb_check_params(const isph_pb_params *p) {
   ISPH_REQUIRE(p->max_iters >= 0 && p->prec_max_age >= 1, "need max_iters >= 0 and prec_max_age >= 1");
   ISPH_REQUIRE(p->prec_kind == 0 || p->prec_kind == 1, "prec_kind: 0 SA-AMG, 1 block-Jacobi ILU(0)");
   ISPH_REQUIRE(p->linear.solver_type == 0, "the Newton step's linear solve is GMRES (solver_type 0)");
+  ISPH_REQUIRE(!(p->prec_kind == 0 && p->amg.cycle_bits == 32 && p->linear.flexible == 0),
+               "amg.cycle_bits = 32 needs linear.flexible = 1: the rounded cycle is not a linear operator");
   return ISPH_SUCCESS;
 }
 

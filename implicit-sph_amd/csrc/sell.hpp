@@ -389,29 +389,34 @@ __global__ void k_sell_rows_to_csr(int row0, int n, const int *__restrict__ rowl
 // LIST: the launch covers the slices slice_list[0..nslices) (interior / boundary split of a matrix with a halo: the
 // interior slices have no ghost column and run while the halo exchange is in flight).  GHOST: columns >= nrow are
 // read from the ghost buffer xg the exchange received into (no copy of x into an extended vector).
-template <bool GHOST>
-__device__ __forceinline__ double x_at(const double *__restrict__ x, const double *__restrict__ xg, int nrow, int c) {
-  if (GHOST) return c < nrow ? x[c] : xg[c - nrow];
-  return x[c];
+// XT = float: the vector is stored in single precision (the cycle_bits = 32 V cycle of amg.hpp), a 4-byte gather widened
+// here; ghost values always arrive as doubles (the pack kernel widens them: comm.hpp moves doubles only).
+template <bool GHOST, class XT>
+__device__ __forceinline__ double x_at(const XT *__restrict__ x, const double *__restrict__ xg, int nrow, int c) {
+  if (GHOST) return c < nrow ? (double)x[c] : xg[c - nrow];
+  return (double)x[c];
 }
 
 // VT = float: sval is a float copy of the values in the same positions (the value plane of a Chebyshev preconditioner with
 // value_bits 32, chebyshev.hpp); each value is widened before its fma, everything else is the double kernel.
+// XT / YT = float (with VT = float, no DOT): x and badd / y are float vectors.  Every operand is widened, the row sum and the
+// epilogue are fp64 (a product of two floats is exact there) and the result is rounded once, in the store.
 template <class VT> struct SellPair;
 template <> struct SellPair<double> { typedef double2 type; };
 template <> struct SellPair<float> { typedef float2 type; };
 
-template <int UNROLL, bool DOT, bool NT = false, bool LIST = false, bool GHOST = false, class VT = double>
+template <int UNROLL, bool DOT, bool NT = false, bool LIST = false, bool GHOST = false, class VT = double, class XT = double,
+          class YT = XT>
 __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int nblocks_padded,
                                                       const long long *__restrict__ slice_off,
                                                       const int *__restrict__ scol,
                                                       const VT *__restrict__ sval,
-                                                      const double *__restrict__ x, double *__restrict__ y,
+                                                      const XT *__restrict__ x, YT *__restrict__ y,
                                                       const double *__restrict__ nvec,
                                                       double *__restrict__ dot_partial,
                                                       const int *__restrict__ slice_list = nullptr,
                                                       const double *__restrict__ xg = nullptr,
-                                                      const double *badd = nullptr, double alpha = 1.0) {
+                                                      const XT *badd = nullptr, double alpha = 1.0) {
   typedef typename SellPair<VT>::type VT2;
   const int b = xcd_remap(blockIdx.x, nblocks_padded);
   int slice = b * (kBlock / kWave) + (threadIdx.x >> 6);
@@ -462,8 +467,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int
   // epilogue of the AMG cycle: y = badd + alpha (A x) -- residual b - A x, corrections x += P e, r -= (A P) e -- with the
   // bits of the product followed by the vector kernel it replaces (badd may be y itself)
   if (alpha != 1.0) r *= alpha;
-  if (badd != nullptr && row < nrow) r += badd[row];
-  if (row < nrow) y[row] = r;
+  if (badd != nullptr && row < nrow) r += (double)badd[row];
+  if (row < nrow) y[row] = (YT)r;
   if (DOT) {
     const double d = wave_sum(row < nrow ? r * nvec[row] : 0.0);
     if (lane == 0) dot_partial[slice] = d;
@@ -538,18 +543,18 @@ __global__ __launch_bounds__(kBlock) void k_sell_compress_cols(int slice_begin, 
   }
 }
 
-template <int UNROLL, bool DOT, bool LIST = false, bool GHOST = false, class VT = double>
+template <int UNROLL, bool DOT, bool LIST = false, bool GHOST = false, class VT = double, class XT = double, class YT = XT>
 __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, int nblocks_padded,
                                                         const long long *__restrict__ slice_off,
                                                         const unsigned short *__restrict__ c16,
                                                         const int *__restrict__ wtab,
                                                         const VT *__restrict__ sval,
-                                                        const double *__restrict__ x, double *__restrict__ y,
+                                                        const XT *__restrict__ x, YT *__restrict__ y,
                                                         const double *__restrict__ nvec,
                                                         double *__restrict__ dot_partial,
                                                         const int *__restrict__ slice_list = nullptr,
                                                         const double *__restrict__ xg = nullptr,
-                                                        const double *badd = nullptr, double alpha = 1.0) {
+                                                        const XT *badd = nullptr, double alpha = 1.0) {
   typedef typename SellPair<VT>::type VT2;
   __shared__ int tab[kBlock / kWave][64];
   const int b = xcd_remap(blockIdx.x, nblocks_padded);
@@ -602,8 +607,8 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, i
   // epilogue of the AMG cycle: y = badd + alpha (A x) -- residual b - A x, corrections x += P e, r -= (A P) e -- with the
   // bits of the product followed by the vector kernel it replaces (badd may be y itself)
   if (alpha != 1.0) r *= alpha;
-  if (badd != nullptr && row < nrow) r += badd[row];
-  if (row < nrow) y[row] = r;
+  if (badd != nullptr && row < nrow) r += (double)badd[row];
+  if (row < nrow) y[row] = (YT)r;
   if (DOT) {
     const double d = wave_sum(row < nrow ? r * nvec[row] : 0.0);
     if (lane == 0) dot_partial[slice] = d;

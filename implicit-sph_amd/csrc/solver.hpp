@@ -51,6 +51,19 @@ inline int fetch_scalars(isph_ctx *ctx, int first, int count) {
 __global__ void k_gather(int n, const int *__restrict__ idx, const double *__restrict__ x, double *__restrict__ out) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = x[idx[i]];
 }
+// the pack kernel of a float vector (the cycle_bits = 32 V cycle): ghost values travel as doubles that hold floats, so the
+// transports of comm.hpp see what they always see
+__global__ void k_gather_widen(int n, const int *__restrict__ idx, const float *__restrict__ x, double *__restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = (double)x[idx[i]];
+}
+inline void halo_pack(isph_ctx *ctx, const isph_halo &H, const double *x) {
+  hipLaunchKernelGGL(k_gather, dim3(stream_grid(H.nsend)), dim3(kBlock), 0, ctx->stream, H.nsend, H.send_idx.p, x,
+                     ctx->sendbuf.p);
+}
+inline void halo_pack(isph_ctx *ctx, const isph_halo &H, const float *x) {
+  hipLaunchKernelGGL(k_gather_widen, dim3(stream_grid(H.nsend)), dim3(kBlock), 0, ctx->stream, H.nsend, H.send_idx.p, x,
+                     ctx->sendbuf.p);
+}
 
 // Starts the halo exchange of x for a matrix with ghost columns: the boundary values are packed on the compute stream,
 // the point-to-point exchange (comm.hpp: grouped ncclSend/ncclRecv, or the host-staged transport) runs on
@@ -61,7 +74,8 @@ __global__ void k_gather(int n, const int *__restrict__ idx, const double *__res
 // itself waits for ev_halo.  (Ifpack/Epetra do this Import inside Epetra_CrsMatrix::Apply, solver_lin.h:133.)
 // hev (profile mode, the caller's operator only): three timing events of this product -- [0] values packed (compute
 // stream), [1] ghost values landed (halo stream), [2] interior slices done (compute stream, recorded by spmv_dev)
-inline int halo_begin(isph_ctx *ctx, const isph_mat *A, const double *x, hipEvent_t *hev = nullptr) {
+template <class XT>
+inline int halo_begin(isph_ctx *ctx, const isph_mat *A, const XT *x, hipEvent_t *hev = nullptr) {
   ISPH_REQUIRE(comm_active(ctx) && ctx->comm_stream,
                "a matrix with a halo needs a context made by isph_ctx_create_dist or isph_ctx_create_hostcomm");
   const Sell &S = A->S;
@@ -70,9 +84,7 @@ inline int halo_begin(isph_ctx *ctx, const isph_mat *A, const double *x, hipEven
   ISPH_REQUIRE(H.n_int + H.n_bnd == S.nslices, "halo plan without the interior/boundary slice lists");
   ISPH_CHECK(ctx->xghost.reserve((size_t)(H.nrecv > 0 ? H.nrecv : 1)));
   ISPH_CHECK(ctx->sendbuf.reserve((size_t)(H.nsend > 0 ? H.nsend : 1)));
-  if (H.nsend > 0)
-    hipLaunchKernelGGL(k_gather, dim3(stream_grid(H.nsend)), dim3(kBlock), 0, ctx->stream, H.nsend, H.send_idx.p, x,
-                       ctx->sendbuf.p);
+  if (H.nsend > 0) halo_pack(ctx, H, x);
   ISPH_CHECK_HIP(hipEventRecord(ctx->ev_pack, ctx->stream));
   if (hev) ISPH_CHECK_HIP(hipEventRecord(hev[0], ctx->stream));
   ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->comm_stream, ctx->ev_pack, 0));
@@ -165,6 +177,46 @@ inline int spmv_dev(isph_ctx *ctx, const isph_mat *A, const double *x, double *y
                        ctx->dscal.p + SC_MISC);
     ISPH_CHECK(allreduce_inplace(ctx, ctx->dscal.p + SC_MISC, 1));
   }
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+// ---- float vectors: the products of the cycle_bits = 32 V cycle (amg.hpp) -----------------------------------------------
+// y = badd + alpha (A~ x) with A~ the float plane val32 (same positions as S.val), x and badd float vectors, y a float
+// vector (YT = float: rounded once, in the store) or a double one (the unfused Chebyshev cross-check keeps b - A~ y
+// unrounded, as the fused step does).  Same slice walk, lists, halo overlap and column forms as spmv_dev.
+template <bool LIST, bool GHOST, class YT>
+inline void spmv_launch_f32(isph_ctx *ctx, const Sell &S, bool c16, int nsl, const int *list, const float *val32, const float *x,
+                            const double *xg, YT *y, const float *badd, double alpha) {
+  if (nsl <= 0) return;
+  int nbp = 0;
+  const int grid = spmv_grid(nsl, &nbp);
+  if (c16)
+    hipLaunchKernelGGL((k_sell_spmv16<8, false, LIST, GHOST, float, float, YT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       S.slice_off.p, S.col16.p, S.wtab.p, val32, x, y, (const double *)nullptr, (double *)nullptr, list, xg, badd, alpha);
+  else
+    hipLaunchKernelGGL((k_sell_spmv<8, false, true, LIST, GHOST, float, float, YT>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, nsl, nbp,
+                       S.slice_off.p, S.col.p, val32, x, y, (const double *)nullptr, (double *)nullptr, list, xg, badd, alpha);
+}
+
+template <class YT>
+inline int spmv_dev_f32(isph_ctx *ctx, const isph_mat *A, const float *val32, const float *x, YT *y, const float *badd = nullptr,
+                        double alpha = 1.0) {
+  const Sell &S = A->S;
+  ISPH_REQUIRE(val32 != nullptr, "spmv: the float product needs the float plane of the matrix");
+  const bool halo = !A->local && (S.ncol != S.nrow || A->halo.nsend > 0);
+  const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
+  ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);
+  if (!halo) {
+    spmv_launch_f32<false, false, YT>(ctx, S, c16, S.nslices, nullptr, val32, x, nullptr, y, badd, alpha);
+  } else {
+    const isph_halo &H = A->halo;
+    ISPH_CHECK(halo_begin(ctx, A, x));
+    spmv_launch_f32<true, false, YT>(ctx, S, c16, H.n_int, H.list_int.p, val32, x, nullptr, y, badd, alpha);
+    ISPH_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
+    spmv_launch_f32<true, true, YT>(ctx, S, c16, H.n_bnd, H.list_bnd.p, val32, x, ctx->xghost.p, y, badd, alpha);
+  }
+  prof.end();
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }

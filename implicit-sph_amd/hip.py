@@ -29,7 +29,7 @@ EXPORTS = [
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
-    "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits",
+    "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits", "isph_prec_cycle_bits",
     "isph_prec_eig_estimate",
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
@@ -41,7 +41,7 @@ class AmgParams(C.Structure):
     """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55)."""
     _fields_ = [("max_levels", C.c_int), ("coarse_max", C.c_int), ("omega", C.c_double), ("block", C.c_int),
                 ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double),
-                ("cheb_value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int)]
+                ("cheb_value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int), ("cycle_bits", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -239,6 +239,8 @@ def lib():
         L.isph_ilu_params_default.restype = None
         L.isph_prec_create_ilu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_value_bits.restype = C.c_int
+        L.isph_prec_cycle_bits.argtypes = [C.c_void_p]
+        L.isph_prec_cycle_bits.restype = C.c_int
         L.isph_prec_amg_info.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_aggregates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -768,6 +770,12 @@ class Precond:
         preconditioner, or an AMG with the Chebyshev smoother); 32 for a block ILU with single-precision stream values
         ("bjacobi-ilu<k>-f32"); 0 for every other preconditioner."""
         return int(lib().isph_prec_value_bits(self.h))
+
+    @property
+    def cycle_bits(self):
+        """isph_prec_cycle_bits: 32 for an AMG built with AmgParams(cycle_bits=32) (the whole V cycle in single-precision
+        storage: operators, level vectors and gathers float, arithmetic fp64; flexible GMRES only), 64 for everything else"""
+        return int(lib().isph_prec_cycle_bits(self.h))
 
     def eig_estimate(self, level=0):
         """isph_prec_eig_estimate: lambda_used, rho = ||D^-1 A||_inf and the Arnoldi steps taken, for a Chebyshev

@@ -78,6 +78,14 @@ class PrecondWrapper_ML : public PrecondWrapper {
                    prm.cheb_value_bits);
       return ISPH_FAILURE;
     }
+    // device-side extension, read beside it: 32 = the whole V cycle in single-precision storage (isph_amg_params::cycle_bits;
+    // the solver must then be flexible GMRES, SolverLin_Belos' default)
+    if (cheb) prm.cycle_bits = _param->get("isph: amg cycle bits", 64);
+    if (cheb && prm.cycle_bits != 64 && prm.cycle_bits != 32) {
+      std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): \"isph: amg cycle bits\" = %d is not available; available: 64, 32\n",
+                   prm.cycle_bits);
+      return ISPH_FAILURE;
+    }
     // ML's own keys.  "Anorm" -- the bound rho = ||D^-1 A||_inf -- is this wrapper's default and a kept departure (ML's
     // default is "cg"); "cg" asks for the estimate after "eigen-analysis: iterations" steps, which the device takes with
     // Arnoldi (isph_amg_params::eig_type = 1: correct for the nonsymmetric matrices too, the same projection otherwise)

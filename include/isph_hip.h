@@ -390,6 +390,9 @@ int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb
  * smoother = 2); 32 for a block ILU whose solves stream single-precision factor values ("bjacobi-ilu<k>-f32",
  * isph_ilu_params::value_bits = 32); 0 for every other preconditioner -- a plain "bjacobi-ilu<k>" included -- and for NULL. */
 int isph_prec_value_bits(const isph_prec *M);
+/* 32 for an AMG built with isph_amg_params::cycle_bits = 32 (its whole V cycle runs in single-precision storage; its
+ * isph_prec_value_bits is 32 too); 64 for every other preconditioner and for NULL. */
+int isph_prec_cycle_bits(const isph_prec *M);
 /* out = {lambda_used, rho, Arnoldi steps taken} of a Chebyshev preconditioner (level 0) or of level `level` of an AMG
  * (the estimate of the level's fp64 operator: the one that damps the prolongator; with cheb_value_bits = 32 the
  * smoother's own estimate on fl32(A_l) is not reported).  With eig_type 0 -- or an explicit lambda_max -- it returns
@@ -750,6 +753,38 @@ typedef struct {
    * 2.00 / 2.23 / 2.10): smoother 2 of degree 2 needs 17 against 26 iterations, 33.1 against 38.4 ms for create plus solve
    * (create 14.6 against 10.3 ms); smoother 0 needs 27 against 33 iterations, 41.6 against 43.1 ms. */
   int eig_type, eig_iters;
+  /* 64 (default; 0 means the same) or 32 = the whole V cycle in single-precision STORAGE: operators, level vectors and
+   * gathers are float, all arithmetic stays fp64.  With 64 or 0 the launches, arguments and bits of every result are those
+   * of a library without the field.  Needs smoother = 2; any other width, or 32 with another smoother (the Gauss-Seidel
+   * stream and the dense block smoothers keep fp64 vectors), is refused by the create call.  Off by default.
+   * The arithmetic with cycle_bits = 32, smoother = 2:
+   *   Hierarchy.  Aggregates, P, R, the Galerkin products, the eigenvalue estimates of A_l, the damping and the exported
+   *     levels are the fp64 ones, bit for bit those of cycle_bits = 64.
+   *   Float planes.  After the set-up every operator the cycle applies gets a float plane, each stored value rounded once
+   *     (nearest even, subnormals kept, element positions unchanged): A~_l = fl32(A_l), the plane cheb_value_bits = 32
+   *     makes; P~_l = fl32(P_l); R~_l = P~_l^T; and on the levels that keep A P (one rank, no halo), fl32(A_l P_l) of the
+   *     set-up's product.  A value beyond FLT_MAX fails the create call; a diagonal that rounds to 0 fails as a zero
+   *     diagonal, as cheb_value_bits = 32 does.
+   *   Scalars and diagonal.  D^-1 of a level is stored as float, fl32(1 / a~_ii) with the quotient taken in fp64.  rho, the
+   *     interval and the Chebyshev scalars come from A~_l exactly as cheb_value_bits = 32 takes them, the second Arnoldi
+   *     estimate on fl32(A_l) with eig_type = 1 included; cheb_value_bits itself is not read.
+   *   Stored vectors.  Every level vector is float: x, b, r of the cycle and w, y of the polynomial.  Every kernel widens its
+   *     operands to fp64, does all arithmetic in fp64 and rounds ONCE per stored element.  A product of two floats is exact
+   *     in fp64, so a row sum is an fp64 sum of exact products.  In a Chebyshev step wn is computed in fp64; then
+   *     w = fl32(wn) and yout = fl32(y + wn) with the unrounded wn.
+   *   Entry, exit, coarsest solve.  b_0 = fl32(r) of the Krylov vector; z = the float result widened.  The coarsest dense
+   *     inverse stays fp64; it reads the float b and writes fl32(x).  Across ranks the right-hand side is widened and the
+   *     all-reduce stays fp64.  With a null vector the coarsest level runs the same float polynomial.
+   *   Cycle order, unchanged: (1) pre-smoother from a zero guess (product-free first step); (2) r = fl32(b - A~ x);
+   *     (3) b_c = fl32(R~ r); (4) recursion; (5) x = fl32(x + P~ e); (6) where A P is kept, r = fl32(r - fl32(A P) e) feeds
+   *     the post-smoother's first step, otherwise that step forms b - A~ x itself.
+   *   Halo.  Ghost values travel as doubles, widened in the pack kernel: a ghost read in a sweep is a double that holds a
+   *     float.
+   * The cycle is NOT a linear operator (it rounds): isph_solve and isph_solve_block take such a preconditioner only with
+   * flexible GMRES (solver_type 0, flexible 1: the default); solver_type 1 or 2, or flexible = 0, is refused there with
+   * cycle_bits named -- x += M^-1 (V y) would apply the rounded cycle to a vector it was never applied to.
+   * isph_solve_poisson_boltzmann passes the pair through and keeps the same rule. */
+  int cycle_bits;
 } isph_amg_params;
 void isph_amg_params_default(isph_amg_params *p);
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,
