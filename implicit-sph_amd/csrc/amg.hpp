@@ -69,6 +69,11 @@ struct AmgLevel {
   // cycle applies has a float plane -- A~_l is cheb->val32; p32 = fl32 of Pm's values, ap32 = fl32 of APm's (position by
   // position; APm's doubles go back to the pool), rv32 = fl32 of R.v = P~^T
   DevBuf<float> x32, b32, r32, p32, ap32, rv32;
+  // amg_vcycle_multi: x, b, r of K vectors, vector k at k * multi_ld() (level 0 keeps r only: its x and b are the caller's).
+  // From the pool at the first K-vector cycle, grown when a larger K comes, released with the level; x, b, r above stay the
+  // single cycle's own.
+  DevBuf<double> xm, bm, rm;
+  size_t multi_ld() const { return ((size_t)(A.n > 0 ? A.n : 1) + 64 + 1) & ~(size_t)1; }   // even: every vector 16-byte aligned
   // which branch of every ladder the set-up took on this level (isph_prec_amg_path): host integers, filled as it goes
   long long path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // isph_amg_params::eig_type == 1: the estimate of lambda_max(D^-1 A_l) of this level's fp64 operator (eig_estimate.hpp)
@@ -959,6 +964,33 @@ __global__ __launch_bounds__(256) void k_csr_spmv_wave(int n, const rp_t *__rest
   if (lane == 0) y[i] = (XT)s;
 }
 
+// ... for NV = 2..4 double vectors: the row of R (values and columns) is read once, every vector keeps its own fma chain over
+// the lane's entries and its own wave sum -- the bits of NV launches of k_csr_spmv_wave
+struct AmgMultiVecs {
+  const double *in[4];
+  double *out[4];
+};
+template <int NV>
+__global__ __launch_bounds__(256) void k_csr_spmv_wave_multi(int n, const rp_t *__restrict__ rp, const int *__restrict__ ci,
+                                                             const double *__restrict__ v, AmgMultiVecs V) {
+  const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  double s[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) s[k] = 0.0;
+  for (rp_t p = rp[i] + lane; p < rp[i + 1]; p += 64) {
+    const double a = v[p];
+    const int c = ci[p];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] = fma(a, V.in[k][c], s[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const double t = wave_sum(s[k]);
+    if (lane == 0) V.out[k][i] = t;
+  }
+}
+
 constexpr int kAmgDenseMax = 2048;  // largest coarsest level the dense inverse is formed for
 // ---- dense direct solve of the coarsest level (non-singular case) ---------------------------------------
 __global__ void k_dense_from_csr(int n, const rp_t *__restrict__ rp, const int *__restrict__ ci,
@@ -1054,6 +1086,27 @@ __global__ __launch_bounds__(256) void k_dense_apply(int n, const double *__rest
   for (int c = lane; c < n; c += 64) s += aug[(size_t)i * 2 * n + c] * (double)b[c];   // the inverse: left half (k_gj_finish)
   s = wave_sum(s);
   if (lane == 0) x[i] = (XT)s;
+}
+
+// ... for NV = 2..4 double right-hand sides: a row of the inverse is read once; the sum of every vector is the expression of
+// k_dense_apply term by term (the compiler contracts both alike), then its own wave sum
+template <int NV>
+__global__ __launch_bounds__(256) void k_dense_apply_multi(int n, const double *__restrict__ aug, AmgMultiVecs V) {
+  const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  double s[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) s[k] = 0.0;
+  for (int c = lane; c < n; c += 64) {
+    const double a = aug[(size_t)i * 2 * n + c];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) s[k] += a * V.in[k][c];
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const double t = wave_sum(s[k]);
+    if (lane == 0) V.out[k][i] = t;
+  }
 }
 
 // ---- the smoother of small coarse levels as dense block inverses ---------------------------------------------------
@@ -1342,6 +1395,7 @@ inline void amg_level_destroy(AmgLevel *L) {
   if (L->cheb) cheb_destroy(L->cheb);
   L->agg.release(); L->nv.release(); L->x.release(); L->b.release(); L->r.release(); L->z.release();
   L->x32.release(); L->b32.release(); L->r32.release(); L->p32.release(); L->ap32.release(); L->rv32.release();
+  L->xm.release(); L->bm.release(); L->rm.release();
   delete L;
 }
 
@@ -2310,6 +2364,93 @@ inline int amg_apply(isph_ctx *ctx, const isph_amg *G, const double *r, double *
   } else {
     ISPH_CHECK(amg_vcycle_t<double>(ctx, G, 0, r, z));
   }
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+// ---- K vectors per sweep ----------------------------------------------------------------------------------------------
+// whether amg_apply_multi can serve this hierarchy: the fp64 cycle with the Chebyshev smoother on one rank, every level's
+// polynomial in its fused form and no operator with a halo.  Gauss-Seidel smoothers, cycle_bits 32 and hierarchies across
+// ranks apply their vectors one after the other.
+inline bool amg_multi_ok(const isph_amg *G) {
+  if (!G || !G->cheb || G->cycle_bits != 64 || G->dist || G->nlev < 1) return false;
+  for (int l = 0; l < G->nlev; ++l) {
+    const AmgLevel *L = G->L[(size_t)l];
+    const bool last = l == G->nlev - 1;
+    if (!L->Am || mat_has_halo(L->Am)) return false;
+    if (!last || G->coarse_smooth) { if (!cheb_multi_ok(L->Am, L->cheb)) return false; }
+    if (!last && (!L->Pm || mat_has_halo(L->Pm) || (L->APm && mat_has_halo(L->APm)))) return false;
+  }
+  return true;
+}
+
+// the K-fold level vectors, sized for K (grow-only)
+inline int amg_multi_buffers(const isph_amg *G, int K) {
+  for (int l = 0; l < G->nlev; ++l) {
+    AmgLevel *L = G->L[(size_t)l];
+    const size_t m = L->multi_ld() * (size_t)K;
+    if (l > 0) { ISPH_CHECK(L->xm.reserve(m)); ISPH_CHECK(L->bm.reserve(m)); }
+    if (l < G->nlev - 1) ISPH_CHECK(L->rm.reserve(m));
+  }
+  return ISPH_SUCCESS;
+}
+
+template <class KERNEL_LAUNCH>
+inline void amg_multi_dispatch(int K, KERNEL_LAUNCH &&launch) {
+  if (K == 2) launch(std::integral_constant<int, 2>());
+  else if (K == 3) launch(std::integral_constant<int, 3>());
+  else launch(std::integral_constant<int, 4>());
+}
+
+// amg_vcycle_t<double> of the Chebyshev smoother restated over K = 2..4 vectors: every operator of the cycle -- the
+// polynomial's sweeps, A_l, R_l, P_l, A_l P_l, the dense inverse -- is read once for all of them, and every vector goes
+// through the operations of the single kernels in their order.  Same shortcut rule, same coarsest-level branches.
+inline int amg_vcycle_multi(isph_ctx *ctx, const isph_amg *G, int l, int K, const double *const *b, double *const *x) {
+  AmgLevel *L = G->L[(size_t)l];
+  const int n = L->A.n;
+  if (l == G->nlev - 1) {
+    if (G->coarse_smooth) {
+      ISPH_CHECK(cheb_apply_multi(ctx, L->Am, L->cheb, K, b, x, /*zero_guess=*/true));   // the level is "solved" by the same polynomial
+    } else if (n > 0) {
+      AmgMultiVecs V;
+      for (int k = 0; k < 4; ++k) { V.in[k] = b[k < K ? k : 0]; V.out[k] = x[k < K ? k : 0]; }
+      amg_multi_dispatch(K, [&](auto nv) {
+        hipLaunchKernelGGL((k_dense_apply_multi<decltype(nv)::value>), dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n,
+                           (const double *)G->cinv.p, V);
+      });
+    }
+    return ISPH_SUCCESS;
+  }
+  AmgLevel *Lc = G->L[(size_t)l + 1];
+  double *r[4], *bc[4], *xc[4];
+  for (int k = 0; k < K; ++k) {
+    r[k] = L->rm.p + L->multi_ld() * (size_t)k;
+    bc[k] = Lc->bm.p + Lc->multi_ld() * (size_t)k;
+    xc[k] = Lc->xm.p + Lc->multi_ld() * (size_t)k;
+  }
+  ISPH_CHECK(cheb_apply_multi(ctx, L->Am, L->cheb, K, b, x, /*zero_guess=*/true));
+  ISPH_CHECK(spmm_axpb_dev(ctx, L->Am, K, x, r, b, -1.0));   // r = b - A x
+  if (L->R.n > 0) {
+    AmgMultiVecs V;
+    for (int k = 0; k < 4; ++k) { V.in[k] = r[k < K ? k : 0]; V.out[k] = bc[k < K ? k : 0]; }
+    amg_multi_dispatch(K, [&](auto nv) {
+      hipLaunchKernelGGL((k_csr_spmv_wave_multi<decltype(nv)::value>), dim3(amg_wave_grid(L->R.n)), dim3(256), 0, ctx->stream, L->R.n,
+                         (const rp_t *)L->R.rp.p, (const int *)L->R.ci.p, (const double *)L->R.v.p, V);
+    });
+  }
+  ISPH_CHECK(amg_vcycle_multi(ctx, G, l + 1, K, bc, xc));
+  ISPH_CHECK(spmm_axpb_dev(ctx, L->Pm, K, xc, x, x, 1.0));   // x += P e
+  // (the shortcut rule of amg_vcycle_t; cycle_bits is 64 here)
+  const bool shortcut = L->APm != nullptr && (G->cheb_value_bits != 32 || G->cycle_bits == 32);
+  if (shortcut) ISPH_CHECK(spmm_axpb_dev(ctx, L->APm, K, xc, r, r, -1.0));   // r -= (A P) e
+  return cheb_apply_multi(ctx, L->Am, L->cheb, K, b, x, /*zero_guess=*/false, shortcut ? r : nullptr);
+}
+
+// z_k = the cycle applied to r_k, k < K, 2 <= K <= 4, for a hierarchy amg_multi_ok accepts: the bits of K calls of amg_apply
+inline int amg_apply_multi(isph_ctx *ctx, const isph_amg *G, int K, const double *const *rs, double *const *zs) {
+  ISPH_REQUIRE(G != nullptr && K >= 2 && K <= 4 && amg_multi_ok(G), "AMG: no K-vector form for this hierarchy or K");
+  ISPH_CHECK(amg_multi_buffers(G, K));
+  ISPH_CHECK(amg_vcycle_multi(ctx, G, 0, K, rs, zs));
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }

@@ -29,6 +29,12 @@
 // y, b, w and D^-1 = fl32(1 / a~_ii).  Every kernel widens its operands, does the arithmetic of the double kernel in fp64
 // (a product of two floats is exact there) and rounds once per stored element: w = fl32(wn), yout = fl32(y + wn) with the
 // unrounded increment wn.  The gather of y is a 4-byte load; ghost values arrive as doubles that hold floats.
+//
+// K = 2..4 vectors per sweep (cheb_apply_multi; isph_prec_apply_multi, the lockstep solve, the block solve): the fused step
+// and the first step restated over K double vectors -- values, columns and D^-1 loaded once, every vector its own gather,
+// its own fma chains and the shared epilogue, so each vector has the bits of its own cheb_apply.  No halo form, no unfused
+// form, no float-vector form: those apply one vector after the other.  100^3, K = 3: one step 416.0 us against 557.6 for
+// three single steps (0.75; the algorithmic bytes say 0.64), chebyshev3 904.6 against 1239.3 us.
 #pragma once
 #include <cfloat>
 #include <type_traits>
@@ -49,6 +55,11 @@ struct Cheb {
   DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
   DevBuf<float> val32;                               // value_bits 32: fl32 of S.val, position by position (padding 0)
   DevBuf<float> dinv32, w32, t32;                    // vec_bits 32: fl32(1 / a~_ii), the increment, the second y
+  // cheb_apply_multi: the increments and the second y's of K vectors, vector k at k * multi_ld().  Taken from the pool at
+  // the first K-vector application, grown when a larger K comes, released with the polynomial; w and t above stay the
+  // single application's own, so that one after a K-vector one finds what it always found.
+  mutable DevBuf<double> wm, tm;
+  size_t multi_ld() const { return ((size_t)(n > 0 ? n : 1) + 64 + 1) & ~(size_t)1; }   // even: every vector 16-byte aligned
 };
 
 // the vectors of the polynomial by their type
@@ -69,6 +80,7 @@ inline void cheb_destroy(Cheb *C) {
   if (!C) return;
   C->dinv.release(); C->w.release(); C->t.release(); C->r.release(); C->val32.release();
   C->dinv32.release(); C->w32.release(); C->t32.release();
+  C->wm.release(); C->tm.release();
   delete C;
 }
 
@@ -251,6 +263,50 @@ __global__ __launch_bounds__(kBlock) void k_sell_cheby_step(int nrow, int nslice
   }
 }
 
+// ... for NV = 2..4 vectors in one sweep of the matrix (double vectors, no halo): the values (VT = double, or the float
+// plane of value_bits 32), the columns and dinv are read once, every vector gathers its own y_k and runs the fma chains
+// and the epilogue of k_sell_cheby_step (sell_rowsums_multi, cheb_increment) -- the bits of NV single steps.
+// yout_k must not alias any y_j that is still gathered.
+struct ChebMultiVecs {
+  const double *y[4];
+  const double *b[4];
+  double *w[4];
+  double *yout[4];
+};
+template <bool C16, class VT, int NV>
+__global__ __launch_bounds__(kBlock) void k_sell_cheby_step_multi(int nrow, int nslices, int nblocks_padded,
+                                                                  const long long *__restrict__ slice_off,
+                                                                  const void *__restrict__ cols, const int *__restrict__ wtab,
+                                                                  const VT *__restrict__ sval, const double *__restrict__ dinv,
+                                                                  ChebMultiVecs V, double c1, double c2) {
+  __shared__ int tab[C16 ? kBlock / kWave : 1][64];
+  const int blk = xcd_remap(blockIdx.x, nblocks_padded);
+  const int wave = threadIdx.x >> 6;
+  const int slice = blk * (kBlock / kWave) + wave;
+  if (slice >= nslices) return;
+  const int lane = threadIdx.x & 63;
+  if (C16) {
+    tab[wave][lane] = wtab[(long long)slice * 64 + lane] << 10;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  const long long off = slice_off[slice];
+  const int npair = (int)((slice_off[slice + 1] - off) >> 7);
+  double sum[NV];
+  sell_rowsums_multi<C16, VT, NV>(tab[C16 ? wave : 0], off, npair, lane, cols, sval, V.y, sum);
+  const int row = slice * kSlice + lane;
+  if (row < nrow) {
+    const double d = dinv[row];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      const double r = V.b[k][row] - sum[k];
+      const double wn = cheb_increment(c1, c2, c1 != 0.0 ? V.w[k][row] : 0.0, d, r);
+      V.w[k][row] = wn;
+      V.yout[k][row] = V.y[k][row] + wn;
+    }
+  }
+}
+
 // ---- streaming kernels ------------------------------------------------------------------------------------------------
 // The product-free first step:  w = c2 D^-1 r,  yout = yin + w  (yin == NULL: the zero guess, yout = w).  r is b for a
 // zero guess, or a residual b - A yin the caller already holds.  VEC: 16-byte loads and stores (all pointers aligned).
@@ -285,6 +341,57 @@ __global__ __launch_bounds__(kBlock) void k_cheby_first(int n, double c2, const 
       const double wn = cheb_increment(0.0, c2, 0.0, dinv[i], r[i]);
       w[i] = wn;
       yout[i] = yin ? yin[i] + wn : wn;
+    }
+  }
+}
+
+// ... for NV = 2..4 vectors: dinv is read once per element.  VEC only when every one of the NV pointers of every kind is
+// 16-byte aligned (the components of a block system with an odd leading dimension are not): the host decides.
+struct ChebFirstVecs {
+  const double *r[4];
+  const double *yin[4];   // all NULL (the zero guess) or none
+  double *w[4];
+  double *yout[4];
+};
+template <bool VEC, int NV>
+__global__ __launch_bounds__(kBlock) void k_cheby_first_multi(int n, double c2, const double *__restrict__ dinv, ChebFirstVecs V) {
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool guess = V.yin[0] != nullptr;
+  if (VEC) {
+    const long long n2 = n >> 1;
+    const double2 *d2 = reinterpret_cast<const double2 *>(dinv);
+    for (long long i = t0; i < n2; i += stride) {
+      const double2 d = d2[i];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const double2 rr = reinterpret_cast<const double2 *>(V.r[k])[i];
+        double2 wn, yo;
+        wn.x = cheb_increment(0.0, c2, 0.0, d.x, rr.x);
+        wn.y = cheb_increment(0.0, c2, 0.0, d.y, rr.y);
+        yo = wn;
+        if (guess) { const double2 yy = reinterpret_cast<const double2 *>(V.yin[k])[i]; yo.x = yy.x + wn.x; yo.y = yy.y + wn.y; }
+        reinterpret_cast<double2 *>(V.w[k])[i] = wn;
+        reinterpret_cast<double2 *>(V.yout[k])[i] = yo;
+      }
+    }
+    if ((n & 1) && t0 == 0) {
+      const int i = n - 1;
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const double wn = cheb_increment(0.0, c2, 0.0, dinv[i], V.r[k][i]);
+        V.w[k][i] = wn;
+        V.yout[k][i] = guess ? V.yin[k][i] + wn : wn;
+      }
+    }
+  } else {
+    for (long long i = t0; i < n; i += stride) {
+      const double d = dinv[i];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const double wn = cheb_increment(0.0, c2, 0.0, d, V.r[k][i]);
+        V.w[k][i] = wn;
+        V.yout[k][i] = guess ? V.yin[k][i] + wn : wn;
+      }
     }
   }
 }
@@ -617,6 +724,100 @@ inline int cheb_apply(isph_ctx *ctx, const isph_mat *A, const Cheb *C, const XT 
   }
   if (cur != y && nbytes > 0)   // (a guess and an odd number of products)
     ISPH_CHECK_HIP(hipMemcpyAsync(y, T, nbytes, hipMemcpyDeviceToDevice, ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+// ---- K vectors per sweep ----------------------------------------------------------------------------------------------
+// whether cheb_apply_multi can serve this polynomial: fused steps of double vectors on a matrix without a halo
+inline bool cheb_multi_ok(const isph_mat *A, const Cheb *C) {
+  return C != nullptr && A != nullptr && !C->unfused && C->vec_bits == 64 && !mat_has_halo(A);
+}
+
+template <class VT>
+inline void cheb_step_multi_launch(isph_ctx *ctx, const Sell &S, bool c16, int K, const VT *val, const double *dinv,
+                                   const ChebMultiVecs &V, double c1, double c2) {
+  if (S.nslices <= 0) return;
+  int nbp = 0;
+  const int grid = spmv_grid(S.nslices, &nbp);
+#define ISPH_CHEB_STEP_MULTI(C16, NV, COLS, WTAB)                                                                             \
+  hipLaunchKernelGGL((k_sell_cheby_step_multi<C16, VT, NV>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices, nbp, \
+                     (const long long *)S.slice_off.p, (const void *)(COLS), (const int *)(WTAB), val, dinv, V, c1, c2)
+  if (c16) {
+    if (K == 2) ISPH_CHEB_STEP_MULTI(true, 2, S.col16.p, S.wtab.p);
+    else if (K == 3) ISPH_CHEB_STEP_MULTI(true, 3, S.col16.p, S.wtab.p);
+    else ISPH_CHEB_STEP_MULTI(true, 4, S.col16.p, S.wtab.p);
+  } else {
+    if (K == 2) ISPH_CHEB_STEP_MULTI(false, 2, S.col.p, nullptr);
+    else if (K == 3) ISPH_CHEB_STEP_MULTI(false, 3, S.col.p, nullptr);
+    else ISPH_CHEB_STEP_MULTI(false, 4, S.col.p, nullptr);
+  }
+#undef ISPH_CHEB_STEP_MULTI
+}
+
+template <bool VEC>
+inline void cheb_first_multi_launch(isph_ctx *ctx, const Cheb *C, int K, int grid, const ChebFirstVecs &V) {
+  const double *dinv = C->dinv.p;
+  if (K == 2) hipLaunchKernelGGL((k_cheby_first_multi<VEC, 2>), dim3(grid), dim3(kBlock), 0, ctx->stream, C->n, C->c2[0], dinv, V);
+  else if (K == 3) hipLaunchKernelGGL((k_cheby_first_multi<VEC, 3>), dim3(grid), dim3(kBlock), 0, ctx->stream, C->n, C->c2[0], dinv, V);
+  else hipLaunchKernelGGL((k_cheby_first_multi<VEC, 4>), dim3(grid), dim3(kBlock), 0, ctx->stream, C->n, C->c2[0], dinv, V);
+}
+
+// cheb_apply for K = 2..4 double vectors, one sweep of the matrix per step for all of them: y_k <- y_k + p(D^-1 A) D^-1
+// (b_k - A y_k).  The same first step, the same ping-pong parity between y_k and the second buffer (tm, vector k) and the
+// same closing copy as cheb_apply, so y_k has the bits of cheb_apply(.., b_k, y_k, zero_guess, r0_k).
+// r0s: NULL, or the K residuals b_k - A y_k the caller already holds (with a guess).
+inline int cheb_apply_multi(isph_ctx *ctx, const isph_mat *A, const Cheb *C, int K, const double *const *bs, double *const *ys,
+                            bool zero_guess, const double *const *r0s = nullptr) {
+  ISPH_REQUIRE(C != nullptr && C->n == A->S.nrow, "Chebyshev: not set up for this matrix");
+  ISPH_REQUIRE(K >= 2 && K <= 4 && cheb_multi_ok(A, C), "Chebyshev: no K-vector form for this polynomial, matrix or K");
+  const Sell &S = A->S;
+  const int d = C->degree, n = C->n;
+  const size_t ld = C->multi_ld(), nbytes = sizeof(double) * (size_t)(n > 0 ? n : 0);
+  ISPH_CHECK(C->wm.reserve(ld * (size_t)K));
+  ISPH_CHECK(C->tm.reserve(ld * (size_t)K));
+  double *W[4], *T[4];
+  for (int k = 0; k < 4; ++k) { W[k] = C->wm.p + ld * (size_t)(k < K ? k : 0); T[k] = C->tm.p + ld * (size_t)(k < K ? k : 0); }
+  auto at = [K](const double *const *v, int k) { return v[k < K ? k : 0]; };
+  bool in_y;   // where the current iterates are: the callers' y_k, or T
+  int k0;      // first step that needs a product
+  if (zero_guess || r0s) {
+    in_y = (d - 1) % 2 == 0;   // d - 1 products follow: an even number ends where it starts
+    if (n > 0) {
+      ChebFirstVecs V;
+      uintptr_t bits = 0;
+      for (int k = 0; k < 4; ++k) {
+        V.r[k] = at(zero_guess ? bs : r0s, k);
+        V.yin[k] = zero_guess ? nullptr : ys[k < K ? k : 0];
+        V.w[k] = W[k];
+        V.yout[k] = in_y ? ys[k < K ? k : 0] : T[k];
+        bits |= reinterpret_cast<uintptr_t>(V.r[k]) | reinterpret_cast<uintptr_t>(V.yin[k]) | reinterpret_cast<uintptr_t>(V.yout[k]);
+      }
+      if ((bits & 15) == 0) cheb_first_multi_launch<true>(ctx, C, K, stream_grid((n + 1) / 2), V);   // (dinv, wm, tm: the pool's)
+      else cheb_first_multi_launch<false>(ctx, C, K, stream_grid(n), V);
+    }
+    k0 = 1;
+  } else {
+    in_y = true;
+    k0 = 0;
+  }
+  const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
+  for (int k = k0; k < d; ++k) {
+    ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);   // a sweep of the caller's operator, like cheb_step's
+    ChebMultiVecs V;
+    for (int j = 0; j < 4; ++j) {
+      double *yj = ys[j < K ? j : 0];
+      V.y[j] = in_y ? yj : T[j];
+      V.yout[j] = in_y ? T[j] : yj;
+      V.b[j] = at(bs, j);
+      V.w[j] = W[j];
+    }
+    if (C->value_bits == 32) cheb_step_multi_launch<float>(ctx, S, c16, K, (const float *)C->val32.p, (const double *)C->dinv.p, V, C->c1[k], C->c2[k]);
+    else cheb_step_multi_launch<double>(ctx, S, c16, K, (const double *)S.val.p, (const double *)C->dinv.p, V, C->c1[k], C->c2[k]);
+    in_y = !in_y;
+  }
+  if (!in_y && nbytes > 0)   // (a guess and an odd number of products)
+    for (int k = 0; k < K; ++k) ISPH_CHECK_HIP(hipMemcpyAsync(ys[k], T[k], nbytes, hipMemcpyDeviceToDevice, ctx->stream));
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }

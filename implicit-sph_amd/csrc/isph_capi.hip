@@ -125,10 +125,41 @@ int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, double *z
   return ilu_apply(ctx, M->ilu, r, z);
 }
 
-// K applications of one preconditioner: block ILU(k) sweeps its factor stream once for all vectors
+// whether K vectors share the sweeps of M (isph_prec_multi_path).  Block ILU(k): 2..4 vectors in one sweep of the factor
+// stream (ilu_apply_multi decides on the LDS a workgroup gets; this repeats its rule).  The Chebyshev polynomial and the
+// fp64 V cycle of the Chebyshev-smoothed AMG: any K >= 2, in groups of up to kPrecMultiMax.
+constexpr int kPrecMultiMax = 4;
+bool prec_multi_shared(const isph_prec *M, int K) {
+  if (!M || K < 2 || M->multi_single) return false;
+  if (M->type == 2 && M->ilu) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
+      v = 64 * 1024;
+    return K <= 4 && M->ilu->n > 0 && sizeof(double) * (size_t)(K + 1) * (size_t)M->ilu->B * 4 <= (size_t)v;
+  }
+  if (M->type == 6) return cheb_multi_ok(M->cheb_A, M->cheb);
+  if (M->type == 3) return amg_multi_ok(M->amg);
+  return false;
+}
+
+// K applications of one preconditioner: block ILU(k) sweeps its factor stream once for all vectors, the Chebyshev
+// polynomial and the Chebyshev-smoothed fp64 V cycle sweep every operator once per group of up to four vectors
+// (cheb_apply_multi, amg_apply_multi).  Everything else -- and everything under ISPH_PREC_MULTI_SINGLE=1 -- applies the
+// vectors one after the other; the bits are the same either way.
 int prec_apply_multi_dev(isph_ctx *ctx, const isph_prec *M, int K, const double *const *rs, double *const *zs) {
   ISPH_REQUIRE(M != nullptr, "preconditioner is NULL");
-  if (M->type == 2 && M->ilu) return ilu_apply_multi(ctx, M->ilu, K, rs, zs);
+  if (!M->multi_single && M->type == 2 && M->ilu) return ilu_apply_multi(ctx, M->ilu, K, rs, zs);
+  if ((M->type == 6 || M->type == 3) && prec_multi_shared(M, K)) {
+    ProfScope prof(ctx, PROF_PREC_APPLY);
+    for (int k0 = 0; k0 < K; k0 += kPrecMultiMax) {
+      const int g = std::min(kPrecMultiMax, K - k0);
+      if (g == 1) ISPH_CHECK(M->type == 6 ? cheb_apply(ctx, M->cheb_A, M->cheb, rs[k0], zs[k0], /*zero_guess=*/true)
+                                          : amg_apply(ctx, M->amg, rs[k0], zs[k0]));
+      else if (M->type == 6) ISPH_CHECK(cheb_apply_multi(ctx, M->cheb_A, M->cheb, g, rs + k0, zs + k0, /*zero_guess=*/true));
+      else ISPH_CHECK(amg_apply_multi(ctx, M->amg, g, rs + k0, zs + k0));
+    }
+    return ISPH_SUCCESS;
+  }
   for (int k = 0; k < K; ++k) ISPH_CHECK(prec_apply_dev(ctx, M, rs[k], zs[k]));
   return ISPH_SUCCESS;
 }
@@ -1521,6 +1552,62 @@ int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r, double *
   ISPH_CHECK_HIP(hipMemcpyAsync(ctx->xdev.p, r, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
   ISPH_CHECK(prec_apply_dev(ctx, M, ctx->xdev.p, ctx->bdev.p));
   ISPH_CHECK_HIP(hipMemcpyAsync(z, ctx->bdev.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  return prec_health(ctx, M);
+}
+
+int isph_prec_multi_path(isph_ctx *ctx, const isph_prec *M, int nvec) {
+  if (!ctx || !M) return 0;
+  return prec_multi_shared(M, nvec) ? 1 : 0;
+}
+
+int isph_prec_apply_multi(isph_ctx *ctx, const isph_prec *M, int nvec, const double *r, double *z, int lda, int on_device) {
+  ISPH_REQUIRE(ctx && M && r && z, "NULL argument");
+  ISPH_REQUIRE(nvec >= 1, "isph_prec_apply_multi: nvec must be at least 1");
+  ISPH_REQUIRE(lda >= M->n, "isph_prec_apply_multi: lda must be at least the number of rows");
+  const int n = M->n;
+  if (n == 0) return ISPH_SUCCESS;
+  const size_t K = (size_t)nvec, ldd = ((size_t)n + 64 + 1) & ~(size_t)1, rowbytes = sizeof(double) * (size_t)n;
+  const bool ordered = (bool)M->order;
+  // host operands: one strided copy each way (the padding rows of z are not written); the matrix' own numbering: the
+  // vectors are gathered into it and the results scattered back, as isph_prec_apply does
+  DevTmp<double> rin, ri, zi;
+  const double *dr = r;
+  double *dz = z;
+  size_t ldr = (size_t)lda, ldz = (size_t)lda;
+  if (!on_device) {
+    ISPH_REQUIRE(!is_device_pointer(r) && !is_device_pointer(z), "device pointer passed with on_device = 0");
+    ISPH_CHECK(rin.reserve(ldd * K));
+    ISPH_CHECK_HIP(hipMemcpy2DAsync(rin.p, sizeof(double) * ldd, r, sizeof(double) * (size_t)lda, rowbytes, K, hipMemcpyHostToDevice, ctx->stream));
+    dr = rin.p; ldr = ldd;
+  }
+  if (ordered) {
+    ISPH_CHECK(ri.reserve(ldd * K));
+    for (size_t k = 0; k < K; ++k)
+      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid((long long)n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1,
+                         (const int *)M->order->perm.p, dr + k * ldr, ri.p + k * ldd);
+    dr = ri.p; ldr = ldd;
+  }
+  if (ordered || !on_device) {
+    ISPH_CHECK(zi.reserve(ldd * K));
+    dz = zi.p; ldz = ldd;
+  }
+  std::vector<const double *> rs(K);
+  std::vector<double *> zs(K);
+  for (size_t k = 0; k < K; ++k) { rs[k] = dr + k * ldr; zs[k] = dz + k * ldz; }
+  ISPH_CHECK(prec_apply_multi_dev(ctx, M, nvec, rs.data(), zs.data()));
+  if (!ordered && on_device) return ISPH_SUCCESS;
+  if (ordered) {   // back to the caller's numbering: into z itself on the device, into the staged r otherwise
+    double *out = on_device ? z : rin.p;
+    const size_t ldo = on_device ? (size_t)lda : ldd;
+    for (size_t k = 0; k < K; ++k)
+      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, n, (const int *)M->order->perm.p,
+                         (const double *)(zi.p + k * ldd), out + k * ldo);
+    dz = out;
+  }
+  if (!on_device)
+    ISPH_CHECK_HIP(hipMemcpy2DAsync(z, sizeof(double) * (size_t)lda, dz, sizeof(double) * ldd, rowbytes, K, hipMemcpyDeviceToHost, ctx->stream));
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   ISPH_CHECK_HIP(hipGetLastError());
   return prec_health(ctx, M);

@@ -405,6 +405,16 @@ template <class VT> struct SellPair;
 template <> struct SellPair<double> { typedef double2 type; };
 template <> struct SellPair<float> { typedef float2 type; };
 
+// the epilogue of the AMG cycle, y = badd + alpha (A x) -- residual b - A x, corrections x += P e, r -= (A P) e -- with the
+// bits of the product followed by the vector kernel it replaces (badd may be y itself).  ONE expression for the single
+// and the K-vector kernels: whatever the compiler contracts here, it contracts in all of them.
+template <class XT>
+__device__ __forceinline__ double sell_epilogue(double r, double alpha, const XT *badd, int row, int nrow) {
+  if (alpha != 1.0) r *= alpha;
+  if (badd != nullptr && row < nrow) r += (double)badd[row];
+  return r;
+}
+
 template <int UNROLL, bool DOT, bool NT = false, bool LIST = false, bool GHOST = false, class VT = double, class XT = double,
           class YT = XT>
 __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int nblocks_padded,
@@ -463,11 +473,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv(int nrow, int nslices, int
     acc1 = fma((double)vv.y, x_at<GHOST>(x, xg, nrow, cc.y), acc1);
   }
   const int row = slice * kSlice + lane;
-  double r = acc0 + acc1;
-  // epilogue of the AMG cycle: y = badd + alpha (A x) -- residual b - A x, corrections x += P e, r -= (A P) e -- with the
-  // bits of the product followed by the vector kernel it replaces (badd may be y itself)
-  if (alpha != 1.0) r *= alpha;
-  if (badd != nullptr && row < nrow) r += (double)badd[row];
+  const double r = sell_epilogue(acc0 + acc1, alpha, badd, row, nrow);
   if (row < nrow) y[row] = (YT)r;
   if (DOT) {
     const double d = wave_sum(row < nrow ? r * nvec[row] : 0.0);
@@ -603,11 +609,7 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmv16(int nrow, int nslices, i
     acc1 = fma((double)vv.y, x_at<GHOST>(x, xg, nrow, tw[hi >> 10] | (int)(hi & 1023u)), acc1);
   }
   const int row = slice * kSlice + lane;
-  double r = acc0 + acc1;
-  // epilogue of the AMG cycle: y = badd + alpha (A x) -- residual b - A x, corrections x += P e, r -= (A P) e -- with the
-  // bits of the product followed by the vector kernel it replaces (badd may be y itself)
-  if (alpha != 1.0) r *= alpha;
-  if (badd != nullptr && row < nrow) r += (double)badd[row];
+  const double r = sell_epilogue(acc0 + acc1, alpha, badd, row, nrow);
   if (row < nrow) y[row] = (YT)r;
   if (DOT) {
     const double d = wave_sum(row < nrow ? r * nvec[row] : 0.0);
@@ -687,6 +689,117 @@ __global__ __launch_bounds__(kBlock) void k_sell_spmm16(int nrow, int nslices, i
   if (row < nrow) {
 #pragma unroll
     for (int k = 0; k < NV; ++k) V.y[k][row] = acc0[k] + acc1[k];
+  }
+}
+
+// ---- K-vector forms for the preconditioners (chebyshev.hpp, amg.hpp) ---------------------------------------------------
+// The row sums (A x_k)_row, k < NV, of one slice in one walk: values (VT = double, or the float plane of a Chebyshev
+// preconditioner) and columns are loaded once per entry, every vector does its own gather and keeps its own acc0 / acc1
+// fma chain over the even / odd positions -- the chains of k_sell_spmv / k_sell_spmv16 entry by entry, so sum[k] has the
+// bits of the single kernels' acc0 + acc1 (the unroll only changes how many loads are in flight, never the order of a
+// chain).  C16: cols are the 16-bit windowed columns and tw the wave's window table in LDS; otherwise 32-bit columns.
+// No halo form: the callers route a matrix with ghost columns to the single kernels.
+// UNROLL 4 as in k_sell_spmm16: 2 x UNROLL gathers per vector in flight per lane, the vectors one after the other.  The
+// instances compile to 74 .. 88 VGPRs (5 or 6 waves per SIMD, what the single kernels have) and none uses scratch
+// (docs/kernels_detail.md, profiles/prec_multi_kernel_resource_usage.txt).
+constexpr int kSellMultiUnroll = 4;
+template <bool C16, class VT, int NV>
+__device__ __forceinline__ void sell_rowsums_multi(const int *__restrict__ tw, long long off, int npair, int lane,
+                                                   const void *__restrict__ cols, const VT *__restrict__ sval,
+                                                   const double *const (&x)[4], double (&sum)[NV]) {
+  constexpr int UNROLL = kSellMultiUnroll;
+  typedef typename SellPair<VT>::type VT2;
+  const VT2 *__restrict__ v = reinterpret_cast<const VT2 *>(sval + off) + lane;
+  const unsigned *__restrict__ c16 = reinterpret_cast<const unsigned *>(static_cast<const unsigned short *>(cols) + off) + lane;
+  const int2 *__restrict__ c32 = reinterpret_cast<const int2 *>(static_cast<const int *>(cols) + off) + lane;
+  double acc0[NV], acc1[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) { acc0[k] = 0.0; acc1[k] = 0.0; }
+  int q = 0;
+  for (; q + UNROLL <= npair; q += UNROLL) {
+    VT2 vv[UNROLL];
+    int ca[UNROLL], cb[UNROLL];
+#pragma unroll
+    for (int u = 0; u < UNROLL; ++u) {
+      vv[u].x = __builtin_nontemporal_load(&v[(q + u) * 64].x);
+      vv[u].y = __builtin_nontemporal_load(&v[(q + u) * 64].y);
+      if (C16) {
+        const unsigned cc = __builtin_nontemporal_load(&c16[(q + u) * 64]);
+        const unsigned lo = cc & 0xffffu, hi = cc >> 16;
+        ca[u] = tw[lo >> 10] | (int)(lo & 1023u);
+        cb[u] = tw[hi >> 10] | (int)(hi & 1023u);
+      } else {
+        ca[u] = __builtin_nontemporal_load(&c32[(q + u) * 64].x);
+        cb[u] = __builtin_nontemporal_load(&c32[(q + u) * 64].y);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      double xa[UNROLL], xb[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) { xa[u] = x[k][ca[u]]; xb[u] = x[k][cb[u]]; }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        acc0[k] = fma((double)vv[u].x, xa[u], acc0[k]);
+        acc1[k] = fma((double)vv[u].y, xb[u], acc1[k]);
+      }
+    }
+  }
+  for (; q < npair; ++q) {
+    const VT2 vv = v[q * 64];
+    int ca, cb;
+    if (C16) {
+      const unsigned cc = c16[q * 64];
+      const unsigned lo = cc & 0xffffu, hi = cc >> 16;
+      ca = tw[lo >> 10] | (int)(lo & 1023u);
+      cb = tw[hi >> 10] | (int)(hi & 1023u);
+    } else {
+      const int2 cc = c32[q * 64];
+      ca = cc.x;
+      cb = cc.y;
+    }
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      acc0[k] = fma((double)vv.x, x[k][ca], acc0[k]);
+      acc1[k] = fma((double)vv.y, x[k][cb], acc1[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NV; ++k) sum[k] = acc0[k] + acc1[k];
+}
+
+// y_k = badd_k + alpha (A x_k), k < NV, in one sweep of the matrix: the K-vector form of the AMG cycle's three products
+// (residual, prolongation, residual update), same bits as NV launches of k_sell_spmv16 / k_sell_spmv with badd and alpha
+// (sell_epilogue is theirs).  badd_k may be y_k (every lane reads its own row before it writes it).
+struct SpmmAxpbVecs {
+  const double *x[4];
+  const double *badd[4];
+  double *y[4];
+};
+template <bool C16, int NV>
+__global__ __launch_bounds__(kBlock) void k_sell_spmm_axpb(int nrow, int nslices, int nblocks_padded,
+                                                           const long long *__restrict__ slice_off,
+                                                           const void *__restrict__ cols, const int *__restrict__ wtab,
+                                                           const double *__restrict__ sval, SpmmAxpbVecs V, double alpha) {
+  __shared__ int tab[C16 ? kBlock / kWave : 1][64];
+  const int b = xcd_remap(blockIdx.x, nblocks_padded);
+  const int wave = threadIdx.x >> 6;
+  const int slice = b * (kBlock / kWave) + wave;
+  if (slice >= nslices) return;
+  const int lane = threadIdx.x & 63;
+  if (C16) {
+    tab[wave][lane] = wtab[(long long)slice * 64 + lane] << 10;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  const long long off = slice_off[slice];
+  const int npair = (int)((slice_off[slice + 1] - off) >> 7);
+  double sum[NV];
+  sell_rowsums_multi<C16, double, NV>(tab[C16 ? wave : 0], off, npair, lane, cols, sval, V.x, sum);
+  const int row = slice * kSlice + lane;
+  if (row < nrow) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) V.y[k][row] = sell_epilogue(sum[k], alpha, V.badd[k], row, nrow);
   }
 }
 

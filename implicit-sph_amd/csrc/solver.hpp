@@ -251,6 +251,41 @@ inline int spmm_dev(isph_ctx *ctx, const isph_mat *A, int K, const double *const
   return ISPH_SUCCESS;
 }
 
+// true when the products of A exchange ghost values (the condition of spmv_dev): such a matrix has no K-vector form
+inline bool mat_has_halo(const isph_mat *A) { return !A->local && (A->S.ncol != A->S.nrow || A->halo.nsend > 0); }
+
+// y_k = badd_k + alpha (A x_k), k < K, 2 <= K <= 4, for a matrix without a halo: one sweep of the matrix for all vectors
+// (k_sell_spmm_axpb), with the column form spmv_dev would take and the bits of K calls of spmv_dev(.., badd_k, alpha).
+inline int spmm_axpb_dev(isph_ctx *ctx, const isph_mat *A, int K, const double *const *xs, double *const *ys,
+                         const double *const *badds, double alpha) {
+  const Sell &S = A->S;
+  ISPH_REQUIRE(K >= 2 && K <= 4 && !mat_has_halo(A), "spmm: the K-vector product takes 2 to 4 vectors and a matrix without a halo");
+  const bool c16 = !A->local && !A->aux && sell_cols16(ctx, S);
+  ProfScope prof((A->local || A->aux) ? nullptr : ctx, PROF_SPMV);
+  SpmmAxpbVecs V;
+  for (int k = 0; k < 4; ++k) { V.x[k] = xs[k < K ? k : 0]; V.y[k] = ys[k < K ? k : 0]; V.badd[k] = badds[k < K ? k : 0]; }
+  int nbp = 0;
+  const int grid = spmv_grid(S.nslices, &nbp);
+#define ISPH_SPMM_AXPB(C16, NV, COLS, WTAB)                                                                                  \
+  hipLaunchKernelGGL((k_sell_spmm_axpb<C16, NV>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices, nbp,          \
+                     (const long long *)S.slice_off.p, (const void *)(COLS), (const int *)(WTAB), (const double *)S.val.p, V, alpha)
+  if (S.nslices > 0) {
+    if (c16) {
+      if (K == 2) ISPH_SPMM_AXPB(true, 2, S.col16.p, S.wtab.p);
+      else if (K == 3) ISPH_SPMM_AXPB(true, 3, S.col16.p, S.wtab.p);
+      else ISPH_SPMM_AXPB(true, 4, S.col16.p, S.wtab.p);
+    } else {
+      if (K == 2) ISPH_SPMM_AXPB(false, 2, S.col.p, nullptr);
+      else if (K == 3) ISPH_SPMM_AXPB(false, 3, S.col.p, nullptr);
+      else ISPH_SPMM_AXPB(false, 4, S.col.p, nullptr);
+    }
+  }
+#undef ISPH_SPMM_AXPB
+  prof.end();
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
 struct LinOp {
   isph_ctx *ctx;
   const isph_mat *A;

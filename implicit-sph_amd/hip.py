@@ -20,6 +20,7 @@ EXPORTS = [
     "isph_ctx_create", "isph_comm_unique_id", "isph_ctx_create_dist", "isph_ctx_create_hostcomm", "isph_ctx_sync", "isph_ctx_destroy", "isph_pool_trim", "isph_pool_set_cap", "isph_set_exact_stream_threshold", "isph_pool_cached_bytes", "isph_pool_info", "isph_halo_create", "isph_halo_forward", "isph_halo_destroy", "isph_prec_create_overlap",
     "isph_last_error", "isph_mat_create_csr", "isph_mat_create_csr_bjacobi", "isph_mat_create_csr_blocks", "isph_mat_create_csr_coords", "isph_mat_create_csr_coords_bjacobi", "isph_ingress_info", "isph_mat_set_halo", "isph_mat_info", "isph_mat_export_csr", "isph_mat_export_rows", "isph_mat_column_bits",
     "isph_mat_destroy", "isph_spmv", "isph_spmv_time", "isph_prec_create", "isph_prec_create_blocks", "isph_prec_create_blocks_fill", "isph_prec_apply",
+    "isph_prec_apply_multi", "isph_prec_multi_path",
     "isph_prec_export_ilu", "isph_prec_nnz", "isph_prec_info", "isph_prec_destroy", "isph_solver_params_default", "isph_solve",
     "isph_ctx_set_profile", "isph_ctx_hold_neighbours", "isph_ctx_profile_read", "isph_ctx_set_ordering", "isph_ctx_set_periodic_box", "isph_mat_ordering_info", "isph_mat_ordering", "isph_mat_ordering_faces", "isph_ctx_halo_profile_read", "isph_ctx_comm_info", "isph_device_identity", "isph_assemble_poisson", "isph_assemble_helmholtz", "isph_assemble_solute_transport", "isph_assemble_applied_potential", "isph_compute_volumes", "isph_compute_pnd", "isph_compute_corrections", "isph_gradient", "isph_divergence", "isph_correct_velocity_pressure",
     "isph_advance_begin", "isph_advance_end", "isph_compute_shift", "isph_apply_shift", "isph_shift_particles",
@@ -199,6 +200,8 @@ def lib():
         L.isph_prec_create_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         L.isph_prec_create_blocks_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_prec_apply_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.isph_prec_multi_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.isph_prec_export_ilu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_destroy.argtypes = [C.c_void_p]
         L.isph_prec_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -758,6 +761,46 @@ class Precond:
                 z = np.zeros(self.n)
         _check(lib().isph_prec_apply(self.ctx.h, self.h, _ptr(r), _ptr(z), _on_device(r, z)))
         return z
+
+    def apply_multi(self, R, Z=None, nvec=None, lda=None):
+        """isph_prec_apply_multi: z_k = M^-1 r_k for several vectors, sharing the sweeps of M where the type has a one-sweep
+        form (multi_path) -- the bits of one apply() per vector either way.  R (and Z) are column-major [lda x nvec] like
+        the multivectors of solve(): a 2-D array / tensor [nvec, lda], or a flat one with nvec (and lda, default n) given.
+        Rows n .. lda of Z are not written; a Z made here starts as zeros.  The element counts are checked before the call."""
+        R = _f64(R)
+        shape = tuple(R.shape)
+        if len(shape) == 2:
+            if nvec is None:
+                nvec = shape[0]
+            if lda is None:
+                lda = shape[1]
+        if nvec is None:
+            raise OperandError("R is flat: nvec is needed")
+        nvec, lda = int(nvec), int(self.n if lda is None else lda)
+        if nvec < 1:
+            raise OperandError("nvec = %d: at least one vector is needed" % nvec)
+        if lda < self.n:
+            raise OperandError("lda = %d is below the %d rows of the preconditioner" % (lda, self.n))
+        if len(shape) == 2 and (shape[0] != nvec or shape[1] != lda):
+            raise OperandError("R is %r, not [nvec = %d, lda = %d]" % (shape, nvec, lda))
+        need = lda * (nvec - 1) + self.n
+        _need(R, need, "R [lda x nvec]")
+        if Z is None:
+            if _is_torch(R):
+                import torch
+                Z = torch.zeros_like(R)
+            else:
+                Z = np.zeros_like(R)
+        else:
+            Z = _f64(Z)
+        _need(Z, need, "Z [lda x nvec]")
+        _check(lib().isph_prec_apply_multi(self.ctx.h, self.h, nvec, _ptr(R), _ptr(Z), lda, _on_device(R, Z)))
+        return Z
+
+    def multi_path(self, nvec):
+        """isph_prec_multi_path: 1 when nvec vectors share the sweeps of this preconditioner (apply_multi, solve with
+        nvec > 1, solve_block), 0 when they are applied one after the other"""
+        return int(lib().isph_prec_multi_path(self.ctx.h, self.h, int(nvec)))
 
     def refactor(self, A):
         """isph_prec_refactor: the numeric factorisation of a "bjacobi-ilu<k>" again on the (updated) values of A; pattern,

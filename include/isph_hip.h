@@ -403,6 +403,25 @@ int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r /*[h|d]*/,
                     double *z /*[h|d]*/, int on_device);
+/* z_k = M^-1 r_k for nvec vectors: r and z are column-major [lda x nvec] like the multivectors of isph_solve, nvec >= 1
+ * and lda >= n (anything else is an error); rows n .. lda of z are not written.  Any preconditioner type.  Host operands
+ * cross the link in one strided copy each way.
+ * Where the type has a one-sweep form the vectors share the sweeps of M, with the bits of nvec calls of isph_prec_apply:
+ *   - block ILU(k): 2..4 vectors in one sweep of the factor stream;
+ *   - the Chebyshev polynomial (isph_prec_create_chebyshev, either value_bits) and the SA-AMG with smoother = 2 and
+ *     cycle_bits = 64 (either cheb_value_bits): every step of the polynomial, every A_l, R_l, P_l, A_l P_l and the dense
+ *     coarse inverse is read once per group of up to 4 vectors; the matrix values and columns are loaded once per entry,
+ *     every vector does its own gather and runs the single kernels' operations in their order.
+ * Applied one vector after the other: every other type, the Gauss-Seidel smoothers, cycle_bits = 32, a matrix with a halo
+ * plan or ghost columns, a hierarchy across ranks, ISPH_CHEB_UNFUSED=1, nvec = 1, and any preconditioner created under
+ * ISPH_PREC_MULTI_SINGLE=1 (the cross-check and the timing baseline of the one-sweep forms).  isph_solve with nvec > 1
+ * and isph_solve_block apply their preconditioner by the same rule.  The K-fold work vectors come from the pool at the
+ * first application to several vectors and go back with the preconditioner. */
+int isph_prec_apply_multi(isph_ctx *ctx, const isph_prec *M, int nvec, const double *r /*[h|d] lda x nvec*/,
+                          double *z /*[h|d] lda x nvec*/, int lda, int on_device);
+/* 1 when nvec vectors share the sweeps of M in isph_prec_apply_multi / isph_solve / isph_solve_block, 0 when they are
+ * applied one after the other (read-only, in the spirit of isph_prec_amg_path). */
+int isph_prec_multi_path(isph_ctx *ctx, const isph_prec *M, int nvec);
 /* Export the factor as CSR (strict L, D, strict U in one pattern == A's
  * in-block pattern, columns sorted) for parity tests. */
 int isph_prec_export_ilu(isph_ctx *ctx, const isph_prec *M, int *rowptr, int *colidx, double *val);
