@@ -188,6 +188,22 @@ def build_cpp_amg_cycle_f32_test(force=False):
     return CPP_AMG_CYCLE_F32_TEST
 
 
+CPP_RECYCLE_TEST = os.path.join(ROOT, "tests", "cpp", "test_recycle")
+
+
+def build_cpp_recycle_test(force=False):
+    """C++ driver of SolverLin_Belos' key "isph: recycle across solves" (host/*.h), linked like build_cpp_test; used by
+    tests/test_gpu_gcrodr_recycle.py."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_recycle.cpp")
+    host = os.path.join(PKG, "host")
+    deps = [src] + [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(INC, "isph_hip.h")]
+    if force or _stale(CPP_RECYCLE_TEST, deps):
+        build_hip()
+        _run(["g++", "-O2", "-std=c++17", "-I", INC, "-I", host, "-o", CPP_RECYCLE_TEST, src,
+              "-L", PKG, "-lisph_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return CPP_RECYCLE_TEST
+
+
 RANK_THREADS = os.path.join(ROOT, "tests", "cpp", "librank_threads.so")
 
 

@@ -99,6 +99,37 @@ inline void least_squares(int r, int c, const std::vector<double> &A, const std:
   }
 }
 
+// G = R^T R (G n x n symmetric, R upper triangular); false when a pivot is not a positive finite number
+inline bool cholesky_upper(int n, const std::vector<double> &G, std::vector<double> &R) {
+  R.assign((size_t)n * n, 0.0);
+  for (int i = 0; i < n; ++i) {
+    double d = G[(size_t)i * n + i];
+    for (int l = 0; l < i; ++l) d -= R[(size_t)l * n + i] * R[(size_t)l * n + i];
+    if (!(std::isfinite(d) && d > 0.0)) return false;
+    const double rii = std::sqrt(d);
+    R[(size_t)i * n + i] = rii;
+    for (int j = i + 1; j < n; ++j) {
+      double s = G[(size_t)i * n + j];
+      for (int l = 0; l < i; ++l) s -= R[(size_t)l * n + i] * R[(size_t)l * n + j];
+      R[(size_t)i * n + j] = s / rii;
+    }
+  }
+  return true;
+}
+
+// inverse of an upper triangular matrix with a non-zero diagonal (upper triangular again)
+inline void upper_inverse(int n, const std::vector<double> &R, std::vector<double> &Ri) {
+  Ri.assign((size_t)n * n, 0.0);
+  for (int c = 0; c < n; ++c) {
+    Ri[(size_t)c * n + c] = 1.0 / R[(size_t)c * n + c];
+    for (int i = c - 1; i >= 0; --i) {
+      double s = 0.0;
+      for (int l = i + 1; l <= c; ++l) s -= R[(size_t)i * n + l] * Ri[(size_t)l * n + c];
+      Ri[(size_t)i * n + c] = s / R[(size_t)i * n + i];
+    }
+  }
+}
+
 // eigenvalues lam[n] and eigenvectors X (n x n, column k belongs to lam[k]) of a general real matrix
 inline bool eig_general(int n, const std::vector<double> &A, std::vector<cplx> &lam, std::vector<cplx> &X) {
   std::vector<cplx> H((size_t)n * n), Z((size_t)n * n, cplx(0.0));

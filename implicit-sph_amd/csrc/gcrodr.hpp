@@ -9,10 +9,28 @@
 // same projected one as in solveProblem.  One iteration = one Arnoldi step; convergence = implicit residual / |r0|.
 // oracle/gcrodr.py restates the same algorithm with numpy/LAPACK; the projected dense problems here use
 // dense_small.hpp.  Vector work reuses the Krylov kernels (multi-dot, multi-axpy); this solver type is not on the
-// bench path and trades a few extra sweeps per cycle for simplicity.
+// bench path and, without a recycle handle, trades a few extra sweeps per cycle for simplicity.
+//
+// Carried recycle space (isph_solve_recycle with a handle, RecycleRun below; restated in
+// tests/gcrodr_recycle_reference.py).  Unlike the reference, a solve may start from the U its predecessor left:
+//   entry   Cn = Op U0 (one application per vector, in groups of up to four where the operator has a several-vector
+//           form), Cholesky-QR twice (G = Cn^T Cn = R^T R, C <- Cn R^-1, U <- U0 R^-1); the space is dropped and the solve
+//           is the fresh one when a pivot is not positive and finite or the second Gram matrix has kk max|G2 - I| > 1/2
+//           (beyond that the first pass left singular values outside [0.71, 1.22] and the second no longer restores
+//           orthogonality to round-off).  Then c = C^T r0, t = U c, r = r0 - C c; the convergence scale stays |r0|.
+//   exit    the recycle step also runs after the last cycle, converged or not; a first cycle of j <= k steps keeps nothing.
+//   columns the next right-hand side of the same call starts from U and C as the previous one left them.
+// On that path the recycle step's dense contractions go through tall_skinny.hpp (one sweep of the block per product);
+// ISPH_GCRODR_UNFUSED=1, read when the handle is created, keeps the per-column launches there (cross-check and timing
+// baseline).  Without a handle the launches are the ones this file always made.
+// Measured at 100^3 over three consecutive pressure systems, GCRO-DR(50, 10), create + solve (profiles/recycle_100cubed.txt):
+// Jacobi 10-13 steps + 10 applications instead of 43-44 steps, 25.8 against 42.5 ms of FGMRES(50); chebyshev3 5-6 + 10
+// instead of 22, 38.9 against 48.5 ms; bjacobi-ilu0 61-69 + 10 instead of 70-71 and SLOWER, 154.5 against 113.4 ms.  Off by
+// default.
 #pragma once
 #include "dense_small.hpp"
 #include "solver.hpp"
+#include "tall_skinny.hpp"
 
 namespace isph {
 
@@ -43,7 +61,21 @@ inline int combine(isph_ctx *ctx, int n, int nin, const double *Basis, long long
   return ISPH_SUCCESS;
 }
 
-inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver_params *prm, isph_solve_info *info) {
+// The recycle space of one isph_solve_recycle call, in the rows the solve works in: U and C hold (k + 1) vectors of
+// ld = n rounded up to 64 each (the caller reserves them), kk of them in use.  have_C: C = Op U, C^T C = I already holds
+// (the previous right-hand side of the same call left both).
+struct RecycleRun {
+  DevBuf<double> U, C;
+  int kk = 0;
+  bool have_C = false;
+  bool fused = true;       // tall_skinny.hpp kernels; false: the per-column launches (ISPH_GCRODR_UNFUSED=1)
+  bool started = false;    // out: a solve of this call started from the carried space
+  int reason = 0;          // out: 2 when the orthonormalisation guard dropped the space
+  long long apps = 0;      // out: operator applications spent on rebuilding C
+};
+
+inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver_params *prm, isph_solve_info *info,
+                  RecycleRun *rr = nullptr) {
   isph_ctx *ctx = op.ctx;
   const int n = op.n, m = prm->num_blocks, k = prm->num_recycled;
   ISPH_REQUIRE(m >= 2 && m <= 62, "Num Blocks must be in [2,62]");
@@ -51,7 +83,23 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
                                 "reference's default list 50/50 as well)");
   const long long ld = ((long long)n + 63) / 64 * 64;
   const int kc = k + 1;  // a complex pair that straddles the k-th slot is kept whole
-  DevTmp<double> Vb, Cb, Ub, Cn, Un, tb, rb, wb, zb, cbuf;
+  DevTmp<double> Vb, Cb, Ub, Cn, Un, tb, rb, wb, zb, cbuf, gscr;
+  // with a carried space U and C are the caller's blocks for the length of this solve (handed back below)
+  struct HandBack {
+    RecycleRun *rr;
+    DevBuf<double> &U, &C;
+    void done() {
+      if (!rr) return;
+      std::swap(rr->U, U);
+      std::swap(rr->C, C);
+      rr = nullptr;
+    }
+    ~HandBack() { done(); }
+  } hand_back{rr, Ub, Cb};
+  if (rr) {
+    std::swap(rr->U, static_cast<DevBuf<double> &>(Ub));
+    std::swap(rr->C, static_cast<DevBuf<double> &>(Cb));
+  }
   ISPH_CHECK(Vb.reserve((size_t)ld * (size_t)(m + 1)));
   ISPH_CHECK(Cb.reserve((size_t)ld * (size_t)kc));
   ISPH_CHECK(Ub.reserve((size_t)ld * (size_t)kc));
@@ -60,13 +108,14 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
   ISPH_CHECK(tb.reserve((size_t)ld));
   ISPH_CHECK(rb.reserve((size_t)ld));
   ISPH_CHECK(wb.reserve((size_t)ld));
-  ISPH_CHECK(zb.reserve((size_t)ld));
+  ISPH_CHECK(zb.reserve((size_t)ld * (size_t)(rr ? kMaxLockstep : 1)));
   double *V = Vb.p, *C = Cb.p, *U = Ub.p, *t = tb.p, *r = rb.p, *w = wb.p, *z = zb.p;
   const int sg = stream_grid(n);
   hipStream_t st = ctx->stream;
   auto release_all = [&]() {
+    hand_back.done();
     Vb.release(); Cb.release(); Ub.release(); Cn.release(); Un.release(); tb.release(); rb.release(); wb.release();
-    zb.release(); cbuf.release();
+    zb.release(); cbuf.release(); gscr.release();
   };
   GmresCycle cyc;  // the implicit residual only: the harmonic Ritz problem needs H unrotated, kept below
 
@@ -79,6 +128,101 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
   if (cyc.beta / cyc.scale <= prm->tol) info->converged = 1;
   int kk = 0;  // current size of the recycle space
   int rc = ISPH_SUCCESS;
+  const bool fused = rr && rr->fused;
+  bool c_valid = false;  // C = Op U with orthonormal columns
+  std::vector<double> gm;  // host copy of a block Gram matrix
+  if (rr && rr->kk > 0) {
+    kk = rr->kk;
+    c_valid = rr->have_C;
+  }
+  if (kk > 0 && !info->converged) {
+    if (!c_valid) {
+      // ---- C = Op U0, in groups that share the sweeps of M and A where both have a several-vector form
+      int i = 0;
+      if (!op.nvec && !op.blk) {
+        for (; kk - i >= 2 && rc == ISPH_SUCCESS; ) {
+          const int g = std::min(kMaxLockstep, kk - i);
+          const double *us[kMaxLockstep], *zin[kMaxLockstep];
+          double *zs[kMaxLockstep], *cs[kMaxLockstep];
+          for (int c = 0; c < g; ++c) {
+            us[c] = U + (long long)(i + c) * ld;
+            zs[c] = z + (long long)c * ld;
+            zin[c] = zs[c];
+            cs[c] = C + (long long)(i + c) * ld;
+          }
+          if (op.M) rc = prec_apply_multi_dev(ctx, op.M, g, us, zs);
+          else
+            for (int c = 0; c < g && rc == ISPH_SUCCESS; ++c) rc = op.prec(us[c], zs[c]);
+          if (rc == ISPH_SUCCESS) rc = spmm_dev(ctx, op.A, g, zin, cs);
+          i += g;
+        }
+      }
+      for (; i < kk && rc == ISPH_SUCCESS; ++i) {
+        rc = op.prec(U + (long long)i * ld, z);
+        if (rc == ISPH_SUCCESS) rc = op.apply(z, C + (long long)i * ld);
+      }
+      rr->apps += kk;
+      // ---- Cholesky-QR, twice
+      bool ok = true;
+      std::vector<double> R, Ri, col((size_t)kk);
+      for (int pass = 0; pass < 2 && ok && rc == ISPH_SUCCESS; ++pass) {
+        gm.assign((size_t)kk * kk, 0.0);
+        if (fused) rc = block_gram(ctx, n, kk, C, ld, 0, nullptr, ld, kk, C, ld, gm.data(), gscr, true);
+        else
+          for (int c = 0; c < kk && rc == ISPH_SUCCESS; ++c) {
+            rc = multi_dot_host(ctx, n, kk, C, ld, C + (long long)c * ld, col.data());
+            for (int a2 = 0; a2 < kk; ++a2) gm[(size_t)a2 * kk + c] = col[(size_t)a2];
+          }
+        if (rc != ISPH_SUCCESS) break;
+        if (pass == 1) {
+          double dev = 0.0;
+          for (int a2 = 0; a2 < kk; ++a2)
+            for (int c = 0; c < kk; ++c) {
+              const double d = std::fabs(gm[(size_t)a2 * kk + c] - (a2 == c ? 1.0 : 0.0));
+              if (!(d <= dev)) dev = d;  // a NaN sticks
+            }
+          if (!(kk * dev <= 0.5)) { ok = false; break; }
+        }
+        for (double v : gm) ok = ok && std::isfinite(v);
+        if (!ok || !dense::cholesky_upper(kk, gm, R)) { ok = false; break; }
+        dense::upper_inverse(kk, R, Ri);
+        if (fused) {
+          rc = tall_gemm_inplace(ctx, n, kk, C, ld, Ri.data(), cbuf);
+          if (rc == ISPH_SUCCESS) rc = tall_gemm_inplace(ctx, n, kk, U, ld, Ri.data(), cbuf);
+        } else {
+          for (int c = 0; c < kk && rc == ISPH_SUCCESS; ++c) {
+            for (int a2 = 0; a2 < kk; ++a2) col[(size_t)a2] = Ri[(size_t)a2 * kk + c];
+            rc = combine(ctx, n, kk, C, ld, col.data(), Cn.p + (long long)c * ld, false, cbuf);
+            if (rc == ISPH_SUCCESS) rc = combine(ctx, n, kk, U, ld, col.data(), Un.p + (long long)c * ld, false, cbuf);
+          }
+          std::swap(static_cast<DevBuf<double> &>(Cb), static_cast<DevBuf<double> &>(Cn));
+          std::swap(static_cast<DevBuf<double> &>(Ub), static_cast<DevBuf<double> &>(Un));
+          C = Cb.p;
+          U = Ub.p;
+        }
+      }
+      if (rc == ISPH_SUCCESS && !ok) {  // the guard: solve as if no space had been carried
+        kk = 0;
+        rr->reason = 2;
+      }
+      c_valid = rc == ISPH_SUCCESS && ok;
+    }
+    if (rc == ISPH_SUCCESS && kk > 0) {
+      // ---- c = C^T r0, t = U c, r = r0 - C c; the scale of the convergence test stays |r0|
+      std::vector<double> cv((size_t)kk);
+      rc = multi_dot_host(ctx, n, kk, C, ld, r, cv.data());
+      if (rc == ISPH_SUCCESS) rc = combine(ctx, n, kk, U, ld, cv.data(), t, true, cbuf);
+      for (double &v : cv) v = -v;
+      if (rc == ISPH_SUCCESS) rc = combine(ctx, n, kk, C, ld, cv.data(), r, true, cbuf);
+      double rn = 0.0;
+      if (rc == ISPH_SUCCESS) rc = norm_host(ctx, n, r, &rn);
+      if (rc == ISPH_SUCCESS) {
+        rr->started = true;
+        info->rel_res_implicit = rn / cyc.scale;
+        if (info->rel_res_implicit <= prm->tol) info->converged = 1;
+      }
+    }
+  }
 
   while (!info->converged && info->iters < prm->max_iters && rc == ISPH_SUCCESS) {
     const int steps = kk == 0 ? m : m - kk;
@@ -156,8 +300,15 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     if (rc == ISPH_SUCCESS && kk > 0) rc = combine(ctx, n, kk, C, ld, gy.data(), r, true, cbuf);
     if (rc == ISPH_SUCCESS) rc = combine(ctx, n, j + 1, V, ld, gy.data() + kk, r, true, cbuf);
     if (rc != ISPH_SUCCESS) break;
-    if (conv) { info->converged = 1; break; }
-    if (info->iters >= prm->max_iters || info->restarts >= prm->max_restarts) break;
+    if (conv) info->converged = 1;
+    // another cycle follows; with a carried space the recycle step also runs after the last cycle (`last`), and whatever
+    // keeps it from producing a space then leaves none instead of failing a solve that is over
+    const bool more = !conv && info->iters < prm->max_iters && info->restarts < prm->max_restarts;
+    const bool last = !more;
+    if (last && (!rr || (kk == 0 && j <= k))) {
+      if (rr && kk == 0) c_valid = false;
+      break;
+    }
     // ---- harmonic Ritz vectors -> new recycle space
     std::vector<double> P;
     int knew = 0;
@@ -168,19 +319,34 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
       for (int a2 = 0; a2 < j; ++a2)
         for (int c = 0; c < j; ++c) { HmT[(size_t)a2 * j + c] = H[(size_t)c * steps + a2]; Mh[(size_t)a2 * j + c] = H[(size_t)a2 * steps + c]; }
       f[(size_t)j - 1] = 1.0;
-      if (!dense::lu_solve(j, HmT, 1, f)) { rc = fail("GCRO-DR: singular Hessenberg matrix", __FILE__, __LINE__); break; }
+      if (!dense::lu_solve(j, HmT, 1, f)) {
+        if (last) { kk = 0; break; }
+        rc = fail("GCRO-DR: singular Hessenberg matrix", __FILE__, __LINE__);
+        break;
+      }
       const double h2 = H[(size_t)j * steps + (j - 1)] * H[(size_t)j * steps + (j - 1)];
       for (int a2 = 0; a2 < j; ++a2) Mh[(size_t)a2 * j + (j - 1)] += h2 * f[(size_t)a2];
-      if (!dense::eig_general(j, Mh, lam, X)) { rc = fail("GCRO-DR: eigenvalue iteration did not converge", __FILE__, __LINE__); break; }
+      if (!dense::eig_general(j, Mh, lam, X)) {
+        if (last) { kk = 0; break; }
+        rc = fail("GCRO-DR: eigenvalue iteration did not converge", __FILE__, __LINE__);
+        break;
+      }
       knew = dense::select_real_basis(j, lam, X, k, /*largest=*/false, P);
     } else {
       // G^T G z = theta G^T W^T Vh z  <=>  (G^T G)^-1 (G^T W^T Vh) z = (1/theta) z : largest |1/theta|
       std::vector<double> WtV((size_t)rows * cols, 0.0), col((size_t)std::max(kk, j + 1));
-      for (int i = 0; i < kk && rc == ISPH_SUCCESS; ++i) {
-        rc = multi_dot_host(ctx, n, kk, C, ld, U + (long long)i * ld, col.data());
-        for (int a2 = 0; a2 < kk; ++a2) WtV[(size_t)a2 * cols + i] = col[(size_t)a2] * dsc[(size_t)i];
-        if (rc == ISPH_SUCCESS) rc = multi_dot_host(ctx, n, j + 1, V, ld, U + (long long)i * ld, col.data());
-        for (int a2 = 0; a2 <= j; ++a2) WtV[(size_t)(kk + a2) * cols + i] = col[(size_t)a2] * dsc[(size_t)i];
+      if (fused) {  // W^T U, W = [C | V], in one sweep
+        gm.assign((size_t)rows * kk, 0.0);
+        rc = block_gram(ctx, n, kk, C, ld, j + 1, V, ld, kk, U, ld, gm.data(), gscr, true);
+        for (int a2 = 0; a2 < rows; ++a2)
+          for (int i = 0; i < kk; ++i) WtV[(size_t)a2 * cols + i] = gm[(size_t)a2 * kk + i] * dsc[(size_t)i];
+      } else {
+        for (int i = 0; i < kk && rc == ISPH_SUCCESS; ++i) {
+          rc = multi_dot_host(ctx, n, kk, C, ld, U + (long long)i * ld, col.data());
+          for (int a2 = 0; a2 < kk; ++a2) WtV[(size_t)a2 * cols + i] = col[(size_t)a2] * dsc[(size_t)i];
+          if (rc == ISPH_SUCCESS) rc = multi_dot_host(ctx, n, j + 1, V, ld, U + (long long)i * ld, col.data());
+          for (int a2 = 0; a2 <= j; ++a2) WtV[(size_t)(kk + a2) * cols + i] = col[(size_t)a2] * dsc[(size_t)i];
+        }
       }
       if (rc != ISPH_SUCCESS) break;
       for (int c = 0; c < j; ++c) WtV[(size_t)(kk + c) * cols + kk + c] = 1.0;
@@ -192,8 +358,16 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
           GtG[(size_t)a2 * cols + c] = s1;
           GtW[(size_t)a2 * cols + c] = s2;
         }
-      if (!dense::lu_solve(cols, GtG, cols, GtW)) { rc = fail("GCRO-DR: singular projected matrix", __FILE__, __LINE__); break; }
-      if (!dense::eig_general(cols, GtW, lam, X)) { rc = fail("GCRO-DR: eigenvalue iteration did not converge", __FILE__, __LINE__); break; }
+      if (!dense::lu_solve(cols, GtG, cols, GtW)) {
+        if (last) { kk = 0; c_valid = false; break; }
+        rc = fail("GCRO-DR: singular projected matrix", __FILE__, __LINE__);
+        break;
+      }
+      if (!dense::eig_general(cols, GtW, lam, X)) {
+        if (last) { kk = 0; c_valid = false; break; }
+        rc = fail("GCRO-DR: eigenvalue iteration did not converge", __FILE__, __LINE__);
+        break;
+      }
       knew = dense::select_real_basis(cols, lam, X, k, /*largest=*/true, P);
     }
     // [Q,R] = qr(G P)  (first cycle: G = Hbar), C = W Q, U = Vh P R^-1
@@ -214,7 +388,14 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
         for (int l = 0; l < c; ++l) s -= T[(size_t)a2 * knew + l] * R[(size_t)l * knew + c];
         T[(size_t)a2 * knew + c] = s / R[(size_t)c * knew + c];
       }
-    for (int c = 0; c < knew && rc == ISPH_SUCCESS; ++c) {
+    if (fused) {  // C = W Q and U = Vh P R^-1: one sweep of [C | V] and one of [U | V] for all columns
+      rc = tall_gemm(ctx, n, kk, C, ld, j + 1, V, ld, knew, Q.data(), Cn.p, ld, false, cbuf);
+      std::vector<double> cu((size_t)std::max(pr, 1) * knew);
+      for (int i = 0; i < pr; ++i)
+        for (int c = 0; c < knew; ++c) cu[(size_t)i * knew + c] = (i < kk ? dsc[(size_t)i] : 1.0) * T[(size_t)i * knew + c];
+      if (rc == ISPH_SUCCESS) rc = tall_gemm(ctx, n, kk, U, ld, pr - kk, V, ld, knew, cu.data(), Un.p, ld, false, cbuf);
+    }
+    for (int c = 0; c < knew && rc == ISPH_SUCCESS && !fused; ++c) {
       double *cn = Cn.p + (long long)c * ld, *un = Un.p + (long long)c * ld;
       for (int i = 0; i < rows; ++i) coef[(size_t)i] = Q[(size_t)i * knew + c];
       if (kk > 0) rc = combine(ctx, n, kk, C, ld, coef.data(), cn, false, cbuf);
@@ -231,7 +412,13 @@ inline int gcrodr(const LinOp &op, const double *b, double *x, const isph_solver
     C = Cb.p;
     U = Ub.p;
     kk = knew;
+    c_valid = true;
+    if (last) break;
     ++info->restarts;
+  }
+  if (rr && rc == ISPH_SUCCESS) {
+    rr->kk = kk;
+    rr->have_C = kk > 0 && c_valid;
   }
   if (rc == ISPH_SUCCESS) {  // x = x0 + M^-1 t
     rc = op.prec(t, z);

@@ -1853,9 +1853,27 @@ void isph_solver_params_default(isph_solver_params *p) {
   p->basis_bits = 64;
 }
 
-int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, double *x, int nvec, int lda,
-               int is_singular, const int *null_mask, const isph_solver_params *prm_in, isph_solve_info *info,
-               int on_device) {
+// A recycle space carried from one isph_solve_recycle call to the next (gcrodr.hpp): kk vectors of U in the CALLER's row
+// numbering -- the library's own numbering changes whenever the particles move --, ld = n rounded up to 64 apart.
+struct isph_recycle {
+  isph_ctx *ctx = nullptr;
+  int n = 0, kk = 0;
+  isph::DevBuf<double> U;
+  long long started = 0, discarded = 0, apps = 0, steps = 0;
+  int reason = 0;
+  bool unfused = false;  // ISPH_GCRODR_UNFUSED=1 when the handle was created
+};
+
+namespace {
+struct RecycleRunScope : isph::RecycleRun {
+  ~RecycleRunScope() { U.release(); C.release(); }
+};
+}  // namespace
+
+// isph_solve and isph_solve_recycle: R == NULL is the solve without a handle, launch for launch
+static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, double *x, int nvec, int lda,
+                      int is_singular, const int *null_mask, const isph_solver_params *prm_in, isph_solve_info *info,
+                      int on_device, isph_recycle *R) {
   ISPH_REQUIRE(ctx && A && b && x && info, "NULL argument");
   const int n = A->S.nrow;
   ISPH_REQUIRE(nvec >= 1 && lda >= n, "need nvec >= 1 and lda >= nlocal");
@@ -1871,6 +1889,10 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
     ISPH_REQUIRE(prm.ortho != 2, "basis_bits = 32 takes DGKS or ICGS: IMGS (ortho = 2) keeps the fp64 basis");
   }
   ISPH_CHECK(check_cycle_bits_solver(M, &prm));
+  if (R) {
+    ISPH_REQUIRE(prm.solver_type == 2, "isph_solve_recycle: a recycle handle (isph_recycle) goes with solver_type 2, Recycling GMRES, only");
+    ISPH_REQUIRE(R->ctx == ctx, "isph_solve_recycle: the recycle handle belongs to another context");
+  }
   memset(info, 0, sizeof(*info));
   ISPH_CHECK(ensure_scalars(ctx));
   hipStream_t st = ctx->stream;
@@ -1953,6 +1975,35 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
   LinOp op{ctx, A, M, nv, n};
   int iters = 0, restarts = 0, res_restarts = 0, conv = 1;
   double worst_imp = 0.0, worst_exp = 0.0;
+  RecycleRunScope rr;
+  const long long rld = ((long long)n + 63) / 64 * 64;
+  if (R) {
+    rr.fused = !R->unfused;
+    // whether the carried space can serve this system is one decision of all ranks
+    double bad[2] = {R->kk > 0 && R->n != n ? 1.0 : 0.0, R->kk > prm.num_recycled + 1 ? 1.0 : 0.0};
+    if (comm_active(ctx) && ctx->nranks > 1) ISPH_CHECK(comm_host_allreduce(ctx, bad, 2, /*sum*/ 0));
+    const int reason = bad[0] != 0.0 ? 1 : bad[1] != 0.0 ? 3 : 0;
+    if (reason && R->kk > 0) {
+      R->kk = 0;
+      R->reason = reason;
+      ++R->discarded;
+    }
+    if (prm.num_recycled >= 1 && prm.num_recycled < prm.num_blocks && prm.num_blocks <= 62) {  // gcrodr() refuses the rest
+      const size_t cap = (size_t)rld * (size_t)(prm.num_recycled + 1);
+      ISPH_CHECK(rr.U.reserve(cap > 0 ? cap : 1));
+      ISPH_CHECK(rr.C.reserve(cap > 0 ? cap : 1));
+      if (R->kk > 0 && n > 0) {
+        if (ord) {
+          for (int c = 0; c < R->kk; ++c)
+            hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
+                               (const double *)R->U.p + (size_t)c * rld, rr.U.p + (size_t)c * rld);
+        } else {
+          ISPH_CHECK_HIP(hipMemcpyAsync(rr.U.p, R->U.p, sizeof(double) * (size_t)rld * (size_t)R->kk, hipMemcpyDeviceToDevice, st));
+        }
+      }
+      rr.kk = R->kk;
+    }
+  }
   // several right-hand sides of a non-singular system (the Helmholtz solve: one per velocity component) advance
   // together and share their matrix sweeps; the result is the one of solving them one after the other
   const bool lockstep = gmres_lockstep_ok(op, &prm, nvec);
@@ -1971,7 +2022,7 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
     memset(&ci, 0, sizeof(ci));
     if (lockstep) ci = cls[c];
     else if (prm.solver_type == 1) ISPH_CHECK(pcg(op, bc, xc, &prm, &ci));
-    else if (prm.solver_type == 2) ISPH_CHECK(gcrodr(op, bc, xc, &prm, &ci));
+    else if (prm.solver_type == 2) ISPH_CHECK(gcrodr(op, bc, xc, &prm, &ci, R ? &rr : nullptr));
     else ISPH_CHECK(gmres(op, bc, xc, &prm, &ci));
     {  // ||b - A x|| / ||b|| with the unprojected A (:201-212)
       ISPH_CHECK(ctx->wv.reserve((size_t)n + 64));
@@ -1993,6 +2044,28 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
       // non-convergence is reported, never raised (:192-213)
       if (ci.converged) printf(">> isph::Status - Passed! (%d iterations)\n", ci.iters);
       else printf(">> isph::Status - Failed to converge! ||r|| / ||b|| = %6.4e\n", ci.rel_res_explicit);
+    }
+  }
+  if (R) {  // the space this call leaves, back in the caller's numbering
+    if (rr.reason) {
+      R->reason = rr.reason;
+      ++R->discarded;
+    }
+    if (rr.started) ++R->started;
+    R->apps = rr.apps;
+    R->steps = iters;
+    R->n = n;
+    // the count is what all ranks agree on; a rank without rows keeps the count and holds no values
+    R->kk = rr.kk;
+    if (rr.kk > 0 && n > 0) {
+      ISPH_CHECK(R->U.reserve((size_t)rld * (size_t)rr.kk));
+      if (ord) {
+        for (int c = 0; c < rr.kk; ++c)
+          hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, n, (const int *)ord->perm.p,
+                             (const double *)rr.U.p + (size_t)c * rld, R->U.p + (size_t)c * rld);
+      } else {
+        ISPH_CHECK_HIP(hipMemcpyAsync(R->U.p, rr.U.p, sizeof(double) * (size_t)rld * (size_t)rr.kk, hipMemcpyDeviceToDevice, st));
+      }
     }
   }
   if (ord && n > 0) {  // back into the caller's numbering (b holds its projection when the system is singular)
@@ -2041,6 +2114,180 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, 
   }
   ISPH_CHECK_HIP(hipGetLastError());
   return prec_health(ctx, M);  // the stream is drained (ev1): every application of this solve has reported
+}
+
+int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, double *x, int nvec, int lda,
+               int is_singular, const int *null_mask, const isph_solver_params *prm_in, isph_solve_info *info,
+               int on_device) {
+  return solve_body(ctx, A, M, b, x, nvec, lda, is_singular, null_mask, prm_in, info, on_device, nullptr);
+}
+
+int isph_solve_recycle(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, double *b, double *x, int nvec, int lda,
+                       int is_singular, const int *null_mask, const isph_solver_params *prm_in, isph_solve_info *info,
+                       int on_device, isph_recycle *R) {
+  return solve_body(ctx, A, M, b, x, nvec, lda, is_singular, null_mask, prm_in, info, on_device, R);
+}
+
+int isph_recycle_create(isph_ctx *ctx, isph_recycle **R) {
+  ISPH_REQUIRE(ctx && R, "NULL argument");
+  isph_recycle *r = new isph_recycle();
+  r->ctx = ctx;
+  const char *e = getenv("ISPH_GCRODR_UNFUSED");
+  r->unfused = e && e[0] == '1';
+  *R = r;
+  return ISPH_SUCCESS;
+}
+
+void isph_recycle_destroy(isph_recycle *R) {
+  if (!R) return;
+  R->U.release();
+  delete R;
+}
+
+int isph_recycle_reset(isph_recycle *R) {
+  ISPH_REQUIRE(R, "NULL argument");
+  R->U.release();
+  R->n = 0; R->kk = 0; R->reason = 0;
+  R->apps = 0; R->steps = 0;
+  return ISPH_SUCCESS;
+}
+
+int isph_recycle_info(isph_ctx *ctx, const isph_recycle *R, long long out[8]) {
+  ISPH_REQUIRE(ctx && R && out, "NULL argument");
+  out[0] = R->n; out[1] = R->kk; out[2] = R->started; out[3] = R->discarded; out[4] = R->reason;
+  out[5] = R->apps; out[6] = R->steps; out[7] = (long long)R->U.bytes;
+  return ISPH_SUCCESS;
+}
+
+int isph_recycle_export(isph_ctx *ctx, const isph_recycle *R, double *U) {
+  ISPH_REQUIRE(ctx && R && (U || R->kk == 0 || R->n == 0), "NULL argument");
+  ISPH_REQUIRE(!is_device_pointer(U), "isph_recycle_export writes to host memory");
+  const long long ld = ((long long)R->n + 63) / 64 * 64;
+  for (int c = 0; c < R->kk && R->n > 0; ++c)
+    ISPH_CHECK_HIP(hipMemcpyAsync(U + (size_t)c * (size_t)R->n, R->U.p + (size_t)c * ld, sizeof(double) * (size_t)R->n,
+                                  hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return ISPH_SUCCESS;
+}
+
+// Diagnostic: replace the space by kk vectors of n rows from host memory (column-major [n x kk], caller's numbering), as if
+// a solve on n rows had left them.  Tests hand a rank-deficient space to the orthonormalisation guard this way.
+int isph_recycle_import(isph_ctx *ctx, isph_recycle *R, int n, int kk, const double *U) {
+  ISPH_REQUIRE(ctx && R && n >= 0 && kk >= 0 && kk <= kTallMax - 1 && (U || n == 0 || kk == 0), "isph_recycle_import: bad argument");
+  ISPH_REQUIRE(R->ctx == ctx, "isph_recycle_import: the recycle handle belongs to another context");
+  ISPH_REQUIRE(!is_device_pointer(U), "isph_recycle_import reads host memory");
+  const long long ld = ((long long)n + 63) / 64 * 64;
+  if (kk > 0 && n > 0) {
+    ISPH_CHECK(R->U.reserve((size_t)ld * (size_t)kk));
+    for (int c = 0; c < kk; ++c)
+      ISPH_CHECK_HIP(hipMemcpyAsync(R->U.p + (size_t)c * ld, U + (size_t)c * (size_t)n, sizeof(double) * (size_t)n,
+                                    hipMemcpyHostToDevice, ctx->stream));
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  R->n = n;
+  R->kk = kk;
+  return ISPH_SUCCESS;
+}
+
+/* ---- the dense contractions of tall_skinny.hpp alone (diagnostics) ------- */
+
+// Out[:, c] (+)= sum_i coef[i][c] Basis_i; mode 0 set, 1 accumulate, 2 in place: A <- A coef, coef upper triangular (pb = 0,
+// q = pa, out unused), 3 set by the per-column launches of gcrodr.hpp (k_fill + k_multi_axpy per block and column: what
+// mode 0 replaces; the timing baseline).  Vectors on the device (on_device) or on the host; coef (row-major (pa + pb) x q)
+// on the host.
+int isph_dense_tall_gemm(isph_ctx *ctx, int n, int pa, double *A, long long lda, int pb, const double *B, long long ldb, int q,
+                         const double *coef, double *out, long long ldo, int mode, int on_device) {
+  ISPH_REQUIRE(ctx && coef && n >= 0 && pa >= 0 && pb >= 0 && q >= 1 && mode >= 0 && mode <= 3, "isph_dense_tall_gemm: bad argument");
+  ISPH_REQUIRE((pa == 0 || A) && (pb == 0 || B) && (mode == 2 || out), "isph_dense_tall_gemm: NULL block");
+  ISPH_REQUIRE(mode != 2 || (pb == 0 && q == pa), "isph_dense_tall_gemm: the in-place form takes one block and a square matrix");
+  ISPH_REQUIRE(lda >= n && ldb >= n && (mode == 2 || ldo >= n), "isph_dense_tall_gemm: a leading dimension is shorter than the vectors");
+  DevTmp<double> da, db, dout, cbuf;
+  double *pA = A, *pO = out;
+  const double *pB = B;
+  const size_t na = (size_t)lda * (size_t)(pa > 0 ? pa - 1 : 0) + (size_t)n, nb = (size_t)ldb * (size_t)(pb > 0 ? pb - 1 : 0) + (size_t)n;
+  const size_t no = (size_t)ldo * (size_t)(q - 1) + (size_t)n;
+  if (!on_device) {
+    ISPH_REQUIRE(!is_device_pointer(A) && !is_device_pointer(B) && !is_device_pointer(out), "device pointer passed with on_device = 0");
+    if (pa > 0) {
+      ISPH_CHECK(da.reserve(na + 1));
+      ISPH_CHECK_HIP(hipMemcpyAsync(da.p, A, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
+      pA = da.p;
+    }
+    if (pb > 0) {
+      ISPH_CHECK(db.reserve(nb + 1));
+      ISPH_CHECK_HIP(hipMemcpyAsync(db.p, B, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+      pB = db.p;
+    }
+    if (mode != 2) {
+      ISPH_CHECK(dout.reserve(no + 1));
+      ISPH_CHECK_HIP(hipMemcpyAsync(dout.p, out, sizeof(double) * no, hipMemcpyHostToDevice, ctx->stream));
+      pO = dout.p;
+    }
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (mode == 2) ISPH_CHECK(tall_gemm_inplace(ctx, n, pa, pA, lda, coef, cbuf));
+  else if (mode == 3) {
+    ISPH_REQUIRE(pa + pb <= kTallMax && q <= kTallMax, "isph_dense_tall_gemm: at most 64 vectors and 64 outputs");
+    std::vector<double> col((size_t)(pa + pb > 0 ? pa + pb : 1));
+    for (int c = 0; c < q; ++c) {
+      for (int i = 0; i < pa + pb; ++i) col[(size_t)i] = coef[(size_t)i * q + c];
+      ISPH_CHECK(combine(ctx, n, pa, pA, lda, col.data(), pO + (size_t)c * ldo, false, cbuf));
+      ISPH_CHECK(combine(ctx, n, pb, pB, ldb, col.data() + pa, pO + (size_t)c * ldo, true, cbuf));
+    }
+  } else ISPH_CHECK(tall_gemm(ctx, n, pa, pA, lda, pb, pB, ldb, q, coef, pO, ldo, mode == 1, cbuf));
+  if (!on_device) {
+    if (mode == 2) ISPH_CHECK_HIP(hipMemcpyAsync(A, pA, sizeof(double) * na, hipMemcpyDeviceToHost, ctx->stream));
+    else ISPH_CHECK_HIP(hipMemcpyAsync(out, pO, sizeof(double) * no, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+// G (host, row-major (pa + pb) x q) = [XA | XB]^T Y, this rank's rows only.  per_column: by the launches of gcrodr.hpp
+// that k_block_gram replaces (one k_multi_dot per block and column of Y; at most 63 vectors per block): the timing baseline
+int isph_dense_block_gram(isph_ctx *ctx, int n, int pa, const double *XA, long long lda, int pb, const double *XB, long long ldb,
+                          int q, const double *Y, long long ldy, double *G, int per_column, int on_device) {
+  ISPH_REQUIRE(ctx && Y && G && n >= 0 && pa >= 0 && pb >= 0 && pa + pb >= 1 && q >= 1, "isph_dense_block_gram: bad argument");
+  ISPH_REQUIRE((pa == 0 || XA) && (pb == 0 || XB), "isph_dense_block_gram: NULL block");
+  ISPH_REQUIRE(lda >= n && ldb >= n && ldy >= n, "isph_dense_block_gram: a leading dimension is shorter than the vectors");
+  DevTmp<double> da, db, dy, scratch;
+  const double *pA = XA, *pB = XB, *pY = Y;
+  if (!on_device) {
+    ISPH_REQUIRE(!is_device_pointer(XA) && !is_device_pointer(XB) && !is_device_pointer(Y), "device pointer passed with on_device = 0");
+    const size_t na = (size_t)lda * (size_t)(pa > 0 ? pa - 1 : 0) + (size_t)n, nb = (size_t)ldb * (size_t)(pb > 0 ? pb - 1 : 0) + (size_t)n;
+    const size_t ny = (size_t)ldy * (size_t)(q - 1) + (size_t)n;
+    if (pa > 0) {
+      ISPH_CHECK(da.reserve(na + 1));
+      ISPH_CHECK_HIP(hipMemcpyAsync(da.p, XA, sizeof(double) * na, hipMemcpyHostToDevice, ctx->stream));
+      pA = da.p;
+    }
+    if (pb > 0) {
+      ISPH_CHECK(db.reserve(nb + 1));
+      ISPH_CHECK_HIP(hipMemcpyAsync(db.p, XB, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+      pB = db.p;
+    }
+    ISPH_CHECK(dy.reserve(ny + 1));
+    ISPH_CHECK_HIP(hipMemcpyAsync(dy.p, Y, sizeof(double) * ny, hipMemcpyHostToDevice, ctx->stream));
+    pY = dy.p;
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (per_column) {
+    ISPH_REQUIRE(pa <= 63 && pb <= 63 && q <= kTallMax, "isph_dense_block_gram: the per-column launches take at most 63 vectors per block");
+    ISPH_REQUIRE(ctx->nranks == 1, "isph_dense_block_gram: the per-column launches are all-reduced; one rank only");
+    ISPH_CHECK(ensure_scalars(ctx));
+    std::vector<double> col(64);
+    for (int c = 0; c < q; ++c) {
+      if (pa > 0) ISPH_CHECK(multi_dot_host(ctx, n, pa, pA, lda, pY + (size_t)c * ldy, col.data()));
+      for (int a2 = 0; a2 < pa; ++a2) G[(size_t)a2 * q + c] = col[(size_t)a2];
+      if (pb > 0) ISPH_CHECK(multi_dot_host(ctx, n, pb, pB, ldb, pY + (size_t)c * ldy, col.data()));
+      for (int a2 = 0; a2 < pb; ++a2) G[(size_t)(pa + a2) * q + c] = col[(size_t)a2];
+    }
+  } else {
+    ISPH_CHECK(block_gram(ctx, n, pa, pA, lda, pb, pB, ldb, q, pY, ldy, G, scratch, /*reduce=*/false));
+  }
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
 }
 
 // SolverLin_Belos::solveBlockProblem (ref: solver_lin_belos.h:53-128): GMRES / CG over the product vector

@@ -35,6 +35,8 @@ EXPORTS = [
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
     "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
+    "isph_recycle_create", "isph_recycle_destroy", "isph_recycle_reset", "isph_recycle_info", "isph_recycle_export", "isph_recycle_import",
+    "isph_solve_recycle", "isph_dense_tall_gemm", "isph_dense_block_gram",
 ]
 
 
@@ -300,6 +302,19 @@ def lib():
         L.isph_mat_update_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_mat_pattern_info.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_prec_refactor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.isph_recycle_create.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_recycle_destroy.argtypes = [C.c_void_p]
+        L.isph_recycle_destroy.restype = None
+        L.isph_recycle_reset.argtypes = [C.c_void_p]
+        L.isph_recycle_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.isph_recycle_export.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.isph_recycle_import.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.isph_solve_recycle.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_dense_tall_gemm.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                           C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int]
+        L.isph_dense_block_gram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
+                                            C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int]
         _lib = L
     return _lib
 
@@ -1025,15 +1040,104 @@ class PrecondAMG(Precond):
         return dict(zip(self.PATH_KEYS, (int(x) for x in a)))
 
 
-def solve(ctx, A, b, x, prec=None, singular=False, null_mask=None, params=None, nvec=1, lda=None):
+class RecycleSpace:
+    """isph_recycle: the recycle space of "Recycling GMRES" (solver_type 2) carried from one solve to the next --
+    solve(..., recycle=space).  One object per sequence of systems; not a reference feature (include/isph_hip.h)."""
+    REASONS = {0: "none", 1: "number of rows changed", 2: "orthonormalisation guard", 3: "more vectors than k + 1"}
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        _check(lib().isph_recycle_create(ctx.h, C.byref(self.h)))
+
+    def info(self):
+        out = (C.c_longlong * 8)()
+        _check(lib().isph_recycle_info(self.ctx.h, self.h, out))
+        keys = ("n", "vectors", "started", "discarded", "last_reason", "applications", "steps", "bytes")
+        return dict(zip(keys, (int(v) for v in out)))
+
+    def export(self):
+        """U [n x kk] in the caller's row numbering (numpy, Fortran order)"""
+        i = self.info()
+        U = np.zeros((i["n"], i["vectors"]), dtype=np.float64, order="F")
+        if U.size:
+            _check(lib().isph_recycle_export(self.ctx.h, self.h, _ptr(U)))
+        return U
+
+    def import_(self, U):
+        """isph_recycle_import (diagnostic): U [n x kk] in the caller's row numbering replaces the space"""
+        U = np.asfortranarray(U, dtype=np.float64)
+        _check(lib().isph_recycle_import(self.ctx.h, self.h, int(U.shape[0]), int(U.shape[1]), _ptr(U)))
+
+    def reset(self):
+        _check(lib().isph_recycle_reset(self.h))
+
+    def close(self):
+        if self.h:
+            lib().isph_recycle_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def dense_tall_gemm(ctx, n, A, lda, B, ldb, coef, out, ldo, mode=0):
+    """isph_dense_tall_gemm (diagnostic): A [pa vectors], B [pb vectors or None], coef [(pa + pb) x q]; mode 0 set,
+    1 accumulate into out, 2 in place (A <- A coef, coef upper triangular), 3 set by one launch per block and column"""
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    p, q = coef.shape
+    pa = 0 if A is None else _count_vectors(A, n, lda)
+    pb = 0 if B is None else _count_vectors(B, n, ldb)
+    if pa + pb != p:
+        raise OperandError("coef has %d rows for %d vectors" % (p, pa + pb))
+    if mode != 2:
+        _need(out, ldo * (q - 1) + n, "out [ldo x q]")
+    _check(lib().isph_dense_tall_gemm(ctx.h, n, pa, _ptr(A), lda, pb, _ptr(B), ldb, q, _ptr(coef), _ptr(out), ldo, mode,
+                                      _on_device(A, B, out)))
+    return A if mode == 2 else out
+
+
+def dense_block_gram(ctx, n, XA, lda, XB, ldb, Y, ldy, per_column=False):
+    """isph_dense_block_gram (diagnostic): G [(pa + pb) x q] = [XA | XB]^T Y over n rows; per_column: by one multi-dot
+    launch per block and column of Y"""
+    pa = 0 if XA is None else _count_vectors(XA, n, lda)
+    pb = 0 if XB is None else _count_vectors(XB, n, ldb)
+    q = _count_vectors(Y, n, ldy)
+    G = np.zeros((pa + pb, q), dtype=np.float64)
+    _check(lib().isph_dense_block_gram(ctx.h, n, pa, _ptr(XA), lda, pb, _ptr(XB), ldb, q, _ptr(Y), ldy, _ptr(G),
+                                       int(per_column), _on_device(XA, XB, Y)))
+    return G
+
+
+def _count_vectors(a, n, ld):
+    """vectors of a vector-major block given as a flat array of ld (nv - 1) + n elements (or [nv, ld])"""
+    have = int(a.numel()) if _is_torch(a) else int(np.asarray(a).size)
+    if ld < max(n, 1):
+        raise OperandError("leading dimension %d shorter than the vectors (%d)" % (ld, n))
+    nv = (have - n) // ld + 1 if have >= n else 0
+    if nv < 1:
+        raise OperandError("block shorter than one vector")
+    return nv
+
+
+def solve(ctx, A, b, x, prec=None, singular=False, null_mask=None, params=None, nvec=1, lda=None, recycle=None):
     """isph_solve == SolverLin_Belos::solveProblem.  b and x are updated in
-    place (b by its projection when singular); returns SolveInfo."""
+    place (b by its projection when singular); returns SolveInfo.  recycle: a RecycleSpace (solver_type 2 only) that
+    carries the recycle space to the next solve -- isph_solve_recycle."""
     prm = params or SolverParams()
     info = SolveInfo()
     n = A.info()["nrow"]
     mask = None if null_mask is None else np.ascontiguousarray(null_mask, dtype=np.int32)
     ld = n if lda is None else lda
     _need(b, ld * (nvec - 1) + n, "b [lda x nvec]"); _need(x, ld * (nvec - 1) + n, "x [lda x nvec]"); _need(mask, n, "null_mask [n]")
+    if recycle is not None:
+        _check(lib().isph_solve_recycle(ctx.h, A.h, prec.h if prec is not None else None, _ptr(b), _ptr(x), nvec,
+                                        n if lda is None else lda, int(singular), _ptr(mask), C.byref(prm), C.byref(info),
+                                        _on_device(b, x), recycle.h))
+        return info
     _check(lib().isph_solve(ctx.h, A.h, prec.h if prec is not None else None, _ptr(b), _ptr(x), nvec,
                             n if lda is None else lda, int(singular), _ptr(mask), C.byref(prm), C.byref(info),
                             _on_device(b, x)))

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -26,6 +27,7 @@ class SolverLin_HIP : public SolverLin {
   SolverLin_HIP(MPI_Comm &comm, int device = 0) : SolverLin(comm), _ctx(nullptr), _device(device) {}
   virtual ~SolverLin_HIP() {
     holdPattern(false);
+    releaseRecycle();
     if (_ctx) isph_ctx_destroy(_ctx);
   }
 
@@ -50,7 +52,16 @@ class SolverLin_HIP : public SolverLin {
   }
 
   // same keys/defaults as SolverLin_Belos::setParameters, ref: solver_lin_belos.h:224-264
+  // The carried recycle spaces ("isph: recycle across solves") are freed here, whichever list is given: a caller that
+  // sets parameters starts its sequences anew.
   void setParameters(Teuchos::ParameterList *param = NULL) {
+    releaseRecycle();
+    adoptParameters(param);
+  }
+
+  // what solveProblem / solveBlockProblem call to make sure a list exists (the reference calls setParameters there,
+  // solver_lin_belos.h:134; here that must not end the sequences)
+  void adoptParameters(Teuchos::ParameterList *param) {
     if (param == NULL) {
       _param = Teuchos::rcp(new Teuchos::ParameterList);
       _param->set("Flexible Gmres", true);
@@ -67,6 +78,10 @@ class SolverLin_HIP : public SolverLin {
       _param->set("Verbosity", 33);
       // device-side extension (not a reference key), "Solver Type" = "Block GMRES" only: "isph: krylov basis bits" = 32
       // stores the Krylov basis rounded to float (isph_solver_params::basis_bits).  Not set here: absent means 64.
+      // "isph: recycle across solves" = 1, "Solver Type" = "Recycling GMRES" only (read with no other type): the recycle
+      // space a solve ends with starts the next solveProblem call of the same `name` (isph_solve_recycle; one space per
+      // name, so the "Helmholtz" and "Poisson" systems that alternate through one solver object do not share one).
+      // Not set here: absent means 0.
     } else if (_param.get() != param) {
       _param = Teuchos::rcp(param, false);
     }
@@ -103,7 +118,7 @@ class SolverLin_HIP : public SolverLin {
 
   int solveProblem(PrecondWrapper *prec = NULL, const char *name = NULL) {
     if (_comm.MyPID() == 0 && name != NULL) std::cout << ">> Belos::Label - " << name << std::endl;
-    setParameters(_param.get());
+    adoptParameters(_param.get());
     if (!basisBitsAvailable()) return LAMMPS_FAILURE;
     if (ensureContext() != ISPH_SUCCESS) return LAMMPS_FAILURE;
     if (!_A || !_x || !_b) return LAMMPS_FAILURE;
@@ -179,9 +194,15 @@ class SolverLin_HIP : public SolverLin {
     isph_solver_params p = solverParams();
 
     isph_solve_info info;
+    isph_recycle *R = nullptr;  // NULL: isph_solve_recycle is isph_solve
+    if (rc == ISPH_SUCCESS && p.solver_type == 2 && _param->get("isph: recycle across solves", 0) != 0) {
+      isph_recycle *&slot = _recycle[name == NULL ? std::string() : std::string(name)];
+      if (slot == nullptr) rc = isph_recycle_create(_ctx, &slot);
+      R = slot;
+    }
     if (rc == ISPH_SUCCESS)
-      rc = isph_solve(_ctx, A, prec ? prec->_M : nullptr, _b->Values(), _x->Values(), _x->NumVectors(), _x->Stride(),
-                      _is_singular ? 1 : 0, _null_mask ? _null_mask->Values() : nullptr, &p, &info, 0);
+      rc = isph_solve_recycle(_ctx, A, prec ? prec->_M : nullptr, _b->Values(), _x->Values(), _x->NumVectors(), _x->Stride(),
+                              _is_singular ? 1 : 0, _null_mask ? _null_mask->Values() : nullptr, &p, &info, 0, R);
     const std::chrono::steady_clock::time_point t3 = std::chrono::steady_clock::now();
     if (prec != NULL) {
       if (_is_singular && prec->usesNullVector()) prec->setNullVector(NULL);
@@ -217,7 +238,7 @@ class SolverLin_HIP : public SolverLin {
       std::fprintf(stderr, ">> SolverLin_Belos::solveBlockProblem does not support singular problems\n");
       return LAMMPS_FAILURE;
     }
-    setParameters(_param.get());
+    adoptParameters(_param.get());
     if (!basisBitsAvailable()) return LAMMPS_FAILURE;
     if (ensureContext() != ISPH_SUCCESS) return LAMMPS_FAILURE;
     isph_mat *blk[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -274,6 +295,13 @@ class SolverLin_HIP : public SolverLin {
   }
 
   const isph_solve_info &lastSolveInfo() const { return _last; }
+  // isph_recycle_info of the space kept for solveProblem calls named `name`; ISPH_FAILURE when there is none (not a
+  // reference method)
+  int recycleInfo(const char *name, long long out[8]) const {
+    std::map<std::string, isph_recycle *>::const_iterator it = _recycle.find(name == NULL ? std::string() : std::string(name));
+    if (it == _recycle.end() || it->second == nullptr || !_ctx) return ISPH_FAILURE;
+    return isph_recycle_info(_ctx, it->second, out);
+  }
   // wall time of the last solveProblem in milliseconds: [0] matrix ingress (host CSR -> device; the value update of a
   // kept matrix while holdPattern is on), [1] preconditioner
   // set-up, [2] Krylov solve incl. the transfers of b and x, [3] release.  [1] and [2] are only separated when
@@ -393,6 +421,12 @@ class SolverLin_HIP : public SolverLin {
     _held = HeldKey();
     _held_rp.clear();
   }
+  void releaseRecycle() {
+    for (std::map<std::string, isph_recycle *>::iterator it = _recycle.begin(); it != _recycle.end(); ++it)
+      isph_recycle_destroy(it->second);
+    _recycle.clear();
+  }
+  std::map<std::string, isph_recycle *> _recycle;  // "isph: recycle across solves": one space per solveProblem name
   std::shared_ptr<PatternHold> _hold = std::make_shared<PatternHold>();
   isph_mat *_heldA = nullptr;
   HeldKey _held;

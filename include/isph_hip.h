@@ -507,6 +507,62 @@ int isph_solve(isph_ctx *ctx, const isph_mat *A, const isph_prec *M,
                double *b /*[h|d]*/, double *x /*[h|d]*/, int nvec, int lda,
                int is_singular, const int *null_mask /*[h] or NULL*/,
                const isph_solver_params *prm, isph_solve_info *info, int on_device);
+
+/* ---- Recycling GMRES: a recycle space carried from one solve to the next --------------------------------------------
+ * Not a reference feature: the reference builds a new Belos::GCRODRSolMgr for every solve, so its recycling stops at
+ * the end of a solve.  A handle keeps the space U a solve ends with (k or k + 1 vectors of the preconditioned variable,
+ * in the CALLER's row numbering, on the device) and the next isph_solve_recycle call with that handle starts from it:
+ * for a sequence of slowly changing systems (one Poisson system per time step) or for the right-hand sides of one
+ * system.  The next solve spends kk operator applications on C = A M^-1 U, orthonormalises by Cholesky-QR done twice,
+ * projects the initial residual and continues with cycles of m - kk steps; the convergence test stays relative to the
+ * residual before the projection.  The space is dropped, the solve then being the one without a handle, when the number
+ * of rows changed (reason 1), when the orthonormalisation guard trips (2: a Cholesky pivot that is not positive and
+ * finite, or kk max|C^T C - I| > 1/2 before the second pass), or when it holds more vectors than the new k + 1 (3).
+ * After every solve with a handle the recycle step runs once more and its space is kept, converged or not; a solve
+ * whose only cycle took no more than k steps keeps nothing.  With nvec > 1 the columns after the first start from U and
+ * C as the column before left them (same operator: no applications, no orthonormalisation).  One handle per sequence:
+ * alternating systems (Poisson / Helmholtz) take a handle each.  On several ranks every rank passes its own handle and
+ * all ranks keep or drop their spaces together.  Off unless asked for: what it gains depends on the preconditioner
+ * (README, "Recycling across solves").
+ *
+ * isph_solve_recycle with R == NULL is isph_solve.  With a handle it takes solver_type 2 only; basis_bits = 32 and a
+ * cycle_bits = 32 preconditioner are refused as in isph_solve.  isph_solve_block and isph_solve_poisson_boltzmann take
+ * no handle.  The handle's dense contractions run as two kernels that sweep a block of vectors once (k_tall_gemm,
+ * k_block_gram); ISPH_GCRODR_UNFUSED=1 in the environment when the handle is created keeps one launch per column
+ * there (the cross-check and the timing baseline).
+ *
+ * isph_recycle_info: out[0] rows the space belongs to, [1] vectors held, [2] solves that started from a carried space,
+ * [3] solves that dropped one, [4] reason of the last drop (0 none), [5] operator applications spent on rebuilding C in
+ * the last call, [6] Arnoldi steps of the last call, [7] bytes held.  isph_recycle_reset forgets the space and the last
+ * call's figures and keeps the object and its two counters.  isph_recycle_export: U, column-major [n x kk], caller's
+ * numbering, to host memory. */
+typedef struct isph_recycle isph_recycle;
+int isph_recycle_create(isph_ctx *ctx, isph_recycle **R);
+void isph_recycle_destroy(isph_recycle *R);
+int isph_recycle_reset(isph_recycle *R);
+int isph_recycle_info(isph_ctx *ctx, const isph_recycle *R, long long out[8]);
+int isph_recycle_export(isph_ctx *ctx, const isph_recycle *R, double *U /*[h] n x kk*/);
+/* Diagnostic: the reverse of isph_recycle_export -- the handle then holds these kk vectors of n rows as if a solve had left
+ * them (tests hand a rank-deficient space to the guard this way).  On several ranks every rank imports the same kk. */
+int isph_recycle_import(isph_ctx *ctx, isph_recycle *R, int n, int kk, const double *U /*[h] n x kk*/);
+int isph_solve_recycle(isph_ctx *ctx, const isph_mat *A, const isph_prec *M,
+                       double *b /*[h|d]*/, double *x /*[h|d]*/, int nvec, int lda,
+                       int is_singular, const int *null_mask /*[h] or NULL*/,
+                       const isph_solver_params *prm, isph_solve_info *info, int on_device, isph_recycle *R);
+/* Diagnostics: the two kernels alone.  Blocks are vector-major (vector v at base + v * ld), at most 64 vectors in
+ * [A | B] and at most 64 outputs; coef and G are row-major in host memory; the vectors are device memory when on_device.
+ * isph_dense_tall_gemm: out[:, c] = sum_i coef[i][c] Basis_i (mode 0), out[:, c] += ... (mode 1), or A <- A coef in
+ * place with coef upper triangular, pb = 0, q = pa (mode 2; out is not used).  Per output one fma chain over ascending
+ * i, from 0.0 or from the stored value.  Mode 3 is mode 0 by one launch per block and column, the launches a solve
+ * without a handle makes: the same bits, the timing baseline.  isph_dense_block_gram: G[a][c] = sum over this rank's
+ * rows of X_a Y_c, X = [XA | XB]; the same bits on every call.  per_column: by one multi-dot launch per block and column
+ * of Y (at most 63 vectors per block, one rank): the timing baseline; its sums run in another order. */
+int isph_dense_tall_gemm(isph_ctx *ctx, int n, int pa, double *A /*[h|d]*/, long long lda, int pb, const double *B /*[h|d]*/,
+                         long long ldb, int q, const double *coef /*[h]*/, double *out /*[h|d]*/, long long ldo, int mode,
+                         int on_device);
+int isph_dense_block_gram(isph_ctx *ctx, int n, int pa, const double *XA /*[h|d]*/, long long lda, int pb,
+                          const double *XB /*[h|d]*/, long long ldb, int q, const double *Y /*[h|d]*/, long long ldy,
+                          double *G /*[h]*/, int per_column, int on_device);
 /* profile mode: HIP events on the library's stream around the launches of the hot kernels, by class:
  *   [0] SpMV (k_sell_spmv16 incl. the halo exchange when there is one)   [1] preconditioner application (block ILU:
  *   k_ilu_solve_stream)   [2] k_multi_dot   [3] k_multi_axpy_dot   [4] k_multi_axpy_norm (the three sweeps of one
