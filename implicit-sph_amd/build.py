@@ -204,6 +204,22 @@ def build_cpp_recycle_test(force=False):
     return CPP_RECYCLE_TEST
 
 
+CPP_AMG_ILU_TEST = os.path.join(ROOT, "tests", "cpp", "test_amg_ilu_wrappers")
+
+
+def build_cpp_amg_ilu_test(force=False):
+    """C++ driver of PrecondWrapper_ML's "smoother: type" = "IFPACK" (host/*.h), linked like build_cpp_test; used by
+    tests/test_gpu_amg_ilu_wrappers.py."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_amg_ilu_wrappers.cpp")
+    host = os.path.join(PKG, "host")
+    deps = [src] + [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(INC, "isph_hip.h")]
+    if force or _stale(CPP_AMG_ILU_TEST, deps):
+        build_hip()
+        _run(["g++", "-O2", "-std=c++17", "-I", INC, "-I", host, "-o", CPP_AMG_ILU_TEST, src,
+              "-L", PKG, "-lisph_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return CPP_AMG_ILU_TEST
+
+
 RANK_THREADS = os.path.join(ROOT, "tests", "cpp", "librank_threads.so")
 
 
@@ -259,4 +275,5 @@ def build_cpp_mpi(force=False):
 def build_all(force=False):
     return (build_host(force), build_hip(force), build_cpp_test(force), build_cpp_mpi(force), build_rank_threads(force),
             build_cpp_chebyshev_test(force), build_cpp_chebyshev_f32_test(force), build_cpp_ilu_f32_test(force), build_cpp_basis_f32_test(force),
-            build_cpp_pattern_hold_test(force), build_cpp_eig_estimate_test(force), build_cpp_amg_cycle_f32_test(force))
+            build_cpp_pattern_hold_test(force), build_cpp_eig_estimate_test(force), build_cpp_amg_cycle_f32_test(force),
+            build_cpp_amg_ilu_test(force))

@@ -16,6 +16,9 @@
 // isph_amg_params::smoother = 2 replaces the Gauss-Seidel sweeps by ML's "Chebyshev" ("MLS") smoother: a polynomial of
 // degree `sweeps` in D^-1 A with the same rho per level (chebyshev.hpp) -- no factor, no dense block inverses, not local
 // to blocks, a symmetric operator; the hierarchy is built by the same code whatever the smoother.
+// isph_amg_params::smoother = 4 is ML's "IFPACK" smoother with "ILU": the cycle of smoother 0 with the block ILU(ilu_fill) of
+// every level in the place of the Gauss-Seidel factor (ilu_create with sgs = false; k_ilu_dense_build on small coarse
+// levels); Gauss-Seidel stays on a coarsest level the smoother has to solve and on a level with a row without a diagonal.
 // isph_amg_params::cycle_bits = 32 (smoother 2 only): the whole V cycle in single-precision STORAGE -- float planes of A_l, P_l,
 // P_l^T and A_l P_l, float level vectors, fp64 arithmetic with one rounding per stored element (amg_vcycle_t<float>,
 // include/isph_hip.h states the arithmetic); the hierarchy stays the fp64 one.  Not a linear operator: flexible GMRES only.
@@ -59,8 +62,8 @@ struct AmgLevel {
   isph_mat *Pm = nullptr;
   isph_mat *APm = nullptr;   // A P of the set-up, kept when the level has no halo: residual update after the coarse correction
   DCsr R;                    // restriction P^T in CSR: its rows are hundreds of entries long, one wave per row
-  isph_ilu *sgs = nullptr;   // block-local symmetric Gauss-Seidel in stream form
-  DevBuf<double> wsgs;       // small coarse levels: the same smoother as dense 64 x 64 inverses (k_sgs_dense_build)
+  isph_ilu *sgs = nullptr;   // block-local symmetric Gauss-Seidel in stream form (smoother 4: the block ILU(k) of the level)
+  DevBuf<double> wsgs;       // small coarse levels: the same smoother as dense 64 x 64 inverses (k_sgs_dense_build; smoother 4: k_ilu_dense_build)
   DevBuf<double> wfwd, wbwd; // ... of the forward / backward sweep alone (isph_amg::gs_eff)
   Cheb *cheb = nullptr;      // isph_amg_params::smoother == 2: the Chebyshev polynomial of this level (chebyshev.hpp)
   DevBuf<int> agg;
@@ -90,6 +93,7 @@ struct isph_amg {
   int cheb_value_bits = 64;   // smoother == 2: 32 = every level's polynomial sweeps a float plane of its operator (chebyshev.hpp)
   int cycle_bits = 64;        // smoother == 2: 32 = the whole V cycle in float storage (amg_vcycle_t<float>); sets cheb_value_bits 32
   int cheb = 0;           // isph_amg_params::smoother == 2: Chebyshev polynomial of degree `sweeps` in D^-1 A, before and after
+  int ilu = 0, ilu_fill = 0;  // isph_amg_params::smoother == 4: block ILU(ilu_fill) Richardson sweeps in the cycle of smoother 0
   int eig_type = 0, eig_iters = 10;   // isph_amg_params: 1 = damping and Chebyshev intervals from the Arnoldi estimate of every level
   int coarse_smooth = 0;  // coarsest level solved by the smoother: singular system (precond_ml.h:97-127) or a level too
                           // large for the dense inverse (no coarsening possible: isolated / Dirichlet rows dominate)
@@ -1177,6 +1181,85 @@ __global__ __launch_bounds__(256) void k_sgs_dense_apply(int n, const double *__
   if (row < n) z[row] = ACC ? z[row] + acc : acc;
 }
 
+// ---- isph_amg_params::smoother == 4 on small coarse levels: block ILU(k) as the same dense block inverses -------------
+// (L_B U_B)^-1 of one 64-row block, stored in the layout k_sgs_dense_apply reads.  One wave per block, three stages:
+//   1. the in-block entries into Bm (lane = row), their levels into lev: 0 on a stored entry, kIluDenseAbsent elsewhere;
+//   2. the symbolic level-of-fill pass, rows in order, lane = column, the row's levels in a register: for every k < i of
+//      the row's pattern so far, lev_ij = min(lev_ij, lev_ik + lev_kj + 1) where that is <= fill (Ifpack's rule, the one
+//      k_iluk_merge sweeps to); then the numeric IKJ pass on the final pattern, the row's values in a register: L below
+//      the diagonal (unit diagonal implied), U on and above it, in place in Bm;
+//   3. lane t solves (L_B U_B) y = e_t: forward with the unit lower triangle, backward with division by the U pivots.
+// Conventions of k_sgs_pivots: a zero pivot keeps its unknown at zero (and gives a zero multiplier).  A row of the block
+// without a stored diagonal entry raises err bit kIluDenseNoDiag: the level falls back to Gauss-Seidel (amg_create).
+// LDS: two 64 x 65 double tiles + 4 KB of levels = 70 656 B, dynamic (set-up code, one wave per block: occupancy is not
+// the concern).
+constexpr int kIluDenseAbsent = 255;
+constexpr int kIluDenseNoDiag = 16;
+constexpr size_t kIluDenseLds = 2 * 64 * 65 * sizeof(double) + 64 * 64;
+__global__ __launch_bounds__(64) void k_ilu_dense_build(int n, const rp_t *__restrict__ rp, const int *__restrict__ ci,
+                                                        const double *__restrict__ v, double *__restrict__ W, int fill,
+                                                        int *__restrict__ err) {
+  extern __shared__ __attribute__((aligned(16))) char ilu_dense_lds[];
+  double (*Bm)[65] = reinterpret_cast<double (*)[65]>(ilu_dense_lds);
+  double (*Y)[65] = reinterpret_cast<double (*)[65]>(ilu_dense_lds + 64 * 65 * sizeof(double));
+  unsigned char (*lev)[64] = reinterpret_cast<unsigned char (*)[64]>(ilu_dense_lds + 2 * 64 * 65 * sizeof(double));
+  const int t = threadIdx.x, r0 = blockIdx.x * 64;
+  const int m = min(64, n - r0);
+  // stage 1
+  for (int j = 0; j < 64; ++j) { Bm[t][j] = 0.0; lev[t][j] = (unsigned char)kIluDenseAbsent; }
+  if (t < m) {
+    for (rp_t p = rp[r0 + t]; p < rp[r0 + t + 1]; ++p) {
+      const int j = ci[p] - r0;
+      if (j >= 0 && j < m) { Bm[t][j] = v[p]; lev[t][j] = 0; }
+    }
+    if (lev[t][t] != 0) atomicOr(err, kIluDenseNoDiag);
+  }
+  __syncthreads();
+  // stage 2, symbolic: row i's levels in li (lane = column); rows k < i are final when row i reads them
+  for (int i = 1; i < m && fill > 0; ++i) {
+    int li = lev[i][t];
+    for (int k = 0; k < i; ++k) {
+      const int lik = __shfl(li, k, 64);   // (as updated by the earlier k of this row)
+      if (lik > fill) continue;            // wave-uniform
+      const int nl = lik + (int)lev[k][t] + 1;
+      if (t > k && nl <= fill && nl < li) li = nl;
+    }
+    lev[i][t] = (unsigned char)li;
+    __syncthreads();
+  }
+  // stage 2, numeric: IKJ on the final pattern, row i's values in ai
+  for (int i = 1; i < m; ++i) {
+    double ai = Bm[i][t];
+    const bool in = (int)lev[i][t] <= fill;
+    for (int k = 0; k < i; ++k) {
+      if ((int)lev[i][k] > fill) continue;   // wave-uniform
+      const double piv = Bm[k][k];
+      const double aik = __shfl(ai, k, 64);
+      const double lik = piv != 0.0 ? aik / piv : 0.0;
+      if (t == k) ai = lik;
+      else if (t > k && in) ai -= lik * Bm[k][t];   // (Bm[k][t] is 0 outside row k's pattern)
+    }
+    Bm[i][t] = ai;
+    __syncthreads();
+  }
+  // stage 3: column t of (L_B U_B)^-1
+  for (int i = 0; i < m; ++i) {
+    double s = i == t ? 1.0 : 0.0;
+    for (int j = 0; j < i; ++j) s -= Bm[i][j] * Y[j][t];
+    Y[i][t] = s;
+  }
+  for (int i = m - 1; i >= 0; --i) {
+    double s = Y[i][t];
+    for (int j = i + 1; j < m; ++j) s -= Bm[i][j] * Y[j][t];
+    const double d = Bm[i][i];
+    Y[i][t] = d != 0.0 ? s / d : 0.0;
+  }
+  __syncthreads();
+  // column-major, as k_sgs_dense_build stores it: W[c * 64 + t] = (M^-1)[t][c]
+  double *Wb = W + (size_t)blockIdx.x * 4096;
+  for (int c = 0; c < 64; ++c) Wb[c * 64 + t] = (t < m && c < m) ? Y[t][c] : 0.0;
+}
+
 // ---- host side ------------------------------------------------------------------------------------------
 inline int amg_scan(isph_ctx *ctx, const int *in, rp_t *out, int n, DevBuf<char> &tmp) {
   size_t bytes = 0;
@@ -1919,14 +2002,49 @@ inline int amg_float_planes(isph_ctx *ctx, isph_amg *G) {
   return ISPH_SUCCESS;
 }
 
+// isph_amg_params::smoother == 4: the block ILU(G->ilu_fill) of level l -- dense 64-row block inverses (k_ilu_dense_build,
+// path 4) or the chunk stream (ilu_create, path 5).  *built stays false, with success returned, when a row of the level
+// stores no diagonal entry: the caller builds the Gauss-Seidel smoother instead.  derr: the set-up's error word, 0 on entry.
+inline int amg_ilu_smoother(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int l, bool dense, int *derr, bool *built) {
+  *built = false;
+  if (!dense) {
+    bool no_diag = false;
+    const int rc = ilu_create(ctx, L->Am, l == 0 ? G->block : kAmgCoarseBlock, &L->sgs, /*sgs=*/false, G->ilu_fill, 0, nullptr, 64, &no_diag);
+    if (rc != ISPH_SUCCESS) return no_diag ? ISPH_SUCCESS : rc;
+    L->path[AMG_PATH_SMOOTHER] = 5;
+    *built = true;
+    return ISPH_SUCCESS;
+  }
+  const int nb = (L->A.n + 63) / 64;
+  int herr = 0;
+  ISPH_CHECK(L->wsgs.reserve((size_t)nb * 4096));
+  ISPH_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(k_ilu_dense_build), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)kIluDenseLds));
+  hipLaunchKernelGGL(k_ilu_dense_build, dim3(nb), dim3(64), kIluDenseLds, ctx->stream, L->A.n, (const rp_t *)L->A.rp.p,
+                     (const int *)L->A.ci.p, (const double *)L->A.v.p, L->wsgs.p, G->ilu_fill, derr);
+  ISPH_CHECK(amg_read_int(ctx, derr, &herr));
+  if (herr & kIluDenseNoDiag) {   // (wsgs is built again by the Gauss-Seidel kernel)
+    ISPH_CHECK_HIP(hipMemsetAsync(derr, 0, sizeof(int), ctx->stream));
+    return ISPH_SUCCESS;
+  }
+  L->path[AMG_PATH_SMOOTHER] = 4;
+  *built = true;
+  return ISPH_SUCCESS;
+}
+
 inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
                       isph_amg **out) {
   ISPH_REQUIRE(prm->max_levels >= 1 && prm->max_levels <= 8, "max_levels must be in [1,8]");
   ISPH_REQUIRE(prm->smoother == 2 || (prm->block >= 64 && prm->block <= 1024 && prm->block % 64 == 0),
                "smoother block must be a multiple of 64 in [64,1024]");   // (Chebyshev has no blocks: the field is not read)
   ISPH_REQUIRE(prm->sweeps >= 1, "smoother sweeps must be >= 1");
-  ISPH_REQUIRE(prm->smoother >= 0 && prm->smoother <= 2,
-               "smoother must be 0 (symmetric Gauss-Seidel), 1 (Gauss-Seidel, efficient symmetric) or 2 (Chebyshev)");
+  // (3 is not a smoother and stays refused, as it was before the ILU smoother came: that one is 4)
+  ISPH_REQUIRE((prm->smoother >= 0 && prm->smoother <= 2) || prm->smoother == 4,
+               "smoother must be 0 (symmetric Gauss-Seidel), 1 (Gauss-Seidel, efficient symmetric), 2 (Chebyshev) or 4 (block ILU(k))");
+  ISPH_REQUIRE(prm->smoother != 4 || (prm->ilu_fill >= 0 && prm->ilu_fill <= 8),
+               "ILU smoother: ilu_fill (\"fact: level-of-fill\") must be in [0,8]");
+  ISPH_REQUIRE(prm->smoother != 4 || prm->cheb_value_bits != 32,
+               "cheb_value_bits = 32 needs the Chebyshev smoother (smoother 2): the ILU smoother keeps fp64 factor values");
   ISPH_REQUIRE(prm->smoother != 2 || prm->sweeps <= kChebMaxDegree, "Chebyshev smoother: sweeps is the polynomial degree, at most 16");
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_ratio > 1.0, "Chebyshev smoother: cheb_ratio (\"smoother: Chebyshev alpha\") must be > 1");
   ISPH_REQUIRE(prm->smoother != 2 || prm->cheb_value_bits == 0 || prm->cheb_value_bits == 64 || prm->cheb_value_bits == 32,
@@ -1946,6 +2064,8 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
   G->gs_eff = prm->smoother == 1;
   G->cheb = prm->smoother == 2;
+  G->ilu = prm->smoother == 4;
+  G->ilu_fill = G->ilu ? prm->ilu_fill : 0;
   DevTmp<char> tmp;
   DevTmp<int> derr;
   DevTmp<double> dg;
@@ -2135,7 +2255,14 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     // coarse levels are small: 64-row blocks keep enough waves busy (an 8-block level ran its sweeps on 8 waves)
     if (rc == ISPH_SUCCESS && (!last || G->coarse_smooth)) {
       const char *env_stream = getenv("ISPH_AMG_COARSE_STREAM");   // the chunk-stream sweeps on every level (rounds 2-4)
-      if (l > 0 && L->A.n > 0 && L->A.n <= kSgsDenseMaxRows && kAmgCoarseBlock == 64 && !(env_stream && env_stream[0] == '1')) {
+      const bool dense = l > 0 && L->A.n > 0 && L->A.n <= kSgsDenseMaxRows && kAmgCoarseBlock == 64 && !(env_stream && env_stream[0] == '1');
+      // smoother 4: block ILU(ilu_fill) in the place of the Gauss-Seidel factor -- but a coarsest level the smoother has to
+      // solve gets symmetric Gauss-Seidel (the rule of smoother 1; the complete LU of a singular block is no solver), and so
+      // does a level with a row that stores no diagonal entry (rank-local; the path reports the Gauss-Seidel value)
+      bool ilu_built = false;
+      if (G->ilu && !last) rc = amg_ilu_smoother(ctx, G, L, l, dense, derr.p, &ilu_built);
+      if (rc != ISPH_SUCCESS || ilu_built) continue;
+      if (dense) {
         const int nb = (L->A.n + 63) / 64;
         L->path[AMG_PATH_SMOOTHER] = 1;
         // symmetric sweeps: always on a coarsest level the smoother solves, otherwise unless the cycle uses the one-directional sweeps

@@ -1543,8 +1543,10 @@ inline int ilu_round_stream(isph_ctx *ctx, isph_ilu *F) {
   return ISPH_SUCCESS;
 }
 
+// no_diag != nullptr: set when the call fails because a row has no stored diagonal entry (err bit 1) -- the AMG smoothes
+// such a level by Gauss-Seidel instead (amg.hpp, isph_amg_params::smoother == 4)
 inline int ilu_create(isph_ctx *ctx, const isph_mat *A, int block_size, isph_ilu **out, bool sgs = false, int fill = 0,
-                      int nblocks_tab = 0, const int *host_bptr = nullptr, int value_bits = 64) {
+                      int nblocks_tab = 0, const int *host_bptr = nullptr, int value_bits = 64, bool *no_diag = nullptr) {
   ISPH_REQUIRE(value_bits == 64 || (value_bits == 32 && !sgs), "ILU: value_bits must be 64 or 32 (the Gauss-Seidel streams stay double)");
   const Sell &S = A->S;
   isph_ilu *F = nullptr;
@@ -1625,6 +1627,11 @@ inline int ilu_create(isph_ctx *ctx, const isph_mat *A, int block_size, isph_ilu
     if (rc == ISPH_SUCCESS) rc = ilu_schedule_and_factor(ctx, F, S, sgs);
   }
   if (rc == ISPH_SUCCESS && value_bits == 32) rc = ilu_round_stream(ctx, F);
+  if (rc != ISPH_SUCCESS && no_diag) {
+    int herr = 0;
+    *no_diag = hipMemcpyAsync(&herr, F->err.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+               hipStreamSynchronize(ctx->stream) == hipSuccess && (herr & 1) != 0;
+  }
   if (rc != ISPH_SUCCESS) { ilu_destroy(F); return rc; }
   *out = F;
   return ISPH_SUCCESS;

@@ -1480,6 +1480,15 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
     prm.block = block_size;
     M->type = 3;
     rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
+  } else if (!strncmp(type, "sa-amg-ilu", 10) && type[10] >= '0' && type[10] <= '8' && type[11] == 0) {
+    // "sa-amg-ilu<k>": "sa-amg" with ML's IFPACK smoother, block ILU(k) (isph_amg_params::smoother = 4, ilu_fill = k)
+    isph_amg_params prm;
+    isph_amg_params_default(&prm);
+    prm.block = block_size;
+    prm.smoother = 4;
+    prm.ilu_fill = type[10] - '0';
+    M->type = 3;
+    rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
   } else if (parse_chebyshev_type(type, &cheb_degree, &cheb_bits)) {
     // "chebyshev<d>", d = 1..16: Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults;
     // "chebyshev<d>-f32": the same with value_bits = 32
@@ -1489,7 +1498,7 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
     prm.value_bits = cheb_bits;
     rc = prec_chebyshev_init(ctx, A, &prm, M);
   } else {
-    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)", __FILE__, __LINE__);
+    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>|sa-amg-ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)", __FILE__, __LINE__);
   }
   if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
   M->order = A->order;
@@ -1733,6 +1742,7 @@ void isph_amg_params_default(isph_amg_params *p) {
   p->cheb_value_bits = 64;
   p->eig_type = 0; p->eig_iters = 10;  // "eigen-analysis: type" Anorm (the wrapper's rule); ML's "eigen-analysis: iterations"
   p->cycle_bits = 64;
+  p->ilu_fill = 0;  // Ifpack's "fact: level-of-fill"
 }
 
 int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec,

@@ -41,10 +41,13 @@ EXPORTS = [
 
 
 class AmgParams(C.Structure):
-    """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55)."""
+    """Mirror of isph_amg_params == the keys PrecondWrapper_ML::setParameters sets (precond_ml.h:44-55).  smoother: 0 / 1
+    the Gauss-Seidel smoothers, 2 Chebyshev, 4 block ILU(ilu_fill) (ML's "IFPACK" smoother; ilu_fill = "fact: level-of-fill",
+    0..8)."""
     _fields_ = [("max_levels", C.c_int), ("coarse_max", C.c_int), ("omega", C.c_double), ("block", C.c_int),
                 ("sweeps", C.c_int), ("theta", C.c_double), ("smoother", C.c_int), ("cheb_ratio", C.c_double),
-                ("cheb_value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int), ("cycle_bits", C.c_int)]
+                ("cheb_value_bits", C.c_int), ("eig_type", C.c_int), ("eig_iters", C.c_int), ("cycle_bits", C.c_int),
+                ("ilu_fill", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()

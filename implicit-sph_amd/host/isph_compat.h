@@ -57,7 +57,16 @@ class ParameterList {
   }
   std::string get(const std::string &k, const char *def) const { auto it = s_.find(k); return it == s_.end() ? std::string(def) : it->second; }
   bool isParameter(const std::string &k) const { return i_.count(k) || d_.count(k) || s_.count(k); }
+  // Teuchos: sublist(name) creates the sublist on first use; the const form of a missing sublist is an empty list
+  ParameterList &sublist(const std::string &k) { return sub_[k]; }
+  const ParameterList &sublist(const std::string &k) const {
+    static const ParameterList empty;
+    auto it = sub_.find(k);
+    return it == sub_.end() ? empty : it->second;
+  }
+  bool isSublist(const std::string &k) const { return sub_.count(k) != 0; }
  private:
+  std::map<std::string, ParameterList> sub_;
   std::map<std::string, int> i_;
   std::map<std::string, double> d_;
   std::map<std::string, std::string> s_;

@@ -59,16 +59,36 @@ class PrecondWrapper_ML : public PrecondWrapper {
     // "Chebyshev" ("MLS" is ML's old name for it; the line the benchmark's ml.xml carries commented out): a polynomial of
     // degree "smoother: sweeps" in D^-1 A on [rho / "smoother: Chebyshev alpha", 1.1 rho]
     const bool cheb = smo == "Chebyshev" || smo == "MLS";
-    if (agg != "Uncoupled" || !(smo == "symmetric Gauss-Seidel" || eff || cheb)) {
+    // "IFPACK" with "smoother: ifpack type" = "ILU", "smoother: ifpack overlap" = 0 and "fact: level-of-fill" in the sublist
+    // "smoother: ifpack list" (sph-script/ml-ifpack.xml): block ILU(k) Richardson sweeps, isph_amg_params::smoother = 4
+    const bool ifpack = smo == "IFPACK";
+    if (agg != "Uncoupled" || !(smo == "symmetric Gauss-Seidel" || eff || cheb || ifpack)) {
       std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): aggregation '%s' with smoother '%s' is not available; available: "
                            "\"Uncoupled\" aggregation with \"symmetric Gauss-Seidel\", with \"Gauss-Seidel\" / \"ML Gauss-Seidel\" "
-                           "plus \"smoother: Gauss-Seidel efficient symmetric\", or with \"Chebyshev\" / \"MLS\"\n",
+                           "plus \"smoother: Gauss-Seidel efficient symmetric\", with \"Chebyshev\" / \"MLS\", or with \"IFPACK\" "
+                           "(\"smoother: ifpack type\" = \"ILU\")\n",
                    agg.c_str(), smo.c_str());
       return ISPH_FAILURE;
     }
     isph_amg_params prm;
     isph_amg_params_default(&prm);
-    prm.smoother = cheb ? 2 : eff ? 1 : 0;
+    prm.smoother = ifpack ? 4 : cheb ? 2 : eff ? 1 : 0;
+    if (ifpack) {
+      const std::string itype = _param->get("smoother: ifpack type", "ILU");
+      const int overlap = _param->get("smoother: ifpack overlap", 0);
+      if (itype != "ILU") {
+        std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): \"smoother: ifpack type\" = '%s' is not available; available: \"ILU\"\n",
+                     itype.c_str());
+        return ISPH_FAILURE;
+      }
+      if (overlap != 0) {
+        std::fprintf(stderr, ">> PrecondWrapper_ML(HIP): \"smoother: ifpack overlap\" = %d is not available; available: 0\n", overlap);
+        return ISPH_FAILURE;
+      }
+      // Ifpack's default level of fill is 0; a value outside 0..8 is refused by the create call, ilu_fill named
+      const Teuchos::ParameterList &ilist = *_param;
+      prm.ilu_fill = ilist.sublist("smoother: ifpack list").get("fact: level-of-fill", 0);
+    }
     if (cheb) prm.cheb_ratio = _param->get("smoother: Chebyshev alpha", 20.0);
     // device-side extension (not a reference key), read for the Chebyshev smoother only: 32 = the smoother's sweeps read
     // the level operators rounded to float (isph_amg_params::cheb_value_bits); the hierarchy itself stays fp64
