@@ -156,6 +156,22 @@ def build_cpp_pattern_hold_test(force=False):
     return CPP_PATTERN_HOLD_TEST
 
 
+CPP_AMG_REFRESH_TEST = os.path.join(ROOT, "tests", "cpp", "test_amg_refresh_wrappers")
+
+
+def build_cpp_amg_refresh_test(force=False):
+    """C++ driver of the wrappers' kept-and-refreshed device objects under SolverLin_Belos::holdPattern (host/*.h), linked
+    like build_cpp_test; used by tests/test_gpu_amg_refresh_wrappers.py."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_amg_refresh_wrappers.cpp")
+    host = os.path.join(PKG, "host")
+    deps = [src] + [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(INC, "isph_hip.h")]
+    if force or _stale(CPP_AMG_REFRESH_TEST, deps):
+        build_hip()
+        _run(["g++", "-O2", "-std=c++17", "-I", INC, "-I", host, "-o", CPP_AMG_REFRESH_TEST, src,
+              "-L", PKG, "-lisph_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return CPP_AMG_REFRESH_TEST
+
+
 CPP_EIG_TEST = os.path.join(ROOT, "tests", "cpp", "test_eig_estimate_wrappers")
 
 

@@ -22,6 +22,8 @@
 // isph_amg_params::cycle_bits = 32 (smoother 2 only): the whole V cycle in single-precision STORAGE -- float planes of A_l, P_l,
 // P_l^T and A_l P_l, float level vectors, fp64 arithmetic with one rounding per stored element (amg_vcycle_t<float>,
 // include/isph_hip.h states the arithmetic); the hierarchy stays the fp64 one.  Not a linear operator: flexible GMRES only.
+// isph_prec_refactor (amg_refactor): the hierarchy of new matrix values on the aggregates and patterns of a create call that
+// ran while isph_ctx_hold_pattern was on -- ML's ReComputePreconditioner (k_prolong_values, k_spgemm_values).
 // Set-up kernels work on device CSR copies, one wave per row (rows hold ~100 entries on the fine level); the
 // cycle itself uses the SELL SpMV and the chunk-stream triangular solves of the rest of the library.
 #pragma once
@@ -54,6 +56,14 @@ struct DCsr {
   void release() { rp.release(); ci.release(); v.release(); n = m = 0; nnz = 0; }
 };
 
+// a buffer changes hands (a temporary of the set-up that a held hierarchy keeps)
+template <class T>
+inline void dev_move(DevBuf<T> &dst, DevBuf<T> &src) {
+  dst.release();
+  dst.p = src.p; dst.cap = src.cap; dst.bytes = src.bytes; dst.guard_at = src.guard_at;
+  src.p = nullptr; src.cap = 0; src.bytes = 0; src.guard_at = 0;
+}
+
 struct AmgLevel {
   DCsr A;                    // device CSR of the level operator (fine level: a copy of the SELL matrix)
   const isph_mat *Am = nullptr;
@@ -81,6 +91,15 @@ struct AmgLevel {
   long long path[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // isph_amg_params::eig_type == 1: the estimate of lambda_max(D^-1 A_l) of this level's fp64 operator (eig_estimate.hpp)
   EigResult eig;
+  // a hierarchy created while isph_ctx_hold_pattern was on (isph_amg::held) keeps what amg_refactor needs besides agg and the
+  // patterns of P, R and A: the members of every aggregate (the sorted keys and segment starts of amg_prolongator), for
+  // every entry of R the position of its value in P, and the pattern of A P with ascending columns (AP.v only lives
+  // during a refresh).  The CSR rows of P, A P and the coarse A ascend like the rows of their SELL images Pm, APm, Aown:
+  // entry k of a row is entry k of the image's row, so the refreshed values need no map to reach the images.
+  DevBuf<unsigned long long> mkeys;
+  DevBuf<int> mstart;
+  DevBuf<unsigned> tmap;
+  DCsr AP;
 };
 enum { AMG_PATH_MIS_ROUNDS = 0, AMG_PATH_MIS_LIST_ROUNDS, AMG_PATH_PROLONG, AMG_PATH_AP, AMG_PATH_GALERKIN, AMG_PATH_SMOOTHER,
        AMG_PATH_COARSE, AMG_PATH_PREP };
@@ -104,6 +123,11 @@ struct isph_amg {
   // inverted on every rank (nc = its global size, rows nc_off .. nc_off + nc_loc are this rank's)
   int dist = 0, nc_off = 0, nc_loc = 0;
   isph::DevBuf<double> bglob;
+  // isph_prec_refactor: held = created on one rank while isph_ctx_hold_pattern was on (the levels keep their aggregates and
+  // the maps of AmgLevel); omega and cheb_ratio of the create call; refreshes = amg_refactor calls that went through
+  int held = 0;
+  double omega = 0.0, cheb_ratio = 0.0;
+  long long refreshes = 0;
 };
 
 namespace isph {
@@ -954,6 +978,211 @@ __global__ void k_rows_compact(int n, int cap_shift, const rp_t *__restrict__ rp
   for (int s2 = s0; s2 < len; s2 += 16) { ci[b + s2] = tci[src + s2]; v[b + s2] = tcv[src + s2]; }
 }
 
+// ---- new values into kept patterns (amg_refactor) ----------------------------------------------------------------------
+// The hierarchy of new matrix values on the aggregates of a create call that ran while isph_ctx_hold_pattern was on: the
+// patterns of P_l, R_l, A_l P_l and A_{l+1} stand, only their values are computed.  Both kernels below work the same way.
+// The terms of a row (P: -damp/a_ii a_ij pt_j for the aggregate of j; a product: x_ik y_kc for column c) are STAGED in LDS in
+// the order the data gives them -- the entries of the row, and behind every entry of X's row the row of Y -- and every
+// kept slot of the output row is OWNED by one lane, which walks the staged terms in that order and adds those of its
+// column.  No hash table, no column is written, nothing is compacted; no atomic touches a value, and the order of the
+// additions into a slot is the order of the terms in the data, so two refreshes from the same values give the same bits.
+// The owner's walk IS the look-up of a term's slot: a term nobody owns (a coupling the kept pattern has no room for) shows
+// as a difference between the terms staged and the terms taken, raises kAmgNoSlot in err[0] and leaves the row in err[1]
+// (the smallest such row); it is never written anywhere.  Width ladder: the first LPR (64) slots of a row live in a
+// register of their owner for the whole row; a row with more slots keeps the further ones in the output row itself
+// between the rounds (each lane reads and writes its own slots only).  A slot that no term reaches holds 0.
+constexpr int kAmgNoSlot = 32;
+
+// the owner's walk over m staged terms (columns tc, values tv, both 16-byte aligned; the columns behind m up to the next
+// multiple of four are -1): four terms per trip, no branch -- a term of another column adds 0.0, which leaves the sum as it
+// is -- so the LDS reads of the next trip do not wait for a comparison
+__device__ __forceinline__ void amg_take_terms(const int *tc, const double *tv, int m, int c, double &acc, int &taken) {
+  for (int e = 0; e < m; e += 4) {
+    const int4 cc = *reinterpret_cast<const int4 *>(tc + e);
+    const double2 v01 = *reinterpret_cast<const double2 *>(tv + e), v23 = *reinterpret_cast<const double2 *>(tv + e + 2);
+    const bool h0 = cc.x == c, h1 = cc.y == c, h2 = cc.z == c, h3 = cc.w == c;
+    acc += h0 ? v01.x : 0.0;
+    acc += h1 ? v01.y : 0.0;
+    acc += h2 ? v23.x : 0.0;
+    acc += h3 ? v23.y : 0.0;
+    taken += (int)h0 + (int)h1 + (int)h2 + (int)h3;
+  }
+}
+
+// Row i of P = (I - damp D^-1 A) P_tent into prp[i]..prp[i+1].  LPR lanes per row: 16 (four rows per wave) when the create
+// call's one-pass kernel ran with 16 (isph_prec_amg_path [2]: every row holds at most 16 aggregates), 64 otherwise.
+template <int LPR>
+__global__ __launch_bounds__(256) void k_prolong_values(int n, const rp_t *__restrict__ rp, const int *__restrict__ ci,
+                                                        const double *__restrict__ v, const double *__restrict__ dg,
+                                                        const int *__restrict__ agg, const double *__restrict__ pt, double damp,
+                                                        const rp_t *__restrict__ prp, const int *__restrict__ pci,
+                                                        double *__restrict__ pv, int *__restrict__ err) {
+  constexpr int RPW = 64 / LPR, CH = 4 * LPR;   // CH: entries of A's row staged per round
+  __shared__ __attribute__((aligned(16))) int sa[kAmgWaves * RPW][CH];
+  __shared__ __attribute__((aligned(16))) double st[kAmgWaves * RPW][CH];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane / LPR, sub = lane % LPR;
+  const int tr = w * RPW + g;
+  const int i = (blockIdx.x * kAmgWaves + w) * RPW + g;
+  const bool live = i < n;   // the lanes of a row past the end walk along: the wave barriers below are for all 64
+  rp_t lo = 0, pb = 0;
+  int len = 0, cnt = 0, ai = -1;
+  double f = 0.0, pti = 0.0;
+  if (live) {
+    lo = rp[i]; len = (int)(rp[i + 1] - lo);
+    pb = prp[i]; cnt = (int)(prp[i + 1] - pb);
+    ai = agg[i]; pti = pt[i];
+    f = dg[i] != 0.0 ? damp / dg[i] : 0.0;
+  }
+  const int rounds = (wave_max_i32(len) + CH - 1) / CH, groups = (wave_max_i32(cnt) + LPR - 1) / LPR;
+  int terms = (sub == 0 && ai >= 0) ? 1 : 0, taken = 0;   // the row's own aggregate is a term too
+  int c0 = -1;
+  double acc0 = 0.0;
+  if (sub < cnt) {
+    c0 = pci[pb + sub];
+    if (c0 == ai) { acc0 = pti; ++taken; }
+  }
+  for (int gi = 1; gi < groups; ++gi) {
+    const int s = gi * LPR + sub;
+    if (s < cnt) {
+      const bool own = pci[pb + s] == ai;
+      pv[pb + s] = own ? pti : 0.0;
+      taken += own;
+    }
+  }
+  for (int r = 0; r < rounds; ++r) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int e = u * LPR + sub, k = r * CH + e;
+      int a = -1;
+      double term = 0.0;
+      if (k < len) {
+        const int j = ci[lo + k];
+        if (j < n) {
+          const int aj = agg[j];
+          if (aj >= 0) { a = aj; term = -(f * v[lo + k] * pt[j]); }
+        }
+      }
+      sa[tr][e] = a;
+      st[tr][e] = term;
+      terms += a >= 0;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int m = min(CH, len - r * CH);   // staged entries of this row (<= 0: none; the slots behind them hold column -1)
+    if (c0 >= 0) amg_take_terms(sa[tr], st[tr], m, c0, acc0, taken);
+    for (int gi = 1; gi < groups; ++gi) {
+      const int s = gi * LPR + sub;
+      if (s < cnt) {
+        double a2 = pv[pb + s];
+        amg_take_terms(sa[tr], st[tr], m, pci[pb + s], a2, taken);
+        pv[pb + s] = a2;
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (c0 >= 0) pv[pb + sub] = acc0;
+  int d = terms - taken;
+  for (int o = LPR / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);   // (integers: the order does not matter)
+  if (live && sub == 0 && d != 0) { atomicOr(err, kAmgNoSlot); atomicMin(err + 1, i); }
+}
+
+// C = X * Y into the kept rows crp / cci of C (A_l P_l and R_l (A_l P_l)), one wave per row.  The products of 64 entries
+// of X's row are laid out flat (prefix sum of the Y row lengths, as in k_spgemm_rows) and staged kValStage at a time; a
+// lane stages the products of its own X entry, in the order of Y's row.
+constexpr int kValStage = 512;
+__global__ __launch_bounds__(256) void k_spgemm_values(int n, int yrows, const rp_t *__restrict__ xrp, const int *__restrict__ xci,
+                                                       const double *__restrict__ xv, const rp_t *__restrict__ yrp,
+                                                       const int *__restrict__ yci, const double *__restrict__ yv,
+                                                       const rp_t *__restrict__ crp, const int *__restrict__ cci,
+                                                       double *__restrict__ cv, int *__restrict__ err) {
+  __shared__ __attribute__((aligned(16))) int sc[kAmgWaves][kValStage];
+  __shared__ __attribute__((aligned(16))) double sp[kAmgWaves][kValStage];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = blockIdx.x * kAmgWaves + w;
+  if (i >= n) return;   // wave-uniform; the kernel has no workgroup barrier
+  const rp_t cb = crp[i];
+  const int cnt = (int)(crp[i + 1] - cb), groups = (cnt + 63) / 64;
+  int c0 = -1, terms = 0, taken = 0;
+  double acc0 = 0.0;
+  if (lane < cnt) c0 = cci[cb + lane];
+  for (int gi = 1; gi < groups; ++gi)
+    if (gi * 64 + lane < cnt) cv[cb + gi * 64 + lane] = 0.0;
+  const rp_t x0 = xrp[i], x1 = xrp[i + 1];
+  for (rp_t pp = x0; pp < x1; pp += 64) {
+    const rp_t p = pp + lane;
+    int len = 0;
+    rp_t qb = 0;
+    double xa = 0.0;
+    if (p < x1) {
+      const int k = xci[p];
+      if (k < yrows) { xa = xv[p]; qb = yrp[k]; len = (int)(yrp[k + 1] - qb); }
+    }
+    const int incl = wave_scan_incl_i32(len);
+    const int T = __builtin_amdgcn_readlane(incl, 63), start = incl - len;
+    terms += len;
+    for (int t0 = 0; t0 < T; t0 += kValStage) {   // wave-uniform
+      const int xb = max(start, t0), xe = min(start + len, t0 + kValStage);
+      for (int x = xb; x < xe; ++x) {
+        const rp_t q = qb + (x - start);
+        sc[w][x - t0] = yci[q];
+        sp[w][x - t0] = xa * yv[q];
+      }
+      const int m = min(kValStage, T - t0);
+      if (lane < 4 && m + lane < kValStage) { sc[w][m + lane] = -1; sp[w][m + lane] = 0.0; }   // amg_take_terms reads in fours
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      if (c0 >= 0) amg_take_terms(sc[w], sp[w], m, c0, acc0, taken);
+      for (int gi = 1; gi < groups; ++gi) {
+        const int s = gi * 64 + lane;
+        if (s < cnt) {
+          double a2 = cv[cb + s];
+          amg_take_terms(sc[w], sp[w], m, cci[cb + s], a2, taken);
+          cv[cb + s] = a2;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  if (c0 >= 0) cv[cb + lane] = acc0;
+  int d = terms - taken;
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  if (lane == 0 && d != 0) { atomicOr(err, kAmgNoSlot); atomicMin(err + 1, i); }
+}
+
+// tmap[q] = position in P of the entry that entry q of R = P^T holds: row i = rci[q] of P, the slot of column c (P's rows
+// ascend: binary search).  One wave per row of R.
+__global__ __launch_bounds__(256) void k_transpose_map(int nr, const rp_t *__restrict__ rrp, const int *__restrict__ rci,
+                                                       const rp_t *__restrict__ prp, const int *__restrict__ pci,
+                                                       unsigned *__restrict__ tmap) {
+  const int c = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (c >= nr) return;
+  for (rp_t q = rrp[c] + lane; q < rrp[c + 1]; q += 64) {
+    const int i = rci[q];
+    rp_t lo = prp[i], hi = prp[i + 1] - 1;
+    while (lo < hi) {
+      const rp_t mid = (lo + hi) >> 1;
+      if (pci[mid] < c) lo = mid + 1; else hi = mid;
+    }
+    tmap[q] = (unsigned)lo;
+  }
+}
+__global__ void k_gather_values(long long nnz, const unsigned *__restrict__ map, const double *__restrict__ src, double *__restrict__ dst) {
+  const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < nnz) dst[q] = src[map[q]];
+}
+// the values of a CSR whose rows ascend into the SELL image of the same rows (entry k of row i is entry k of its image)
+__global__ void k_csr_values_to_sell(int n, const rp_t *__restrict__ rp, const double *__restrict__ v,
+                                     const long long *__restrict__ slice_off, double *__restrict__ sval) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long long off = slice_off[i >> 6];
+  const rp_t b = rp[i];
+  const int len = (int)(rp[i + 1] - b);
+  for (int k = 0; k < len; ++k) sval[sell_pos(off, i & 63, k)] = v[b + k];
+}
+
 // y = R x for a CSR matrix with long rows: one wave per row, coalesced reads of the row, fixed-order wave sum
 // VT = XT = float (the cycle_bits = 32 V cycle): float values and vectors, widened; the sum is fp64 and rounded once
 template <class VT = double, class XT = double>
@@ -1479,6 +1708,7 @@ inline void amg_level_destroy(AmgLevel *L) {
   L->agg.release(); L->nv.release(); L->x.release(); L->b.release(); L->r.release(); L->z.release();
   L->x32.release(); L->b32.release(); L->r32.release(); L->p32.release(); L->ap32.release(); L->rv32.release();
   L->xm.release(); L->bm.release(); L->rm.release();
+  L->mkeys.release(); L->mstart.release(); L->tmap.release(); L->AP.release();
   delete L;
 }
 
@@ -1596,8 +1826,9 @@ inline int amg_aggregate(isph_ctx *ctx, AmgLevel *L, double *dg, unsigned long l
 // P = (I - omega/rho D^-1 A) P_tent and the coarse null vector
 // rho_ready: the device word already holds rho (amg_aggregate with threshold 0)
 // lambda > 0 (isph_amg_params::eig_type == 1): the damping is omega / lambda, the level's clipped eigenvalue estimate
+// keep (a held hierarchy): the sorted member keys and the segment starts stay with the level (amg_refactor)
 inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigned long long *rho_dev, bool rho_ready, int nagg, double omega,
-                           DevBuf<double> &nvc, DevBuf<char> &tmp, int *derr, double lambda = 0.0) {
+                           DevBuf<double> &nvc, DevBuf<char> &tmp, int *derr, double lambda = 0.0, bool keep = false) {
   const DCsr &A = L->A;
   const int n = A.n;
   DevTmp<unsigned long long> k0, k1;
@@ -1706,6 +1937,7 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
                          (int *)nullptr, (const rp_t *)P.rp.p, P.ci.p, P.v.p, derr);
   }
   if (rc == ISPH_SUCCESS && hipGetLastError() != hipSuccess) rc = fail("prolongator kernels failed", __FILE__, __LINE__);
+  if (rc == ISPH_SUCCESS && keep) { dev_move(L->mkeys, k1); dev_move(L->mstart, start); }
   k0.release(); k1.release(); start.release(); cnt.release(); pt.release();
   return rc;
 }
@@ -2007,6 +2239,11 @@ inline int amg_float_planes(isph_ctx *ctx, isph_amg *G) {
 // stores no diagonal entry: the caller builds the Gauss-Seidel smoother instead.  derr: the set-up's error word, 0 on entry.
 inline int amg_ilu_smoother(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int l, bool dense, int *derr, bool *built) {
   *built = false;
+  if (!dense && L->sgs) {   // amg_refactor: the factor of the create call stands, its values are redone (ilu_refactor)
+    ISPH_CHECK(ilu_refactor(ctx, L->sgs, L->Am->S));
+    *built = true;
+    return ISPH_SUCCESS;
+  }
   if (!dense) {
     bool no_diag = false;
     const int rc = ilu_create(ctx, L->Am, l == 0 ? G->block : kAmgCoarseBlock, &L->sgs, /*sgs=*/false, G->ilu_fill, 0, nullptr, 64, &no_diag);
@@ -2030,6 +2267,107 @@ inline int amg_ilu_smoother(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int l
   L->path[AMG_PATH_SMOOTHER] = 4;
   *built = true;
   return ISPH_SUCCESS;
+}
+
+// the smoother of every level and its work vectors (amg_create; amg_refactor on the refreshed operators: a polynomial or a
+// Gauss-Seidel stream that exists has been destroyed by the caller, a block ILU stream is refactored where it stands, the
+// dense block inverses are written again).  rc: the outcome of the set-up so far.
+inline int amg_smoothers(isph_ctx *ctx, isph_amg *G, bool dist, int *derr, int rc) {
+  // Chebyshev across ranks: rho of a level is all-reduced, one collective call per level.  The walk is entered only
+  // when the set-up has succeeded so far -- after the consensus above that is all ranks or none, and with success on all
+  // ranks every rank has gone through the same coarsening steps, so nlev is agreed here (a rank that failed in a step
+  // holds one level less than its peers; none of them walks).  A failure that arises INSIDE the walk is carried through
+  // the remaining levels' all-reduces (prior_failure), so that the ranks' calls still pair up.
+  const bool walk = dist && G->cheb && rc == ISPH_SUCCESS;
+  for (int l = 0; l < G->nlev && (rc == ISPH_SUCCESS || walk); ++l) {
+    AmgLevel *L = G->L[(size_t)l];
+    if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L, G->cycle_bits == 32);
+    const bool last = l == G->nlev - 1;
+    if (last) L->path[AMG_PATH_COARSE] = G->coarse_smooth ? 2 : 1;
+    if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
+      if (!last || G->coarse_smooth) {
+        L->path[AMG_PATH_SMOOTHER] = 3;
+        // eig_type 1: the interval [lambda / cheb_ratio, 1.1 lambda] from the level's estimate -- the one the damping used
+        // for double values, a second one on the float plane for cheb_value_bits 32 (the interval comes from fl32(A_l))
+        const bool reuse = G->eig_type == 1 && G->cheb_value_bits != 32;
+        const int r2 = cheb_setup(ctx, L->Am, G->sweeps, G->cheb_ratio, reuse ? L->eig.lambda_used : 0.0, 0.0, /*empty_ok=*/l > 0,
+                                  /*collective=*/dist, /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits,
+                                  reuse ? 0 : G->eig_type, G->eig_iters, l, G->cycle_bits);
+        if (rc == ISPH_SUCCESS) rc = r2;
+      }
+      continue;
+    }
+    // coarse levels are small: 64-row blocks keep enough waves busy (an 8-block level ran its sweeps on 8 waves)
+    if (rc == ISPH_SUCCESS && (!last || G->coarse_smooth)) {
+      const char *env_stream = getenv("ISPH_AMG_COARSE_STREAM");   // the chunk-stream sweeps on every level (rounds 2-4)
+      const bool dense = l > 0 && L->A.n > 0 && L->A.n <= kSgsDenseMaxRows && kAmgCoarseBlock == 64 && !(env_stream && env_stream[0] == '1');
+      // smoother 4: block ILU(ilu_fill) in the place of the Gauss-Seidel factor -- but a coarsest level the smoother has to
+      // solve gets symmetric Gauss-Seidel (the rule of smoother 1; the complete LU of a singular block is no solver), and so
+      // does a level with a row that stores no diagonal entry (rank-local; the path reports the Gauss-Seidel value)
+      bool ilu_built = false;
+      if (G->ilu && !last) rc = amg_ilu_smoother(ctx, G, L, l, dense, derr, &ilu_built);
+      if (rc != ISPH_SUCCESS || ilu_built) continue;
+      if (dense) {
+        const int nb = (L->A.n + 63) / 64;
+        L->path[AMG_PATH_SMOOTHER] = 1;
+        // symmetric sweeps: always on a coarsest level the smoother solves, otherwise unless the cycle uses the one-directional sweeps
+        const bool need_sym = last || !G->gs_eff, need_dir = G->gs_eff && !last;
+        auto build = [&](DevBuf<double> &W, int mode) {
+          int r2 = W.reserve((size_t)nb * 4096);
+          if (r2 == ISPH_SUCCESS)
+            hipLaunchKernelGGL(k_sgs_dense_build, dim3(nb), dim3(64), 0, ctx->stream, L->A.n, (const rp_t *)L->A.rp.p,
+                               (const int *)L->A.ci.p, (const double *)L->A.v.p, W.p, mode);
+          return r2;
+        };
+        if (need_sym) rc = build(L->wsgs, 0);
+        if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wfwd, 1);
+        if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wbwd, 2);
+      } else {
+        L->path[AMG_PATH_SMOOTHER] = 2;
+        rc = ilu_create(ctx, L->Am, l == 0 ? G->block : kAmgCoarseBlock, &L->sgs, /*sgs=*/true);
+      }
+    }
+  }
+  return rc;
+}
+
+// the dense inverse of the coarsest operator on one rank (err bit 4: singular)
+inline int amg_coarse_inverse(isph_ctx *ctx, isph_amg *G, int *derr) {
+  AmgLevel *L = G->L.back();
+  const int nc = L->A.n;
+  G->nc = nc;
+  int rc = G->cinv.reserve((size_t)2 * nc * nc + (size_t)nc + 1);
+  if (rc == ISPH_SUCCESS && nc > 0) {
+    hipLaunchKernelGGL(k_dense_from_csr, dim3(nc), dim3(kBlock), 0, ctx->stream, nc, (const rp_t *)L->A.rp.p,
+                       (const int *)L->A.ci.p, (const double *)L->A.v.p, G->cinv.p);
+    rc = amg_dense_invert(ctx, G->cinv.p, nc, derr);
+    int herr = 0;
+    if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr, &herr);
+    if (rc == ISPH_SUCCESS && (herr & 4)) rc = fail("AMG: coarsest operator is singular (pass the null vector)", __FILE__, __LINE__);
+  }
+  return rc;
+}
+
+// held hierarchy: tmap of level L (k_transpose_map)
+inline int amg_transpose_map(isph_ctx *ctx, AmgLevel *L) {
+  const DCsr &P = L->P, &R = L->R;
+  ISPH_REQUIRE(P.nnz < 4294967295LL, "AMG: a prolongator of 2^32 entries or more cannot be held (the transposition map is 32 bits wide)");
+  ISPH_CHECK(L->tmap.reserve((size_t)(R.nnz > 0 ? R.nnz : 1)));
+  if (R.n > 0)
+    hipLaunchKernelGGL(k_transpose_map, dim3(amg_wave_grid(R.n)), dim3(256), 0, ctx->stream, R.n, (const rp_t *)R.rp.p,
+                       (const int *)R.ci.p, (const rp_t *)P.rp.p, (const int *)P.ci.p, L->tmap.p);
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+// held hierarchy: the rows of C with ascending columns, through the row sort of the SELL conversion and back
+inline int amg_sort_rows(isph_ctx *ctx, DCsr &C, DevBuf<char> &tmp) {
+  isph_mat *T = nullptr;
+  ISPH_CHECK(mat_from_device_csr(ctx, C.n, C.m, C.rp.p, C.ci.p, C.v.p, C.nnz, &T));
+  C.release();
+  const int rc = amg_csr_from_sell(ctx, T->S, C, tmp);
+  isph_mat_destroy(T);
+  return rc;
 }
 
 inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
@@ -2066,6 +2404,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   G->cheb = prm->smoother == 2;
   G->ilu = prm->smoother == 4;
   G->ilu_fill = G->ilu ? prm->ilu_fill : 0;
+  G->omega = prm->omega; G->cheb_ratio = prm->cheb_ratio;
   DevTmp<char> tmp;
   DevTmp<int> derr;
   DevTmp<double> dg;
@@ -2103,6 +2442,8 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   const char *env_local = getenv("ISPH_AMG_RANK_LOCAL");
   const bool dist = comm_active(ctx) && ctx->nranks > 1 && !(env_local && env_local[0] == '1');
   G->dist = dist ? 1 : 0;
+  // isph_ctx_hold_pattern, one rank: the levels keep what amg_refactor needs (AmgLevel); off: nothing below changes
+  G->held = ctx->pattern_hold && !dist && !mat_has_halo(Am);
   while ((dist || rc == ISPH_SUCCESS) && G->nlev < prm->max_levels) {
     AmgLevel *L = G->L.back();
     const int n = L->A.n;
@@ -2141,7 +2482,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     AmgLevel *Lc = new AmgLevel();
     if (rc == ISPH_SUCCESS && identity) { nagg = n; rc = amg_identity_prolongator(ctx, L, Lc->nv); }
     else if (rc == ISPH_SUCCESS) rc = amg_prolongator(ctx, L, dg.p, rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, tmp, derr.p,
-                              G->eig_type == 1 ? L->eig.lambda_used : 0.0);
+                              G->eig_type == 1 ? L->eig.lambda_used : 0.0, G->held != 0);
     DCsr AP, Pext;
     DCsr &R = L->R;
     const isph_halo &H = L->Am->halo;
@@ -2173,7 +2514,10 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
       }
     }
     if (rc == ISPH_SUCCESS) rc = amg_transpose(ctx, L->P, R, tmp);
+    if (rc == ISPH_SUCCESS && G->held) rc = amg_transpose_map(ctx, L);
     if (rc == ISPH_SUCCESS) rc = amg_spgemm_ap(ctx, L->A, extended ? Pext : L->P, AP, tmp, derr.p, &L->path[AMG_PATH_AP]);
+    // held: the kept rows of A P must ascend; the table kernels (stages 3-5) leave them in table order
+    if (rc == ISPH_SUCCESS && G->held && L->path[AMG_PATH_AP] >= 3) rc = amg_sort_rows(ctx, AP, tmp);
     if (rc == ISPH_SUCCESS) {
       L->path[AMG_PATH_GALERKIN] = AP.m <= kGalerkinTable ? 1 : 2;   // k_spgemm's ycols <= TABLE: direct-addressed / open addressing
       rc = amg_spgemm_t<kGalerkinTable, 64>(ctx, R, AP, Lc->A, tmp, derr.p);
@@ -2194,6 +2538,13 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
         ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
       rc = mat_from_device_csr(ctx, AP.n, AP.m, AP.rp.p, AP.ci.p, AP.v.p, AP.nnz, &L->APm, /*rows_sorted=*/true);
       if (rc == ISPH_SUCCESS) L->APm->local = true;
+    }
+    if (rc == ISPH_SUCCESS && G->held) {
+      // the pattern of A P stays; so does the coarse operator in the row order of its SELL image (columns ascending)
+      L->AP.n = AP.n; L->AP.m = AP.m; L->AP.nnz = AP.nnz;
+      dev_move(L->AP.rp, AP.rp); dev_move(L->AP.ci, AP.ci);
+      Lc->A.release();
+      rc = amg_csr_from_sell(ctx, Lc->Aown->S, Lc->A, tmp);
     }
     AP.release();
     if (rc == ISPH_SUCCESS && extended) {   // the coarse operator exchanges with the same peers (lists: amg_extend_pack / amg_extend_finish)
@@ -2228,61 +2579,7 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   // eig_type 1: the coarsest level has no prolongator but its estimate serves the polynomial that "solves" it and
   // isph_prec_eig_estimate (dist: rc is agreed between the ranks here)
   if (G->eig_type == 1 && rc == ISPH_SUCCESS) rc = amg_level_estimate(ctx, G, G->L.back(), G->nlev - 1, dist);
-  // Chebyshev across ranks: rho of a level is all-reduced, one collective call per level.  The walk is entered only
-  // when the set-up has succeeded so far -- after the consensus above that is all ranks or none, and with success on all
-  // ranks every rank has gone through the same coarsening steps, so nlev is agreed here (a rank that failed in a step
-  // holds one level less than its peers; none of them walks).  A failure that arises INSIDE the walk is carried through
-  // the remaining levels' all-reduces (prior_failure), so that the ranks' calls still pair up.
-  const bool walk = dist && G->cheb && rc == ISPH_SUCCESS;
-  for (int l = 0; l < G->nlev && (rc == ISPH_SUCCESS || walk); ++l) {
-    AmgLevel *L = G->L[(size_t)l];
-    if (rc == ISPH_SUCCESS) rc = amg_level_buffers(L, G->cycle_bits == 32);
-    const bool last = l == G->nlev - 1;
-    if (last) L->path[AMG_PATH_COARSE] = G->coarse_smooth ? 2 : 1;
-    if (G->cheb) {   // no Gauss-Seidel factor, no dense block inverses: the diagonal and rho of the level operator
-      if (!last || G->coarse_smooth) {
-        L->path[AMG_PATH_SMOOTHER] = 3;
-        // eig_type 1: the interval [lambda / cheb_ratio, 1.1 lambda] from the level's estimate -- the one the damping used
-        // for double values, a second one on the float plane for cheb_value_bits 32 (the interval comes from fl32(A_l))
-        const bool reuse = G->eig_type == 1 && G->cheb_value_bits != 32;
-        const int r2 = cheb_setup(ctx, L->Am, G->sweeps, prm->cheb_ratio, reuse ? L->eig.lambda_used : 0.0, 0.0, /*empty_ok=*/l > 0,
-                                  /*collective=*/dist, /*prior_failure=*/rc != ISPH_SUCCESS, &L->cheb, G->cheb_value_bits,
-                                  reuse ? 0 : G->eig_type, G->eig_iters, l, G->cycle_bits);
-        if (rc == ISPH_SUCCESS) rc = r2;
-      }
-      continue;
-    }
-    // coarse levels are small: 64-row blocks keep enough waves busy (an 8-block level ran its sweeps on 8 waves)
-    if (rc == ISPH_SUCCESS && (!last || G->coarse_smooth)) {
-      const char *env_stream = getenv("ISPH_AMG_COARSE_STREAM");   // the chunk-stream sweeps on every level (rounds 2-4)
-      const bool dense = l > 0 && L->A.n > 0 && L->A.n <= kSgsDenseMaxRows && kAmgCoarseBlock == 64 && !(env_stream && env_stream[0] == '1');
-      // smoother 4: block ILU(ilu_fill) in the place of the Gauss-Seidel factor -- but a coarsest level the smoother has to
-      // solve gets symmetric Gauss-Seidel (the rule of smoother 1; the complete LU of a singular block is no solver), and so
-      // does a level with a row that stores no diagonal entry (rank-local; the path reports the Gauss-Seidel value)
-      bool ilu_built = false;
-      if (G->ilu && !last) rc = amg_ilu_smoother(ctx, G, L, l, dense, derr.p, &ilu_built);
-      if (rc != ISPH_SUCCESS || ilu_built) continue;
-      if (dense) {
-        const int nb = (L->A.n + 63) / 64;
-        L->path[AMG_PATH_SMOOTHER] = 1;
-        // symmetric sweeps: always on a coarsest level the smoother solves, otherwise unless the cycle uses the one-directional sweeps
-        const bool need_sym = last || !G->gs_eff, need_dir = G->gs_eff && !last;
-        auto build = [&](DevBuf<double> &W, int mode) {
-          int r2 = W.reserve((size_t)nb * 4096);
-          if (r2 == ISPH_SUCCESS)
-            hipLaunchKernelGGL(k_sgs_dense_build, dim3(nb), dim3(64), 0, ctx->stream, L->A.n, (const rp_t *)L->A.rp.p,
-                               (const int *)L->A.ci.p, (const double *)L->A.v.p, W.p, mode);
-          return r2;
-        };
-        if (need_sym) rc = build(L->wsgs, 0);
-        if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wfwd, 1);
-        if (rc == ISPH_SUCCESS && need_dir) rc = build(L->wbwd, 2);
-      } else {
-        L->path[AMG_PATH_SMOOTHER] = 2;
-        rc = ilu_create(ctx, L->Am, l == 0 ? G->block : kAmgCoarseBlock, &L->sgs, /*sgs=*/true);
-      }
-    }
-  }
+  rc = amg_smoothers(ctx, G, dist, derr.p, rc);
   // cycle_bits 32: the float planes of P, P^T and A P (A_l's is the smoother's); rank-local, agreed on just below
   if (rc == ISPH_SUCCESS && G->cycle_bits == 32) rc = amg_float_planes(ctx, G);
   if (dist) {   // the smoothers are built per rank: a failure there must keep every rank out of the collective steps below
@@ -2316,24 +2613,226 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
     }
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == ISPH_SUCCESS) rc = fail("AMG setup failed", __FILE__, __LINE__);   // gs, gr leave scope
   } else if (rc == ISPH_SUCCESS && !G->coarse_smooth) {
-    AmgLevel *L = G->L.back();
-    const int nc = L->A.n;
-    G->nc = nc;
-    if (rc == ISPH_SUCCESS) rc = G->cinv.reserve((size_t)2 * nc * nc + (size_t)nc + 1);
-    if (rc == ISPH_SUCCESS && nc > 0) {
-      hipLaunchKernelGGL(k_dense_from_csr, dim3(nc), dim3(kBlock), 0, ctx->stream, nc, (const rp_t *)L->A.rp.p,
-                         (const int *)L->A.ci.p, (const double *)L->A.v.p, G->cinv.p);
-      rc = amg_dense_invert(ctx, G->cinv.p, nc, derr.p);
-      int herr = 0;
-      if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr.p, &herr);
-      if (rc == ISPH_SUCCESS && (herr & 4)) rc = fail("AMG: coarsest operator is singular (pass the null vector)", __FILE__, __LINE__);
-    }
+    rc = amg_coarse_inverse(ctx, G, derr.p);
   }
   if (rc == ISPH_SUCCESS && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess))
     rc = fail("AMG setup failed", __FILE__, __LINE__);
   tmp.release(); derr.release(); dg.release();
   if (rc != ISPH_SUCCESS) { amg_destroy(G); return rc; }
   *out = G;
+  return ISPH_SUCCESS;
+}
+
+// ---- isph_prec_refactor: the hierarchy of new matrix values on the kept aggregates -------------------------------------
+// ML's MultiLevelPreconditioner::ReComputePreconditioner: aggregates, number of levels, every pattern (P_l, R_l, A_l P_l,
+// A_{l+1}), the SELL images with their column windows, the smoothers' layouts and the path values stand; the diagonal and
+// rho (eig_type 1: the estimate) of every level, the tentative prolongator on the kept member lists, the damping and the
+// values of P_l, R_l, A_l P_l, A_{l+1} and of their images, the smoothers, the float planes and the dense coarse inverse
+// are redone from the values of Am.  The fine-level CSR copy is made again from the SELL image (no preparation outputs)
+// and released as amg_create releases it.  ISPH_AMG_REFRESH_TWO_PASS=1 (read here): the values of P_l come from the FILL
+// pass of the two-pass k_prolong and the products from the FILL pass of k_spgemm, each behind its COUNT pass -- a row
+// that counts more entries than its kept row holds is the refusal of the new kernels -- and a product row, which that
+// kernel leaves in table order, is matched column by column into the kept row (k_match_columns).
+// A refusal leaves G valid for amg_destroy or another amg_refactor (values of some levels may already be the new ones).
+__global__ void k_row_counts_fit(int n, const int *__restrict__ cnt, const rp_t *__restrict__ rp, int *__restrict__ err) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && cnt[i] > (int)(rp[i + 1] - rp[i])) { atomicOr(err, kAmgNoSlot); atomicMin(err + 1, i); }
+}
+// kept row <- the row of the same extent in (tci, tcv), whose first cnt[i] entries hold distinct columns in any order
+__global__ __launch_bounds__(256) void k_match_columns(int n, const rp_t *__restrict__ rp, const int *__restrict__ cci,
+                                                       const int *__restrict__ cnt, const int *__restrict__ tci,
+                                                       const double *__restrict__ tcv, double *__restrict__ cv, int *__restrict__ err) {
+  const int i = blockIdx.x * kAmgWaves + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  const rp_t b = rp[i];
+  const int len = (int)(rp[i + 1] - b), have = cnt[i];
+  int taken = 0;
+  for (int s = lane; s < len; s += 64) {
+    const int c = cci[b + s];
+    double a = 0.0;
+    for (int t = 0; t < have; ++t)
+      if (tci[b + t] == c) { a = tcv[b + t]; ++taken; }
+    cv[b + s] = a;
+  }
+  int d = (lane == 0 ? have : 0) - taken;
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  if (lane == 0 && d != 0) { atomicOr(err, kAmgNoSlot); atomicMin(err + 1, i); }
+}
+
+// err[0] / err[1] of the refresh kernels -> success, or the refusal that names the level and the row
+inline int amg_refresh_check(isph_ctx *ctx, int *derr, int level, const char *what) {
+  int h[2] = {0, 0};
+  ISPH_CHECK_HIP(hipMemcpyAsync(h, derr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  if (h[0] & kAmgNoSlot) {
+    char msg[240];
+    snprintf(msg, sizeof(msg), "refactor: level %d, row %d of %s has a term that finds no slot in the kept pattern (the matrix "
+                               "couples what the hierarchy was not built for): rebuild", level, h[1], what);
+    return fail(msg, __FILE__, __LINE__);
+  }
+  if (h[0] & 1) return fail("AMG: a row touches more than 512 aggregates", __FILE__, __LINE__);
+  if (h[0] & 2) return fail("AMG: coarse operator row too dense for the SpGEMM table", __FILE__, __LINE__);
+  return ISPH_SUCCESS;
+}
+
+// C.v = X * Y on the kept pattern of C (rows ascending)
+inline int amg_spgemm_values(isph_ctx *ctx, const DCsr &X, const DCsr &Y, DCsr &C, bool two_pass, int *derr, int level, const char *what) {
+  ISPH_CHECK(C.v.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
+  if (C.n <= 0) return ISPH_SUCCESS;
+  if (!two_pass) {
+    hipLaunchKernelGGL(k_spgemm_values, dim3(amg_wave_grid(C.n)), dim3(256), 0, ctx->stream, X.n, Y.n, (const rp_t *)X.rp.p,
+                       (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
+                       (const rp_t *)C.rp.p, (const int *)C.ci.p, C.v.p, derr);
+    return amg_refresh_check(ctx, derr, level, what);
+  }
+  DevTmp<int> cnt, tci;
+  DevTmp<double> tcv;
+  ISPH_CHECK(cnt.reserve((size_t)C.n + 1));
+  ISPH_CHECK(tci.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
+  ISPH_CHECK(tcv.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
+  ISPH_CHECK_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)C.n + 1), ctx->stream));
+  hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, false>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
+                     (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
+                     cnt.p, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
+  hipLaunchKernelGGL(k_row_counts_fit, dim3((C.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, C.n, (const int *)cnt.p,
+                     (const rp_t *)C.rp.p, derr);
+  ISPH_CHECK(amg_refresh_check(ctx, derr, level, what));   // the fill pass only writes rows that fit
+  hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, true>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
+                     (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
+                     (int *)nullptr, (const rp_t *)C.rp.p, tci.p, tcv.p, derr);
+  hipLaunchKernelGGL(k_match_columns, dim3(amg_wave_grid(C.n)), dim3(256), 0, ctx->stream, C.n, (const rp_t *)C.rp.p,
+                     (const int *)C.ci.p, (const int *)cnt.p, (const int *)tci.p, (const double *)tcv.p, C.v.p, derr);
+  return amg_refresh_check(ctx, derr, level, what);   // (synchronises: the temporaries leave scope)
+}
+
+// the values of a CSR with ascending rows into its SELL image (S.val reserved again and zeroed when it was given back)
+inline int amg_values_to_sell(isph_ctx *ctx, const DCsr &C, isph_mat *M) {
+  Sell &S = M->S;
+  if (!S.val.p) {
+    ISPH_CHECK(S.val.reserve((size_t)(S.stored > 0 ? S.stored : 1)));
+    ISPH_CHECK_HIP(hipMemsetAsync(S.val.p, 0, sizeof(double) * (size_t)S.stored, ctx->stream));
+  }
+  if (C.n > 0)
+    hipLaunchKernelGGL(k_csr_values_to_sell, dim3((C.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, C.n,
+                       (const rp_t *)C.rp.p, (const double *)C.v.p, (const long long *)S.slice_off.p, S.val.p);
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
+inline int amg_refactor(isph_ctx *ctx, isph_amg *G, const isph_mat *Am) {
+  ISPH_REQUIRE(G->held, "refactor of \"sa-amg\": the hierarchy was created while the pattern was not held (isph_ctx_hold_pattern was "
+                        "off, or the hierarchy spans several ranks): rebuild it");
+  ISPH_REQUIRE(!G->dist && !(comm_active(ctx) && ctx->nranks > 1) && !mat_has_halo(Am),
+               "refactor of \"sa-amg\": a matrix with a halo, or a context of more than one rank -- the neighbours' P rows "
+               "would have to travel again: rebuild");
+  AmgLevel *L0 = G->L[0];
+  if (Am->S.nrow != L0->A.n) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "refactor: the matrix has %d rows, the AMG hierarchy was built for %d", Am->S.nrow, L0->A.n);
+    return fail(msg, __FILE__, __LINE__);
+  }
+  const char *env = getenv("ISPH_AMG_REFRESH_TWO_PASS");
+  const bool two_pass = env && env[0] == '1';
+  DevTmp<char> tmp;
+  DevTmp<int> derr, cnt;
+  DevTmp<double> dg, pt;
+  DevTmp<unsigned long long> rho;
+  ISPH_CHECK(derr.reserve(2));
+  ISPH_CHECK(rho.reserve(1));
+  const int herr0[2] = {0, 0x7fffffff};
+  ISPH_CHECK_HIP(hipMemcpyAsync(derr.p, herr0, sizeof(herr0), hipMemcpyHostToDevice, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // (herr0 is read by the copy)
+  // on every way out: the fine-level CSR copy goes back to the pool as after the create call, and so do the values of A P
+  struct GiveBack {
+    isph_amg *G;
+    ~GiveBack() {
+      AmgLevel *F = G->L[0];
+      if (G->nlev > 1) { F->A.ci.release(); F->A.v.release(); F->A.rp.release(); }
+      for (AmgLevel *L : G->L) L->AP.v.release();
+    }
+  } give_back{G};
+  L0->Am = Am;
+  ISPH_CHECK(amg_csr_from_sell(ctx, Am->S, L0->A, tmp));
+  for (int l = 0; l + 1 < G->nlev; ++l) {
+    AmgLevel *L = G->L[(size_t)l], *Lc = G->L[(size_t)l + 1];
+    const DCsr &A = L->A;
+    DCsr &P = L->P, &R = L->R, &AP = L->AP;
+    const int n = A.n, nagg = P.m, gw = amg_wave_grid(n), gt = (n + kBlock - 1) / kBlock;
+    ISPH_CHECK(dg.reserve((size_t)(n > 0 ? n : 1)));
+    ISPH_CHECK(pt.reserve((size_t)(n > 0 ? n : 1)));
+    // the diagonal and rho (the arithmetic of k_amg_prepare), the estimate, the tentative prolongator on the kept members
+    ISPH_CHECK_HIP(hipMemsetAsync(rho.p, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_amg_diag, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                       (const double *)A.v.p, dg.p);
+    hipLaunchKernelGGL(k_amg_rho, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                       (const double *)A.v.p, (const double *)dg.p, rho.p);
+    if (G->eig_type == 1) ISPH_CHECK(amg_level_estimate(ctx, G, L, l, false));
+    hipLaunchKernelGGL(k_agg_norm, dim3(amg_wave_grid(nagg)), dim3(256), 0, ctx->stream, nagg, (const int *)L->mstart.p,
+                       (const unsigned long long *)L->mkeys.p, (const double *)L->nv.p, Lc->nv.p);
+    hipLaunchKernelGGL(k_ptent, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)L->agg.p, (const double *)L->nv.p,
+                       (const double *)Lc->nv.p, pt.p);
+    double rho_h = 0.0;
+    ISPH_CHECK_HIP(hipMemcpyAsync(&rho_h, rho.p, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    const double lambda = G->eig_type == 1 ? L->eig.lambda_used : 0.0;
+    const double damp = lambda > 0.0 ? G->omega / lambda : rho_h > 0.0 ? G->omega / rho_h : 0.0;
+    // P_l
+    if (two_pass) {
+      ISPH_CHECK(cnt.reserve((size_t)n + 1));
+      hipLaunchKernelGGL((k_prolong<0>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                         (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, cnt.p,
+                         (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr.p);
+      hipLaunchKernelGGL(k_row_counts_fit, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)cnt.p, (const rp_t *)P.rp.p, derr.p);
+      ISPH_CHECK(amg_refresh_check(ctx, derr.p, l, "P"));   // the fill pass only writes rows that fit
+      DevTmp<int> tci;
+      DevTmp<double> tcv;
+      ISPH_CHECK(tci.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+      ISPH_CHECK(tcv.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+      hipLaunchKernelGGL((k_prolong<1>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                         (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, (int *)nullptr,
+                         (const rp_t *)P.rp.p, tci.p, tcv.p, derr.p);
+      hipLaunchKernelGGL(k_match_columns, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)P.rp.p, (const int *)P.ci.p,
+                         (const int *)cnt.p, (const int *)tci.p, (const double *)tcv.p, P.v.p, derr.p);
+      ISPH_CHECK(amg_refresh_check(ctx, derr.p, l, "P"));   // (synchronises: the temporaries leave scope)
+    } else if (L->path[AMG_PATH_PROLONG] == 16) {
+      hipLaunchKernelGGL((k_prolong_values<16>), dim3((n + 15) / 16), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p,
+                         (const int *)A.ci.p, (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p,
+                         damp, (const rp_t *)P.rp.p, (const int *)P.ci.p, P.v.p, derr.p);
+    } else {
+      hipLaunchKernelGGL((k_prolong_values<64>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                         (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp,
+                         (const rp_t *)P.rp.p, (const int *)P.ci.p, P.v.p, derr.p);
+    }
+    ISPH_CHECK(amg_refresh_check(ctx, derr.p, l, "P"));
+    // R_l = P_l^T through the transposition map, then the two products on their kept patterns
+    if (R.nnz > 0)
+      hipLaunchKernelGGL(k_gather_values, dim3((unsigned)((R.nnz + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, R.nnz,
+                         (const unsigned *)L->tmap.p, (const double *)P.v.p, R.v.p);
+    ISPH_CHECK(amg_spgemm_values(ctx, A, P, AP, two_pass, derr.p, l, "A P"));
+    ISPH_CHECK(amg_spgemm_values(ctx, R, AP, Lc->A, two_pass, derr.p, l, "P^T A P"));
+    // the SELL images
+    ISPH_CHECK(amg_values_to_sell(ctx, P, L->Pm));
+    if (L->APm) ISPH_CHECK(amg_values_to_sell(ctx, AP, L->APm));
+    ISPH_CHECK(amg_values_to_sell(ctx, Lc->A, Lc->Aown));
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    AP.v.release();
+  }
+  if (G->nlev > 1) { L0->A.ci.release(); L0->A.v.release(); L0->A.rp.release(); }   // before the smoothers, as in amg_create
+  // the smoothers: polynomials and Gauss-Seidel streams are made again, a block ILU stream is refactored (amg_ilu_smoother)
+  for (int l = 0; l < G->nlev; ++l) {
+    AmgLevel *L = G->L[(size_t)l];
+    if (L->cheb) { cheb_destroy(L->cheb); L->cheb = nullptr; }
+    if (L->sgs && L->path[AMG_PATH_SMOOTHER] != 5) { ilu_destroy(L->sgs); L->sgs = nullptr; }
+  }
+  if (G->eig_type == 1) ISPH_CHECK(amg_level_estimate(ctx, G, G->L.back(), G->nlev - 1, false));
+  ISPH_CHECK_HIP(hipMemsetAsync(derr.p, 0, sizeof(int), ctx->stream));
+  ISPH_CHECK(amg_smoothers(ctx, G, false, derr.p, ISPH_SUCCESS));
+  if (G->cycle_bits == 32) ISPH_CHECK(amg_float_planes(ctx, G));
+  if (!G->coarse_smooth) ISPH_CHECK(amg_coarse_inverse(ctx, G, derr.p));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  ++G->refreshes;
   return ISPH_SUCCESS;
 }
 

@@ -51,6 +51,10 @@ struct Cheb {
   double lambda = 0.0, alpha = 0.0, beta = 0.0;
   double rho = 0.0;                                  // ||D^-1 A||_inf (all-reduced), whatever lambda came from
   int eig_type = 0, eig_steps = 0;                   // eig_type 1: lambda = min(Arnoldi estimate, rho) after eig_steps steps
+  // what cheb_setup was asked for (isph_prec_refactor asks for the same on the new values)
+  double ratio_in = 0.0, lambda_max_in = 0.0, lambda_min_in = 0.0;
+  int eig_type_in = 0, eig_iters_in = 10;
+  bool held = false;   // a stand-alone preconditioner created while isph_ctx_hold_pattern was on: isph_prec_refactor takes it
   double c1[kChebMaxDegree], c2[kChebMaxDegree];   // step k (0-based): w = c1[k] w + c2[k] D^-1 (b - A y)
   DevBuf<double> dinv, w, t, r;                      // 1 / a_ii; the increment; the second y of the ping-pong; unfused: b - A y
   DevBuf<float> val32;                               // value_bits 32: fl32 of S.val, position by position (padding 0)
@@ -516,6 +520,8 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
   Cheb *C = new Cheb();
   C->n = S.nrow;
   C->degree = degree;
+  C->ratio_in = ratio; C->lambda_max_in = lambda_max; C->lambda_min_in = lambda_min;
+  C->eig_type_in = eig_type; C->eig_iters_in = eig_iters;
   C->vec_bits = vec_bits == 32 ? 32 : 64;
   C->value_bits = (value_bits == 32 || C->vec_bits == 32) ? 32 : 64;
   const bool f32 = C->value_bits == 32, v32 = C->vec_bits == 32;

@@ -1372,9 +1372,11 @@ static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb
   ISPH_REQUIRE(prm->eig_iters >= 1 && prm->eig_iters <= kEigMaxIters, "Chebyshev: eig_iters must be in [1,50]");
   M->type = 6;
   M->cheb_A = A;
-  return cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
-                    /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb,
-                    prm->value_bits == 32 ? 32 : 64, prm->eig_type, prm->eig_iters, /*eig_level=*/0);
+  ISPH_CHECK(cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
+                        /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb,
+                        prm->value_bits == 32 ? 32 : 64, prm->eig_type, prm->eig_iters, /*eig_level=*/0));
+  M->cheb->held = ctx->pattern_hold;
+  return ISPH_SUCCESS;
 }
 
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **Mout) {
@@ -1506,14 +1508,47 @@ int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int blo
   return ISPH_SUCCESS;
 }
 
+// isph_prec_refactor of "sa-amg" and "chebyshev<d>": the row count is checked here, everything else by the type
+static int prec_refactor_rows(const isph_prec *M, const isph_mat *A) {
+  if (A->S.nrow == M->n) return ISPH_SUCCESS;
+  char msg[160];
+  snprintf(msg, sizeof(msg), "refactor: the matrix has %d rows, the preconditioner was built for %d", A->S.nrow, M->n);
+  return fail(msg, __FILE__, __LINE__);
+}
+
 int isph_prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
   ISPH_REQUIRE(ctx && M && A, "NULL argument");
+  if (M->type == 3 && M->amg) {   // the hierarchy of the new values on the kept aggregates (amg.hpp amg_refactor)
+    ISPH_CHECK(prec_refactor_rows(M, A));
+    ISPH_REQUIRE(M->order == A->order, "refactor: the matrix is not in the row numbering the AMG hierarchy was built in "
+                                       "(the aggregates are sets of its rows): rebuild");
+    ISPH_CHECK(amg_refactor(ctx, M->amg, A));
+    M->order = A->order;
+    return ISPH_SUCCESS;
+  }
+  if (M->type == 6 && M->cheb && M->cheb->held) {  // nothing of the pattern is kept: the set-up of the create call on the new values
+    ISPH_CHECK(prec_refactor_rows(M, A));
+    const Cheb *C0 = M->cheb;
+    Cheb *C1 = nullptr;
+    ISPH_CHECK(cheb_setup(ctx, A, C0->degree, C0->ratio_in, C0->lambda_max_in, C0->lambda_min_in, /*empty_ok=*/false,
+                          /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &C1, C0->value_bits,
+                          C0->eig_type_in, C0->eig_iters_in, /*eig_level=*/0));
+    cheb_destroy(M->cheb);
+    C1->held = true;
+    M->cheb = C1;
+    M->cheb_A = A;
+    M->order = A->order;
+    return ISPH_SUCCESS;
+  }
+  if (M->type == 6)
+    return fail("refactor of \"chebyshev<d>\": the polynomial was created while the pattern was not held (isph_ctx_hold_pattern "
+                "was off): rebuild it", __FILE__, __LINE__);
   if (M->type != 2 || !M->ilu) {
     static const char *const names[] = {"none", "jacobi", "bjacobi-ilu<k>", "sa-amg", "ilu<k> / additive Schwarz", "overlap ILU(k)",
                                         "chebyshev<d>"};
     char msg[200];
-    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to the block stream \"bjacobi-ilu<k>\" only, not to a preconditioner "
-                               "of type \"%s\": rebuild it", M->type >= 0 && M->type <= 6 ? names[M->type] : "?");
+    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to \"bjacobi-ilu<k>\", \"sa-amg\" and \"chebyshev<d>\", not to a "
+                               "preconditioner of type \"%s\": rebuild it", M->type >= 0 && M->type <= 6 ? names[M->type] : "?");
     return fail(msg, __FILE__, __LINE__);
   }
   // the subdomains of the library's own numbering come with the matrix: they must be the ones the factor was laid out for
@@ -1843,6 +1878,28 @@ int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *
   const AmgLevel *L = M->amg->L[(size_t)level];
   ISPH_CHECK_HIP(hipMemcpyAsync(agg, L->agg.p, sizeof(int) * (size_t)L->A.n, hipMemcpyDeviceToHost, ctx->stream));
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return ISPH_SUCCESS;
+}
+
+long long isph_prec_amg_refreshes(const isph_prec *M) { return (M && M->type == 3 && M->amg) ? M->amg->refreshes : 0; }
+
+int isph_prec_amg_set_nullvec(isph_ctx *ctx, isph_prec *M, const double *nullvec, int on_device) {
+  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && nullvec, "not an AMG preconditioner, or the null vector is NULL");
+  ISPH_REQUIRE(M->amg->singular, "isph_prec_amg_set_nullvec: the hierarchy was created without a null vector (its coarsest "
+                                 "level has a direct solve): rebuild it with one");
+  AmgLevel *L0 = M->amg->L[0];
+  const int n = M->n;
+  if (n <= 0) return ISPH_SUCCESS;
+  DevTmp<double> tn;
+  const double *dn = nullptr;
+  ISPH_CHECK(stage_in(ctx, nullvec, (size_t)n, on_device, tn, &dn));
+  if (M->order)   // the caller's null vector in the numbering of the hierarchy
+    hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1,
+                       (const int *)M->order->perm.p, dn, L0->nv.p);
+  else
+    ISPH_CHECK_HIP(hipMemcpyAsync(L0->nv.p, dn, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }
 

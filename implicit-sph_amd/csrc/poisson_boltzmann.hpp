@@ -318,6 +318,7 @@ void isph_pb_params_default(isph_pb_params *p) {
   p->linear.solver_type = 0;
   p->linear.tol = 1e-6;
   p->linear.max_iters = 80;
+  p->prec_refresh = 0;
 }
 
 int isph_assemble_poisson_boltzmann(isph_ctx *ctx, const isph_particles *P, int antisym, const double *eps, const double *psi0,
@@ -384,8 +385,18 @@ int isph_solve_poisson_boltzmann(isph_ctx *ctx, isph_mat *J, const isph_pb_param
     if (status != 2) break;
     rc = pb_jacobian_dev(ctx, J, &prm, R->psi.p);
     if (rc == ISPH_SUCCESS && (!M || age >= prm.prec_max_age)) {  // "Preconditioner Reuse Policy" = Reuse
-      if (M) { isph_prec_destroy(M); M = nullptr; }
-      rc = pb_build_prec(ctx, J, &prm, &M);
+      // prec_refresh: the preconditioner of the first step was created while the pattern was held; its values are redone
+      // where the type can be refactored (an SA-AMG across ranks or on a matrix with a halo is not held: rebuilt)
+      if (M && prm.prec_refresh && (M->type == 2 || (M->type == 3 && M->amg && M->amg->held))) {
+        rc = isph_prec_refactor(ctx, M, J);
+        ++info->prec_refreshes;
+      } else {
+        if (M) { isph_prec_destroy(M); M = nullptr; }
+        const bool hold0 = ctx->pattern_hold;
+        if (prm.prec_refresh) ctx->pattern_hold = true;
+        rc = pb_build_prec(ctx, J, &prm, &M);
+        ctx->pattern_hold = hold0;
+      }
       age = 0;
       ++info->prec_builds;
     }

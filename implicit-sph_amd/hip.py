@@ -25,7 +25,7 @@ EXPORTS = [
     "isph_ctx_set_profile", "isph_ctx_hold_neighbours", "isph_ctx_profile_read", "isph_ctx_set_ordering", "isph_ctx_set_periodic_box", "isph_mat_ordering_info", "isph_mat_ordering", "isph_mat_ordering_faces", "isph_ctx_halo_profile_read", "isph_ctx_comm_info", "isph_device_identity", "isph_assemble_poisson", "isph_assemble_helmholtz", "isph_assemble_solute_transport", "isph_assemble_applied_potential", "isph_compute_volumes", "isph_compute_pnd", "isph_compute_corrections", "isph_gradient", "isph_divergence", "isph_correct_velocity_pressure",
     "isph_advance_begin", "isph_advance_end", "isph_compute_shift", "isph_apply_shift", "isph_shift_particles",
     "isph_solve_block", "isph_assemble_block_helmholtz", "isph_amg_params_default", "isph_prec_create_amg", "isph_prec_amg_levels", "isph_prec_amg_info",
-    "isph_prec_amg_export", "isph_prec_amg_aggregates", "isph_prec_amg_path",
+    "isph_prec_amg_export", "isph_prec_amg_aggregates", "isph_prec_amg_path", "isph_prec_amg_refreshes", "isph_prec_amg_set_nullvec",
     "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
@@ -76,10 +76,11 @@ class PBParams(C.Structure):
     """Mirror of isph_pb_params: the Poisson-Boltzmann physics (kappa^2 = 2 ezcb / psiref, gamma, linearized) and the
     NOX list of SolverNOX_Stratimikos (solver_nox_impl.h:78-145, solver_nox_stratimikos.h:84-122).  Keyword arguments
     override the defaults of isph_pb_params_default; `amg` / `linear` may be given as AmgParams / SolverParams or as a
-    dict of fields to change."""
+    dict of fields to change.  prec_refresh = 1: at prec_max_age the preconditioner is refreshed on the new Jacobian
+    (isph_prec_refactor) instead of being destroyed and built again; PBInfo.prec_refreshes counts those."""
     _fields_ = [("kappasq", C.c_double), ("gamma", C.c_double), ("linearized", C.c_int), ("max_iters", C.c_int),
                 ("f_tol", C.c_double), ("update_tol", C.c_double), ("prec_max_age", C.c_int), ("prec_kind", C.c_int),
-                ("amg", AmgParams), ("linear", SolverParams)]
+                ("amg", AmgParams), ("linear", SolverParams), ("prec_refresh", C.c_int)]
 
     def __init__(self, **kw):
         super().__init__()
@@ -96,7 +97,7 @@ class PBParams(C.Structure):
 class PBInfo(C.Structure):
     """isph_pb_info: status 1 converged, 0 MaxIters, -1 non-finite ||F||"""
     _fields_ = [("status", C.c_int), ("newton_iters", C.c_int), ("linear_iters", C.c_int), ("prec_builds", C.c_int),
-                ("norm_f", C.c_double), ("norm_update", C.c_double), ("ms", C.c_double)]
+                ("norm_f", C.c_double), ("norm_update", C.c_double), ("ms", C.c_double), ("prec_refreshes", C.c_int)]
 
 
 class SolveInfo(C.Structure):
@@ -253,6 +254,9 @@ def lib():
         L.isph_prec_amg_export.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_amg_aggregates.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.isph_prec_amg_path.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_prec_amg_refreshes.argtypes = [C.c_void_p]
+        L.isph_prec_amg_refreshes.restype = C.c_longlong
+        L.isph_prec_amg_set_nullvec.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_compute_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int]
         L.isph_apply_shift.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_int]
@@ -821,9 +825,15 @@ class Precond:
         return int(lib().isph_prec_multi_path(self.ctx.h, self.h, int(nvec)))
 
     def refactor(self, A):
-        """isph_prec_refactor: the numeric factorisation of a "bjacobi-ilu<k>" again on the (updated) values of A; pattern,
-        schedule and layout are kept, the result is bit for bit a fresh create"""
+        """isph_prec_refactor on the (updated) values of A.  "bjacobi-ilu<k>": the numeric factorisation again; pattern,
+        schedule and layout are kept, the result is bit for bit a fresh create.  "chebyshev<d>" created under
+        Context.hold_pattern(True): diagonal, rho or estimate and float plane again, bit for bit a fresh create.  "sa-amg" created under Context.hold_pattern(True), one rank: the
+        hierarchy of the new values on the kept aggregates and patterns (a fresh create to round-off where it aggregates the
+        same); a term without a slot in a kept pattern, another row count, a halo or a hierarchy created with the mode off
+        are refused by name.  The preconditioner applies A from then on: it is kept alive here where the create call did."""
         _check(lib().isph_prec_refactor(self.ctx.h, self.h, A.h))
+        if getattr(self, "A", None) is not None:
+            self.A = A
 
     @property
     def value_bits(self):
@@ -1033,6 +1043,17 @@ class PrecondAMG(Precond):
         a = np.zeros(self.level_info(l)["rows"], dtype=np.int32)
         _check(lib().isph_prec_amg_aggregates(self.ctx.h, self.h, l, _ptr(a)))
         return a
+
+    def set_nullvec(self, nullvec):
+        """isph_prec_amg_set_nullvec: new values for the null vector given at create, read by the next refactor()"""
+        nv = _f64(nullvec)
+        _need(nv, self.n, "nullvec [n]")
+        _check(lib().isph_prec_amg_set_nullvec(self.ctx.h, self.h, _ptr(nv), int(_is_torch(nv))))
+
+    @property
+    def refreshes(self):
+        """isph_prec_amg_refreshes: the refactor() calls this hierarchy has gone through"""
+        return int(lib().isph_prec_amg_refreshes(self.h))
 
     PATH_KEYS = ("mis_rounds", "mis_list_rounds", "prolong", "ap", "galerkin", "smoother", "coarse", "prep")
 

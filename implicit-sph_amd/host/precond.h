@@ -43,16 +43,19 @@ class PrecondWrapper {
   void adoptDevice(isph_prec *M) { destroyDevice(); _M = M; _block_ilu = M != nullptr; _kept_sig = deviceSignature(); }
   // While SolverLin_HIP holds the pattern (holdPattern(true)), free() KEEPS the device object of a block-stream ILU: the next
   // createOnDevice on the updated matrix refactors it (isph_prec_refactor: Ifpack's Compute() without Initialize()) when
-  // the wrapper's parameters are the ones it was built with.  Every other device object is released as always.
+  // the wrapper's parameters are the ones it was built with.  So it does for a wrapper that marks its object _refreshable:
+  // the Chebyshev polynomial of PrecondWrapper_Ifpack, and the hierarchy of PrecondWrapper_ML when "isph: amg refresh" asks
+  // for ML's ReComputePreconditioner.  Every other device object is released as always.
   std::shared_ptr<PatternHold> _hold;
   bool _block_ilu = false;   // _M is a "bjacobi-ilu<k>" (the three block-Jacobi routes of PrecondWrapper_Ifpack, or adopted)
+  bool _refreshable = false; // _M is a "chebyshev<d>" or an "sa-amg" whose wrapper wants it refreshed by isph_prec_refactor
   bool _kept = false;        // _M was kept by free(): stale until refactored
   bool _warned_refactor = false;
   std::string _kept_sig;     // the parameters _M was built with
   virtual std::string deviceSignature() { return std::string(); }
   void destroyDevice() {
     if (_M) { isph_prec_destroy(_M); _M = nullptr; }
-    _block_ilu = false; _kept = false;
+    _block_ilu = false; _refreshable = false; _kept = false;
   }
   // true: the kept object now holds the factorisation of A; false: nothing kept (or it did not fit and was released)
   bool refactorKept(isph_ctx *ctx, const isph_mat *A) {
@@ -112,7 +115,7 @@ class PrecondWrapper {
   virtual void create() { return; }
   virtual void create(const int) { return; }
   virtual void free() {
-    if (_M && _block_ilu && _hold && _hold->on) { _kept = true; return; }   // holdPattern: kept for isph_prec_refactor
+    if (_M && (_block_ilu || _refreshable) && _hold && _hold->on) { _kept = true; return; }   // holdPattern: kept for isph_prec_refactor
     destroyDevice();
   }
   virtual Epetra_Operator *getPrecondOperator() { return NULL; }

@@ -157,8 +157,14 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
                     cp.value_bits);
         _warned = true;
       }
+      // holdPattern: the polynomial kept by free() is set up again on the updated matrix (nothing of a pattern is kept:
+      // bit for bit the fresh create)
+      if (refactorKept(ctx, A)) return ISPH_SUCCESS;
       destroyDevice();
-      return isph_prec_create_chebyshev(ctx, A, &cp, &_M);
+      _kept_sig = deviceSignature();
+      const int rc = isph_prec_create_chebyshev(ctx, A, &cp, &_M);
+      _refreshable = rc == ISPH_SUCCESS;
+      return rc;
     }
     if (type != "ILU") {
       std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): Precond Type '%s' is not available; available: \"ILU\", \"Chebyshev\"\n",
@@ -279,6 +285,15 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
                   _param->get("isph: ilu value bits", 64), _param->get("Overlap Level", 1), _cx != nullptr ? _cdim : 0);
     sig += buf;
     for (int v : _bptr) { std::snprintf(buf, sizeof(buf), "%d,", v); sig += buf; }
+    if (sig.compare(0, 9, "Chebyshev") == 0) {
+      char cb[200];
+      std::snprintf(cb, sizeof(cb), "|%d|%.17g|%.17g|%.17g|%d|%d|", _param->get("chebyshev: degree", 1),
+                    _param->get("chebyshev: ratio eigenvalue", 30.0), _param->get("chebyshev: max eigenvalue", 0.0),
+                    _param->get("chebyshev: min eigenvalue", 0.0), _param->get("isph: chebyshev value bits", 64),
+                    _param->get("isph: chebyshev eigen-analysis iterations", 10));
+      sig += cb;
+      sig += _param->get("isph: chebyshev eigen-analysis", "Anorm");
+    }
     return sig;
   }
   bool _warned = false, _warned_table = false;

@@ -30,6 +30,10 @@ class PrecondWrapper_ML : public PrecondWrapper {
       _param->set("aggregation: threshold", 0.0);
       // device-side extension: rows the Gauss-Seidel sweeps are local to (ML: the processor).  Not a reference key.
       _param->set("isph: block rows", 512);
+      // device-side extension (not a reference key), read under SolverLin_HIP::holdPattern only: true = the hierarchy of
+      // the first held solve is kept and REFRESHED on the values of the following ones (isph_prec_refactor: ML's
+      // ReComputePreconditioner -- aggregates and patterns stand, every number is redone); false = rebuilt per solve
+      _param->set("isph: amg refresh", false);
     } else if (_param.get() != param) {
       _param = Teuchos::rcp(param, false);
     }
@@ -124,8 +128,32 @@ class PrecondWrapper_ML : public PrecondWrapper {
     prm.theta = _param->get("aggregation: threshold", 0.0);
     prm.sweeps = _param->get("smoother: sweeps", 1);
     prm.block = _param->get("isph: block rows", 512);
-    free();
-    return isph_prec_create_amg(ctx, A, &prm, _null, /*on_device=*/0, &_M);
+    // holdPattern with "isph: amg refresh": the hierarchy kept by free() takes the null vector of this solve and the new
+    // values of the updated matrix and is done; any changed parameter (deviceSignature) means a fresh build
+    if (_kept && _M && _null != nullptr && _kept_sig == deviceSignature()) (void)isph_prec_amg_set_nullvec(ctx, _M, _null, 0);
+    if (refactorKept(ctx, A)) return ISPH_SUCCESS;
+    destroyDevice();
+    _kept_sig = deviceSignature();
+    const int rc = isph_prec_create_amg(ctx, A, &prm, _null, /*on_device=*/0, &_M);
+    _refreshable = rc == ISPH_SUCCESS && _param->get("isph: amg refresh", false);
+    return rc;
+  }
+  // what a kept hierarchy was built with
+  virtual std::string deviceSignature() {
+    setParameters(_param.get());
+    const Teuchos::ParameterList &ilist = *_param;
+    std::string sig = _param->get("aggregation: type", "Uncoupled") + "|" + _param->get("smoother: type", "symmetric Gauss-Seidel") +
+                      "|" + _param->get("eigen-analysis: type", "Anorm") + "|" + _param->get("smoother: ifpack type", "ILU");
+    char buf[256];
+    std::snprintf(buf, sizeof(buf), "|%d|%d|%d|%d|%d|%d|%d|%d|%d|%.17g|%.17g|%.17g|%d|%d|%d|",
+                  (int)_param->get("smoother: Gauss-Seidel efficient symmetric", false), _param->get("smoother: sweeps", 1),
+                  _param->get("isph: chebyshev value bits", 64), _param->get("isph: amg cycle bits", 64),
+                  _param->get("eigen-analysis: iterations", 10), _param->get("max levels", 5), _param->get("coarse: max size", 128),
+                  _param->get("isph: block rows", 512), ilist.sublist("smoother: ifpack list").get("fact: level-of-fill", 0),
+                  _param->get("aggregation: damping factor", 4.0 / 3.0), _param->get("aggregation: threshold", 0.0),
+                  _param->get("smoother: Chebyshev alpha", 20.0), (int)_param->get("isph: amg refresh", false), _null != nullptr ? 1 : 0,
+                  _cx != nullptr ? _cdim : 0);
+    return sig + buf;
   }
   double *_null = nullptr;
 };

@@ -162,8 +162,9 @@ int isph_ctx_hold_pattern(isph_ctx *ctx, int on);
  * offsets are untouched.  Host values travel through the pinned ring and the staging threads of the ingress in its chunks,
  * one copy per chunk, 8 B per entry on the link, with the scatter of a chunk queued behind its copy; device values take
  * one scatter launch.  isph_ingress_info then reports this call ([6] = 8 nnz).  Fails WITHOUT touching A when A has no
- * map or val is NULL.  Preconditioners built from A before the call are stale: those that apply A itself (Chebyshev, AMG)
- * and the float plane of a value_bits = 32 Chebyshev must be rebuilt by the caller; a block ILU can be refactored.
+ * map or val is NULL.  Preconditioners built from A before the call are stale: a block ILU, a Chebyshev polynomial (its
+ * float plane included) and an SA-AMG hierarchy created while the mode was on can be refreshed by isph_prec_refactor; every
+ * other one must be rebuilt by the caller.
  * Replaces Epetra_CrsMatrix::ReplaceMyValues on a FillComplete'd matrix. */
 int isph_mat_update_values(isph_ctx *ctx, isph_mat *A, const double *val /*[h|d]*/, int on_device);
 /* [0] 1 when A carries a map  [1] bytes of the map  [2] value updates A has taken */
@@ -297,7 +298,45 @@ int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params
  * in-block columns are not exactly the level-0 columns of its factor row (the message names the first such row), another
  * row count or subdomain table -- M is then valid only for isph_prec_destroy or another isph_prec_refactor; every other
  * preconditioner type (the message names it); an ILU(k > 0) created while isph_ctx_hold_pattern was off (its fill levels
- * were not kept).  A zero pivot shows exactly as after the create call. */
+ * were not kept).  A zero pivot shows exactly as after the create call.
+ *
+ * "chebyshev<d>" (isph_prec_create_chebyshev or isph_prec_create; both value_bits, both eig_type) CREATED WHILE
+ * isph_ctx_hold_pattern WAS ON.  Nothing of the pattern is kept: the diagonal, rho or the estimate, the scalars and the
+ * float plane are made again by the set-up of the create call with the parameters of the create call, so the application
+ * is bit for bit that of a fresh create on A.  M applies A from then on (the caller keeps it alive).  REFUSED: another row
+ * count; a polynomial created with the mode off (as before this type could be refactored: the mode is the caller's
+ * statement that its preconditioners are meant to follow the matrix), M then untouched and usable.
+ *
+ * "sa-amg" (isph_prec_create_amg or isph_prec_create; every smoother, cheb_value_bits, cycle_bits, eig_type, threshold,
+ * with or without a null vector), on one rank, for a hierarchy CREATED WHILE isph_ctx_hold_pattern WAS ON -- ML's
+ * MultiLevelPreconditioner::ReComputePreconditioner.
+ *   KEPT: the aggregates of every level and the number of levels; the patterns of P_l, R_l = P_l^T, A_l P_l and A_{l+1};
+ *   the transposition order; the SELL images of P_l, A_l P_l and A_{l+1} with their column windows; the layouts of the
+ *   smoothers; the values of isph_prec_amg_path.
+ *   REDONE on the values of A: the diagonal and rho of every level (eig_type 1: each level's estimate); the tentative
+ *   prolongator on the kept member lists of the aggregates; the damping and the values of P_l, R_l, A_l P_l and A_{l+1}
+ *   and of their SELL images; the smoothers (Chebyshev: the set-up again; dense 64-row blocks: built again; the ILU(k)
+ *   streams of smoother 4: refactored in place as above; the Gauss-Seidel stream of the fine level: created again -- a
+ *   value-only refill of it does not exist yet); the float planes of cheb_value_bits / cycle_bits = 32; the dense coarse
+ *   inverse (a singular one is refused as in create).  The fine level points at A from then on: the caller keeps A alive.
+ *   WHAT IT IS: the hierarchy of the new values ON THE KEPT AGGREGATES (ML's reuse semantics).  The second pass of the
+ *   aggregation joins a leftover row to its most strongly coupled neighbour, so a fresh create on the new values may
+ *   aggregate differently; where it aggregates the same, the refresh equals the fresh create to round-off (not to the
+ *   bit: the sums run in another order).  Scaling the off-diagonal entries by one factor keeps their order and the diagonal
+ *   never enters that pass: Newton Jacobians that change on the diagonal and the Helmholtz theta dt variants are such cases.
+ *   A matrix whose pattern differs but whose terms all find a slot in the kept patterns gives a valid hierarchy of the kept
+ *   aggregates (slots no term reaches hold 0).  Two refreshes from the same values give the same bits: every slot is
+ *   summed in an order fixed by the data, without floating-point atomics (the create call does not promise this).
+ *   The null vector of the create call stays; isph_prec_amg_set_nullvec replaces its values before a refactor.
+ *   REFUSED, by name, M then valid only for isph_prec_destroy or another isph_prec_refactor: a hierarchy "created while
+ *   the pattern was not held"; another row count or row numbering; a matrix with a halo or a context of more than one
+ *   rank ("the neighbours' P rows would have to travel again: rebuild"); a term of P_l, A_l P_l or P_l^T A_l P_l that
+ *   finds no slot in the kept pattern (the message names the level and the first such row).
+ *   What the hold mode keeps per level on top of a plain create: the member list of the aggregates (8 B per row), the
+ *   pattern of A_l P_l (8 B per row + 4 B per entry), the transposition map (4 B per entry of P_l) and the CSR of every
+ *   coarse operator in the row order of its SELL image.  With the mode off the create call is what it was, launch for launch.
+ *   ISPH_AMG_REFRESH_TWO_PASS=1 (read by the call): the values come from the count + fill passes of the two-pass kernels of
+ *   the create call instead of the refresh kernels -- their cross-check and the baseline of their timing. */
 int isph_prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A);
 /* Ifpack_AdditiveSchwarz<Ifpack_ILU> with the parameters PrecondWrapper_Ifpack sets (ref: precond_ifpack.h:30-45,
  * 60-74): "fact: level-of-fill" (default 1), "Overlap Level" (default 1), "schwarz: combine mode" (default "Add" = 0;
@@ -907,6 +946,12 @@ int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *
  * rank while out[3] and out[4] name the kernels of its products; out[0], out[1] and out[7] describe the aggregation it
  * tried. */
 int isph_prec_amg_path(isph_ctx *ctx, const isph_prec *M, int level, long long out[8]);
+/* isph_prec_refactor calls this hierarchy has gone through (0 for any other preconditioner) */
+long long isph_prec_amg_refreshes(const isph_prec *M);
+/* New values for the null vector of a hierarchy that was created with one (n doubles, the caller's row numbering), read by
+ * the next isph_prec_refactor: PrecondWrapper_ML::setNullVector before a ReComputePreconditioner.  The cycle is not
+ * touched by this call alone.  REFUSED for a hierarchy created without a null vector. */
+int isph_prec_amg_set_nullvec(isph_ctx *ctx, isph_prec *M, const double *nullvec /*[h|d]*/, int on_device);
 
 /* ---- nonlinear Poisson-Boltzmann: PairISPH::computePoissonBoltzmann (ref: pair_isph.cpp:573-600, every step when
  * enabled, :1312-1313) and the NOX solve it drives through SolverNOX_Stratimikos (pair_isph.h:78).
@@ -936,12 +981,18 @@ typedef struct {
   int prec_kind;            /* 0 SA-AMG (ML in the reference's list), 1 block-Jacobi ILU(0)                 */
   isph_amg_params amg;      /* isph_amg_params_default                                                      */
   isph_solver_params linear;/* Block GMRES (flexible, right preconditioning), tol 1e-6, 80 iterations       */
+  int prec_refresh;         /* 0 (default): at prec_max_age the preconditioner is destroyed and built again.  1: it is
+                             * created while the pattern is held (as under isph_ctx_hold_pattern; the context's own
+                             * setting is put back) and REFRESHED by isph_prec_refactor at prec_max_age -- J changes on
+                             * its diagonal only, so the SA-AMG keeps the aggregates a fresh create would find -- where
+                             * the type can be refactored (the ILU(0) blocks; the SA-AMG on one rank), rebuilt otherwise */
 } isph_pb_params;
 void isph_pb_params_default(isph_pb_params *p);
 typedef struct {
   int status;               /* 1 converged, 0 MaxIters, -1 non-finite ||F|| (NOX FiniteValue)               */
-  int newton_iters, linear_iters, prec_builds;
+  int newton_iters, linear_iters, prec_builds;   /* prec_builds counts a rebuild and a refresh alike */
   double norm_f, norm_update, ms;
+  int prec_refreshes;       /* how many of prec_builds were refreshes (prec_refresh = 1)                     */
 } isph_pb_info;
 /* The Laplacian part of J, Laplacian(-1, eps) (FunctorOuterPoissonBoltzmannJacobian::enterFor, :47-68), -1 unit rows on
  * Solid / Boundary particles; psi0 [nall] the Dirichlet values (NULL: 0), eps [nall] the dielectric coefficient (NULL:
