@@ -1716,6 +1716,15 @@ int isph_prec_schwarz_info(const isph_prec *M, long long info[7]) {
   return ISPH_SUCCESS;
 }
 
+int isph_prec_schwarz_paths(const isph_prec *M, long long out[12]) {
+  ISPH_REQUIRE(M && M->type == 4 && M->schwarz && out, "not a Schwarz preconditioner");
+  const isph_schwarz *S = M->schwarz;
+  out[0] = S->path_devlocal; out[1] = S->path_symbolic1_dev; out[2] = S->long_rows; out[3] = S->factor_waves; out[4] = S->factor_hbits;
+  out[5] = S->nrun_l; out[6] = S->nrun_u; out[7] = S->runs_near[0]; out[8] = S->runs_near[1]; out[9] = S->sub_maxrows;
+  out[10] = S->n4l; out[11] = S->n4u;
+  return ISPH_SUCCESS;
+}
+
 int isph_prec_schwarz_timing(const isph_prec *M, double ms[6]) {
   ISPH_REQUIRE(M && M->type == 4 && M->schwarz && ms, "not a Schwarz preconditioner");
   for (int k = 0; k < 6; ++k) ms[k] = M->schwarz->t_ms[k];

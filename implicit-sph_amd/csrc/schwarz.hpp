@@ -62,6 +62,10 @@ struct isph_schwarz {
   int n4l = 0, n4u = 0;
   bool long_rows = false;   // many rows have more entries on one side of the diagonal than a chunk of the sweeps holds
   bool syncfree = true;
+  // which way create() went (isph_prec_schwarz_paths): row lists built on the device, level-1 pattern built on the device,
+  // waves per row of the persistent factorisation (0: that launch did not run) and the bits of its look-up table (0: binary search)
+  bool path_devlocal = false, path_symbolic1_dev = false;
+  int factor_waves = 0, factor_hbits = 0;
   // many small subdomains (k_gilu_solve_sub): ONE launch per application, one workgroup per subdomain with its part of
   // the vector in LDS and a barrier per dependency level.  Per subdomain ONE list of levels -- the L levels with work
   // (1 ..), then the U levels (0 ..) -- with a 16-byte descriptor per row in that order (sub_desc: first entry on the
@@ -1713,6 +1717,7 @@ inline int schwarz_create(isph_ctx *ctx, const isph_mat *A, int fill, int block_
       resident = true;           // the factor arrays are where they belong: nothing to upload
     }
   }
+  S->path_devlocal = devlocal; S->path_symbolic1_dev = resident1;
   if (resident1 || devlocal) {
     // done above
   } else if (fill == 0) {
@@ -2095,6 +2100,7 @@ inline int schwarz_create(isph_ctx *ctx, const isph_mat *A, int fill, int block_
     // threads per row: one per entry of an average pivot row's upper part, up to 256 (512 measured no better on ILU(2))
     const long long upper = nloc > 0 ? (S->nnz - nloc) / 2 / nloc : 0;
     const int fw = upper > 64 ? 4 : 1;
+    S->factor_waves = fw; S->factor_hbits = hbits;
     const void *fk = fw == 4 ? reinterpret_cast<const void *>(k_gilu_factor_sf<4>) : reinterpret_cast<const void *>(k_gilu_factor_sf<1>);
     if (e == hipSuccess) e = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e == hipSuccess) {

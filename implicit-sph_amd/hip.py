@@ -26,7 +26,7 @@ EXPORTS = [
     "isph_advance_begin", "isph_advance_end", "isph_compute_shift", "isph_apply_shift", "isph_shift_particles",
     "isph_solve_block", "isph_assemble_block_helmholtz", "isph_amg_params_default", "isph_prec_create_amg", "isph_prec_amg_levels", "isph_prec_amg_info",
     "isph_prec_amg_export", "isph_prec_amg_aggregates", "isph_prec_amg_path", "isph_prec_amg_refreshes", "isph_prec_amg_set_nullvec",
-    "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
+    "isph_schwarz_params_default", "isph_prec_create_schwarz", "isph_prec_schwarz_info", "isph_prec_schwarz_paths", "isph_prec_schwarz_timing", "isph_prec_schwarz_export",
     "isph_pb_params_default", "isph_assemble_poisson_boltzmann", "isph_pb_residual", "isph_pb_jacobian", "isph_solve_poisson_boltzmann",
     "isph_compute_normals", "isph_csf_params_default", "isph_csf_phase_normal", "isph_csf_force", "isph_surface_tension_csf", "isph_pairwise_force",
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
@@ -235,6 +235,7 @@ def lib():
                                        C.c_void_p, C.c_void_p, C.c_int]
         L.isph_prec_create_schwarz.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_schwarz_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_prec_schwarz_paths.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_prec_schwarz_export.argtypes = [C.c_void_p] * 7
         L.isph_prec_schwarz_timing.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_amg_params_default.argtypes = [C.c_void_p]
@@ -926,6 +927,13 @@ class PrecondSchwarz(Precond):
         a = (C.c_longlong * 7)()
         _check(lib().isph_prec_schwarz_info(self.h, a))
         return dict(nloc=a[0], nnz=a[1], nsub=a[2], levels_l=a[3], levels_u=a[4], maxrow=a[5], persistent=a[6])
+
+    def paths(self):
+        """which way the create call went (isph_prec_schwarz_paths)."""
+        a = (C.c_longlong * 12)()
+        _check(lib().isph_prec_schwarz_paths(self.h, a))
+        return dict(rows_on_device=a[0], symbolic1_on_device=a[1], long_rows=a[2], factor_waves=a[3], hbits=a[4], nrun_l=a[5],
+                    nrun_u=a[6], runs_near_l=a[7], runs_near_u=a[8], sub_maxrows=a[9], n4l=a[10], n4u=a[11])
 
     def create_timing(self):
         """ms of the create call by stage (isph_prec_schwarz_timing)."""

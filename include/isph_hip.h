@@ -361,6 +361,13 @@ typedef struct {
 void isph_schwarz_params_default(isph_schwarz_params *p);
 int isph_prec_create_schwarz(isph_ctx *ctx, const isph_mat *A, const isph_schwarz_params *prm, isph_prec **M);
 int isph_prec_schwarz_info(const isph_prec *M, long long info[7]);
+/* which way the create call went, for tests that must know the branch a matrix reaches: [0] 1 = subdomain row lists and
+ * local matrices built on the device, 0 = on the host [1] 1 = level-1 pattern built on the device, 0 = on the host (or
+ * level of fill != 1) [2] 1 = the persistent sweeps split the recent words off the chunk loop (many rows beyond one chunk
+ * of 96 entries on a side) [3] waves per row of the persistent factorisation, 0 = that launch did not run [4] bits of its
+ * column look-up table, 0 = binary search [5] [6] runs of the persistent L / U sweep [7] [8] their throttle windows
+ * [9] rows of the largest extended subdomain [10] [11] positions of the padded L / U level order */
+int isph_prec_schwarz_paths(const isph_prec *M, long long out[12]);
 /* wall time of the create call, ms: [0] matrix to the host [1] subdomains + local matrices [2] level-of-fill pattern
  * [3] dependency levels, orders, combine lists [4] upload [5] numeric factorisation */
 int isph_prec_schwarz_timing(const isph_prec *M, double ms[6]);
