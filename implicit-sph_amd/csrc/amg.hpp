@@ -26,7 +26,14 @@
 // ran while isph_ctx_hold_pattern was on -- ML's ReComputePreconditioner (k_prolong_values, k_spgemm_values).
 // Set-up kernels work on device CSR copies, one wave per row (rows hold ~100 entries on the fine level); the
 // cycle itself uses the SELL SpMV and the chunk-stream triangular solves of the rest of the library.
+// The host side of the set-up reads from amg_create down: amg_new (parameters), amg_fine_level, one amg_coarsen_step per
+// level (amg_aggregate, amg_prolongator, amg_extend_prolongator across ranks, amg_level_operators), amg_smoothers and the
+// coarse inverse (amg_coarse_inverse / amg_coarse_inverse_dist).  On more than one rank the ranks agree on every decision and
+// fail together through comm_consensus / comm_rank_offsets (comm.hpp): only the functions that hold such a call carry a
+// return code past a failure; the rank-local ones return at the first and their DevTmp buffers go back with the scope.
 #pragma once
+#include <memory>
+
 #include <rocprim/rocprim.hpp>
 
 #include "chebyshev.hpp"
@@ -1534,20 +1541,17 @@ inline int amg_csr_from_sell(isph_ctx *ctx, const Sell &S, DCsr &A, DevBuf<char>
   ISPH_CHECK(len1.reserve((size_t)S.nrow + 1));
   ISPH_CHECK_HIP(hipMemcpyAsync(len1.p, S.rowlen.p, sizeof(int) * (size_t)S.nrow, hipMemcpyDeviceToDevice, ctx->stream));
   ISPH_CHECK_HIP(hipMemsetAsync(len1.p + S.nrow, 0, sizeof(int), ctx->stream));
-  int rc = amg_scan(ctx, len1.p, A.rp.p, S.nrow + 1, tmp);
-  if (rc == ISPH_SUCCESS && S.nrow > 0) {
-    if (dg && sc && key && rho) {
-      if (hipMemsetAsync(rho, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-      hipLaunchKernelGGL((k_sell_to_csr_i32<true>), dim3((S.nslices + 3) / 4), dim3(256), 0, ctx->stream, S.nrow,
-                         S.rowlen.p, S.slice_off.p, S.col.p, S.val.p, (const rp_t *)A.rp.p, A.ci.p, A.v.p, dg, sc, key, rho);
-    } else {
-      hipLaunchKernelGGL((k_sell_to_csr_i32<false>), dim3((S.nslices + 3) / 4), dim3(256), 0, ctx->stream, S.nrow,
-                         S.rowlen.p, S.slice_off.p, S.col.p, S.val.p, (const rp_t *)A.rp.p, A.ci.p, A.v.p);
-    }
+  ISPH_CHECK(amg_scan(ctx, len1.p, A.rp.p, S.nrow + 1, tmp));
+  if (S.nrow > 0 && dg && sc && key && rho) {
+    ISPH_CHECK_HIP(hipMemsetAsync(rho, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL((k_sell_to_csr_i32<true>), dim3((S.nslices + 3) / 4), dim3(256), 0, ctx->stream, S.nrow,
+                       S.rowlen.p, S.slice_off.p, S.col.p, S.val.p, (const rp_t *)A.rp.p, A.ci.p, A.v.p, dg, sc, key, rho);
+  } else if (S.nrow > 0) {
+    hipLaunchKernelGGL((k_sell_to_csr_i32<false>), dim3((S.nslices + 3) / 4), dim3(256), 0, ctx->stream, S.nrow,
+                       S.rowlen.p, S.slice_off.p, S.col.p, S.val.p, (const rp_t *)A.rp.p, A.ci.p, A.v.p);
   }
-  if (rc == ISPH_SUCCESS && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail("SELL->CSR failed", __FILE__, __LINE__);
-  len1.release();
-  return rc;
+  ISPH_REQUIRE(hipStreamSynchronize(ctx->stream) == hipSuccess, "SELL->CSR failed");
+  return ISPH_SUCCESS;
 }
 
 // R = P^T through a stable radix sort of (column, row) keys
@@ -1558,9 +1562,9 @@ inline int amg_transpose(isph_ctx *ctx, const DCsr &P, DCsr &R, DevBuf<char> &tm
   ISPH_CHECK(R.ci.reserve(nnz1));
   ISPH_CHECK(R.v.reserve(nnz1));
   DevTmp<unsigned long long> k0, k1;
-  int rc = k0.reserve(nnz1);
-  if (rc == ISPH_SUCCESS) rc = k1.reserve(nnz1);
-  if (rc == ISPH_SUCCESS && P.nnz > 0) {
+  ISPH_CHECK(k0.reserve(nnz1));
+  ISPH_CHECK(k1.reserve(nnz1));
+  if (P.nnz > 0) {
     const int gn = (int)((P.nnz + kBlock - 1) / kBlock);
     hipLaunchKernelGGL(k_transpose_keys, dim3((P.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, P.n,
                        (const rp_t *)P.rp.p, (const int *)P.ci.p, k0.p);
@@ -1569,22 +1573,18 @@ inline int amg_transpose(isph_ctx *ctx, const DCsr &P, DCsr &R, DevBuf<char> &tm
     while (cbits < 31 && (1ll << cbits) < (long long)R.n) ++cbits;
     const unsigned b0 = 32, b1 = 32 + (unsigned)cbits;
     size_t bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, bytes, k0.p, k1.p, P.v.p, R.v.p, (size_t)P.nnz, b0, b1, ctx->stream) != hipSuccess)
-      rc = fail("radix sort sizing failed", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS) rc = tmp.reserve(bytes > 0 ? bytes : 1);
-    if (rc == ISPH_SUCCESS &&
-        rocprim::radix_sort_pairs(tmp.p, bytes, k0.p, k1.p, P.v.p, R.v.p, (size_t)P.nnz, b0, b1, ctx->stream) != hipSuccess)
-      rc = fail("radix sort failed", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS) {
-      hipLaunchKernelGGL(k_low32, dim3(gn), dim3(kBlock), 0, ctx->stream, P.nnz, (const unsigned long long *)k1.p, R.ci.p);
-      hipLaunchKernelGGL(k_transpose_rowptr, dim3(gn), dim3(kBlock), 0, ctx->stream, P.nnz, R.n, (const unsigned long long *)k1.p, R.rp.p);
-    }
-  } else if (rc == ISPH_SUCCESS) {
-    if (hipMemsetAsync(R.rp.p, 0, sizeof(rp_t) * ((size_t)R.n + 1), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
+    ISPH_REQUIRE(rocprim::radix_sort_pairs(nullptr, bytes, k0.p, k1.p, P.v.p, R.v.p, (size_t)P.nnz, b0, b1, ctx->stream) == hipSuccess,
+                 "radix sort sizing failed");
+    ISPH_CHECK(tmp.reserve(bytes > 0 ? bytes : 1));
+    ISPH_REQUIRE(rocprim::radix_sort_pairs(tmp.p, bytes, k0.p, k1.p, P.v.p, R.v.p, (size_t)P.nnz, b0, b1, ctx->stream) == hipSuccess,
+                 "radix sort failed");
+    hipLaunchKernelGGL(k_low32, dim3(gn), dim3(kBlock), 0, ctx->stream, P.nnz, (const unsigned long long *)k1.p, R.ci.p);
+    hipLaunchKernelGGL(k_transpose_rowptr, dim3(gn), dim3(kBlock), 0, ctx->stream, P.nnz, R.n, (const unsigned long long *)k1.p, R.rp.p);
+  } else {
+    ISPH_CHECK_HIP(hipMemsetAsync(R.rp.p, 0, sizeof(rp_t) * ((size_t)R.n + 1), ctx->stream));
   }
-  if (rc == ISPH_SUCCESS && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail("transpose failed", __FILE__, __LINE__);
-  k0.release(); k1.release();
-  return rc;
+  ISPH_REQUIRE(hipStreamSynchronize(ctx->stream) == hipSuccess, "transpose failed");
+  return ISPH_SUCCESS;
 }
 
 template <int TABLE, int BS>
@@ -1598,19 +1598,16 @@ inline int amg_spgemm_t(isph_ctx *ctx, const DCsr &X, const DCsr &Y, DCsr &C, De
     hipLaunchKernelGGL((k_spgemm<TABLE, BS, false>), dim3(C.n), dim3(BS), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
                        (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p,
                        (const double *)Y.v.p, cnt.p, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
-  int rc = amg_scan(ctx, cnt.p, C.rp.p, C.n + 1, tmp);
-  long long nnz = 0;
-  if (rc == ISPH_SUCCESS) rc = amg_read_off(ctx, C.rp.p + C.n, &nnz);
-  C.nnz = nnz;
-  if (rc == ISPH_SUCCESS) rc = C.ci.reserve((size_t)(nnz > 0 ? nnz : 1));
-  if (rc == ISPH_SUCCESS) rc = C.v.reserve((size_t)(nnz > 0 ? nnz : 1));
-  if (rc == ISPH_SUCCESS && C.n > 0)
+  ISPH_CHECK(amg_scan(ctx, cnt.p, C.rp.p, C.n + 1, tmp));
+  ISPH_CHECK(amg_read_off(ctx, C.rp.p + C.n, &C.nnz));
+  ISPH_CHECK(C.ci.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
+  ISPH_CHECK(C.v.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
+  if (C.n > 0)
     hipLaunchKernelGGL((k_spgemm<TABLE, BS, true>), dim3(C.n), dim3(BS), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
                        (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p,
                        (const double *)Y.v.p, (int *)nullptr, (const rp_t *)C.rp.p, C.ci.p, C.v.p, derr);
-  if (rc == ISPH_SUCCESS && hipGetLastError() != hipSuccess) rc = fail("SpGEMM launch failed", __FILE__, __LINE__);
-  cnt.release();
-  return rc;
+  ISPH_REQUIRE(hipGetLastError() == hipSuccess, "SpGEMM launch failed");
+  return ISPH_SUCCESS;
 }
 
 // A*P: rows see few distinct aggregates, so small tables are tried first (clearing the table is most of the cost);
@@ -1730,97 +1727,87 @@ inline int amg_aggregate(isph_ctx *ctx, AmgLevel *L, double *dg, unsigned long l
   const bool prepared = prep_sc != nullptr && prep_key != nullptr;
   DevTmp<unsigned long long> key_own, t1, t2;
   DevTmp<int> flag, id, a1, cnt, scb_own, listA, listB, list1, stamp;
-  int rc = prepared ? ISPH_SUCCESS : key_own.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = listA.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = listB.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = list1.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = stamp.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS && hipMemsetAsync(stamp.p, 0, sizeof(int) * (size_t)n, ctx->stream) != hipSuccess)
-    rc = fail("memset failed", __FILE__, __LINE__);
-  if (rc == ISPH_SUCCESS && !prepared) rc = scb_own.reserve((size_t)(A.nnz > 0 ? A.nnz : 1));
+  if (!prepared) ISPH_CHECK(key_own.reserve((size_t)n));
+  ISPH_CHECK(listA.reserve((size_t)n));
+  ISPH_CHECK(listB.reserve((size_t)n));
+  ISPH_CHECK(list1.reserve((size_t)n));
+  ISPH_CHECK(stamp.reserve((size_t)n));
+  ISPH_CHECK_HIP(hipMemsetAsync(stamp.p, 0, sizeof(int) * (size_t)n, ctx->stream));
+  if (!prepared) ISPH_CHECK(scb_own.reserve((size_t)(A.nnz > 0 ? A.nnz : 1)));
   unsigned long long *const keyp = prepared ? prep_key : key_own.p;
   int *const scp = prepared ? prep_sc : scb_own.p;
-  if (rc == ISPH_SUCCESS) rc = t1.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = t2.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = flag.reserve((size_t)n + 1);
-  if (rc == ISPH_SUCCESS) rc = id.reserve((size_t)n + 1);
-  if (rc == ISPH_SUCCESS) rc = a1.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = cnt.reserve(4);
-  if (rc == ISPH_SUCCESS) rc = L->agg.reserve((size_t)n);
+  ISPH_CHECK(t1.reserve((size_t)n));
+  ISPH_CHECK(t2.reserve((size_t)n));
+  ISPH_CHECK(flag.reserve((size_t)n + 1));
+  ISPH_CHECK(id.reserve((size_t)n + 1));
+  ISPH_CHECK(a1.reserve((size_t)n));
+  ISPH_CHECK(cnt.reserve(4));
+  ISPH_CHECK(L->agg.reserve((size_t)n));
   const int gw = amg_wave_grid(n), gt = (n + kBlock - 1) / kBlock;
   const rp_t *rp = A.rp.p;
   const int *ci = A.ci.p;
   const double *v = A.v.p;
-  if (rc == ISPH_SUCCESS) {
-    L->path[AMG_PATH_PREP] = prepared ? 1 : (th2 == 0.0 ? 2 : 3);
-    if (prepared) {
-    } else if (th2 == 0.0) {
-      if (hipMemsetAsync(rho, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-      hipLaunchKernelGGL(k_amg_prepare, dim3(gw), dim3(256), 0, ctx->stream, n, rp, ci, v, dg, scp, keyp, rho);
+  L->path[AMG_PATH_PREP] = prepared ? 1 : (th2 == 0.0 ? 2 : 3);
+  if (prepared) {
+  } else if (th2 == 0.0) {
+    ISPH_CHECK_HIP(hipMemsetAsync(rho, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_amg_prepare, dim3(gw), dim3(256), 0, ctx->stream, n, rp, ci, v, dg, scp, keyp, rho);
+  } else {
+    hipLaunchKernelGGL(k_strong_cols, dim3(gw), dim3(256), 0, ctx->stream, n, rp, ci, v, (const double *)dg, th2, scp);
+    hipLaunchKernelGGL(k_mis_init, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp, keyp);
+  }
+  // rounds: t1 = max over the strong neighbourhood, t2 = max of t1 (distance 2), decide.  From the second round on
+  // the sweeps run over work lists (see k_mis_mark)
+  int und = n, cur = 0;
+  for (int round = 0; round < 1000; ++round) {
+    const int *clist = round == 0 ? nullptr : (cur ? listB.p : listA.p);
+    int *nlist = round == 0 ? listA.p : (cur ? listA.p : listB.p);
+    const int *ccnt = cnt.p + cur;
+    int *ncnt = cnt.p + (round == 0 ? 0 : 1 - cur);
+    ++L->path[AMG_PATH_MIS_ROUNDS];
+    if (clist && (long long)und * 4 <= n) {
+      ++L->path[AMG_PATH_MIS_LIST_ROUNDS];
+      ISPH_CHECK_HIP(hipMemsetAsync(cnt.p + 2, 0, sizeof(int), ctx->stream));
+      hipLaunchKernelGGL(k_mis_mark, dim3(std::min(kMisGrid, (und + 31) / 32)), dim3(256), 0, ctx->stream, ccnt, clist, rp,
+                         (const int *)scp, stamp.p, round, list1.p, cnt.p + 2);
+      hipLaunchKernelGGL(k_mis_max_list, dim3(kMisGrid), dim3(256), 0, ctx->stream, (const int *)(cnt.p + 2),
+                         (const int *)list1.p, rp, (const int *)scp, (const unsigned long long *)keyp, t1.p);
     } else {
-      hipLaunchKernelGGL(k_strong_cols, dim3(gw), dim3(256), 0, ctx->stream, n, rp, ci, v, (const double *)dg, th2, scp);
-      hipLaunchKernelGGL(k_mis_init, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp, keyp);
+      hipLaunchKernelGGL(k_mis_max, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
+                         (const unsigned long long *)keyp, t1.p, (const unsigned long long *)nullptr);
     }
-    // rounds: t1 = max over the strong neighbourhood, t2 = max of t1 (distance 2), decide.  From the second round on
-    // the sweeps run over work lists (see k_mis_mark)
-    int und = n, cur = 0;
-    for (int round = 0; round < 1000 && rc == ISPH_SUCCESS; ++round) {
-      const int *clist = round == 0 ? nullptr : (cur ? listB.p : listA.p);
-      int *nlist = round == 0 ? listA.p : (cur ? listA.p : listB.p);
-      const int *ccnt = cnt.p + cur;
-      int *ncnt = cnt.p + (round == 0 ? 0 : 1 - cur);
-      ++L->path[AMG_PATH_MIS_ROUNDS];
-      if (clist && (long long)und * 4 <= n) {
-        ++L->path[AMG_PATH_MIS_LIST_ROUNDS];
-        if (hipMemsetAsync(cnt.p + 2, 0, sizeof(int), ctx->stream) != hipSuccess) { rc = fail("memset failed", __FILE__, __LINE__); break; }
-        hipLaunchKernelGGL(k_mis_mark, dim3(std::min(kMisGrid, (und + 31) / 32)), dim3(256), 0, ctx->stream, ccnt, clist, rp,
-                           (const int *)scp, stamp.p, round, list1.p, cnt.p + 2);
-        hipLaunchKernelGGL(k_mis_max_list, dim3(kMisGrid), dim3(256), 0, ctx->stream, (const int *)(cnt.p + 2),
-                           (const int *)list1.p, rp, (const int *)scp, (const unsigned long long *)keyp, t1.p);
-      } else {
-        hipLaunchKernelGGL(k_mis_max, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
-                           (const unsigned long long *)keyp, t1.p, (const unsigned long long *)nullptr);
-      }
-      if (clist)
-        hipLaunchKernelGGL(k_mis_max_list, dim3(std::min(kMisGrid, amg_wave_grid(und))), dim3(256), 0, ctx->stream, ccnt, clist,
-                           rp, (const int *)scp, (const unsigned long long *)t1.p, t2.p);
-      else
-        hipLaunchKernelGGL(k_mis_max, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
-                           (const unsigned long long *)t1.p, t2.p, (const unsigned long long *)keyp);
-      if (hipMemsetAsync(ncnt, 0, sizeof(int), ctx->stream) != hipSuccess) { rc = fail("memset failed", __FILE__, __LINE__); break; }
-      const int nd = clist ? und : n;
-      hipLaunchKernelGGL(k_mis_decide_list, dim3(std::min(kMisGrid, (nd + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                         ccnt, clist, n, keyp, (const unsigned long long *)t2.p, nlist, ncnt);
-      rc = amg_read_int(ctx, ncnt, &und);
-      if (round > 0) cur = 1 - cur;
-      if (und == 0) break;
-      if (round == 999) rc = fail("MIS did not terminate", __FILE__, __LINE__);
-    }
+    if (clist)
+      hipLaunchKernelGGL(k_mis_max_list, dim3(std::min(kMisGrid, amg_wave_grid(und))), dim3(256), 0, ctx->stream, ccnt, clist,
+                         rp, (const int *)scp, (const unsigned long long *)t1.p, t2.p);
+    else
+      hipLaunchKernelGGL(k_mis_max, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
+                         (const unsigned long long *)t1.p, t2.p, (const unsigned long long *)keyp);
+    ISPH_CHECK_HIP(hipMemsetAsync(ncnt, 0, sizeof(int), ctx->stream));
+    const int nd = clist ? und : n;
+    hipLaunchKernelGGL(k_mis_decide_list, dim3(std::min(kMisGrid, (nd + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                       ccnt, clist, n, keyp, (const unsigned long long *)t2.p, nlist, ncnt);
+    ISPH_CHECK(amg_read_int(ctx, ncnt, &und));
+    if (round > 0) cur = 1 - cur;
+    if (und == 0) break;
+    ISPH_REQUIRE(round < 999, "MIS did not terminate");
   }
-  int nroot = 0, nleft = 0, last = 0;
-  if (rc == ISPH_SUCCESS) {
-    hipLaunchKernelGGL(k_flag_roots, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const unsigned long long *)keyp, flag.p);
-    if (hipMemsetAsync(flag.p + n, 0, sizeof(int), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-  }
-  if (rc == ISPH_SUCCESS) rc = amg_scan(ctx, flag.p, id.p, n + 1, tmp);
-  if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, id.p + n, &nroot);
-  if (rc == ISPH_SUCCESS) {
-    hipLaunchKernelGGL(k_agg_pass1, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
-                       (const unsigned long long *)keyp, (const int *)id.p, a1.p);
-    hipLaunchKernelGGL(k_agg_pass2, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp, v, (const int *)a1.p,
-                       L->agg.p, flag.p);
-    rc = amg_scan(ctx, flag.p, id.p, n + 1, tmp);
-  }
-  if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, id.p + n, &nleft);
-  (void)last;
-  if (rc == ISPH_SUCCESS && nleft > 0)
+  int nroot = 0, nleft = 0;
+  hipLaunchKernelGGL(k_flag_roots, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const unsigned long long *)keyp, flag.p);
+  ISPH_CHECK_HIP(hipMemsetAsync(flag.p + n, 0, sizeof(int), ctx->stream));
+  ISPH_CHECK(amg_scan(ctx, flag.p, id.p, n + 1, tmp));
+  ISPH_CHECK(amg_read_int(ctx, id.p + n, &nroot));
+  hipLaunchKernelGGL(k_agg_pass1, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp,
+                     (const unsigned long long *)keyp, (const int *)id.p, a1.p);
+  hipLaunchKernelGGL(k_agg_pass2, dim3(gw), dim3(256), 0, ctx->stream, n, rp, (const int *)scp, v, (const int *)a1.p,
+                     L->agg.p, flag.p);
+  ISPH_CHECK(amg_scan(ctx, flag.p, id.p, n + 1, tmp));
+  ISPH_CHECK(amg_read_int(ctx, id.p + n, &nleft));
+  if (nleft > 0)
     hipLaunchKernelGGL(k_agg_pass3, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)flag.p, (const int *)id.p, nroot,
                        L->agg.p);
-  if (rc == ISPH_SUCCESS && hipGetLastError() != hipSuccess) rc = fail("aggregation kernels failed", __FILE__, __LINE__);
+  ISPH_REQUIRE(hipGetLastError() == hipSuccess, "aggregation kernels failed");
   *nagg_out = nroot + nleft;
-  key_own.release(); t1.release(); t2.release(); flag.release(); id.release(); a1.release(); cnt.release(); scb_own.release();
-  listA.release(); listB.release(); list1.release(); stamp.release();
-  return rc;
+  return ISPH_SUCCESS;
 }
 
 // P = (I - omega/rho D^-1 A) P_tent and the coarse null vector
@@ -1834,65 +1821,56 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
   DevTmp<unsigned long long> k0, k1;
   DevTmp<int> start, cnt;
   DevTmp<double> pt;
-  int rc = k0.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = k1.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = start.reserve((size_t)nagg + 1);
-  if (rc == ISPH_SUCCESS) rc = cnt.reserve((size_t)n + 1);
-  if (rc == ISPH_SUCCESS) rc = pt.reserve((size_t)n);
-  if (rc == ISPH_SUCCESS) rc = nvc.reserve((size_t)nagg);
+  ISPH_CHECK(k0.reserve((size_t)n));
+  ISPH_CHECK(k1.reserve((size_t)n));
+  ISPH_CHECK(start.reserve((size_t)nagg + 1));
+  ISPH_CHECK(cnt.reserve((size_t)n + 1));
+  ISPH_CHECK(pt.reserve((size_t)n));
+  ISPH_CHECK(nvc.reserve((size_t)nagg));
   const int gw = amg_wave_grid(n), gt = (n + kBlock - 1) / kBlock;
-  if (rc == ISPH_SUCCESS) {
-    hipLaunchKernelGGL(k_member_keys, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)L->agg.p, k0.p);
-    // keys are made in index order: a STABLE sort by the aggregate bits alone leaves the members of an aggregate ascending
-    // (nodes outside every aggregate carry all ones there: one value more than the aggregates need)
-    int abits = 1;
-    while (abits < 32 && (1ll << abits) <= (long long)nagg) ++abits;
-    const unsigned b0 = 32, b1 = 32 + (unsigned)abits;
-    size_t bytes = 0;
-    if (rocprim::radix_sort_keys(nullptr, bytes, k0.p, k1.p, (size_t)n, b0, b1, ctx->stream) != hipSuccess)
-      rc = fail("radix sort sizing failed", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS) rc = tmp.reserve(bytes > 0 ? bytes : 1);
-    if (rc == ISPH_SUCCESS && rocprim::radix_sort_keys(tmp.p, bytes, k0.p, k1.p, (size_t)n, b0, b1, ctx->stream) != hipSuccess)
-      rc = fail("radix sort failed", __FILE__, __LINE__);
+  hipLaunchKernelGGL(k_member_keys, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)L->agg.p, k0.p);
+  // keys are made in index order: a STABLE sort by the aggregate bits alone leaves the members of an aggregate ascending
+  // (nodes outside every aggregate carry all ones there: one value more than the aggregates need)
+  int abits = 1;
+  while (abits < 32 && (1ll << abits) <= (long long)nagg) ++abits;
+  const unsigned b0 = 32, b1 = 32 + (unsigned)abits;
+  size_t bytes = 0;
+  ISPH_REQUIRE(rocprim::radix_sort_keys(nullptr, bytes, k0.p, k1.p, (size_t)n, b0, b1, ctx->stream) == hipSuccess, "radix sort sizing failed");
+  ISPH_CHECK(tmp.reserve(bytes > 0 ? bytes : 1));
+  ISPH_REQUIRE(rocprim::radix_sort_keys(tmp.p, bytes, k0.p, k1.p, (size_t)n, b0, b1, ctx->stream) == hipSuccess, "radix sort failed");
+  hipLaunchKernelGGL(k_segment_starts, dim3(gt), dim3(kBlock), 0, ctx->stream, n, nagg, (const unsigned long long *)k1.p, start.p);
+  hipLaunchKernelGGL(k_agg_norm, dim3(amg_wave_grid(nagg)), dim3(256), 0, ctx->stream, nagg, (const int *)start.p,
+                     (const unsigned long long *)k1.p, (const double *)L->nv.p, nvc.p);
+  hipLaunchKernelGGL(k_ptent, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)L->agg.p, (const double *)L->nv.p,
+                     (const double *)nvc.p, pt.p);
+  if (!rho_ready) {
+    ISPH_CHECK_HIP(hipMemsetAsync(rho_dev, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_amg_rho, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                       (const double *)A.v.p, dg, rho_dev);
   }
   double rho_h = 0.0;
-  if (rc == ISPH_SUCCESS) {
-    hipLaunchKernelGGL(k_segment_starts, dim3(gt), dim3(kBlock), 0, ctx->stream, n, nagg, (const unsigned long long *)k1.p, start.p);
-    hipLaunchKernelGGL(k_agg_norm, dim3(amg_wave_grid(nagg)), dim3(256), 0, ctx->stream, nagg, (const int *)start.p,
-                       (const unsigned long long *)k1.p, (const double *)L->nv.p, nvc.p);
-    hipLaunchKernelGGL(k_ptent, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)L->agg.p, (const double *)L->nv.p,
-                       (const double *)nvc.p, pt.p);
-    if (!rho_ready) {
-      if (hipMemsetAsync(rho_dev, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-      hipLaunchKernelGGL(k_amg_rho, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
-                         (const double *)A.v.p, dg, rho_dev);
-    }
-    if (rc == ISPH_SUCCESS &&
-        (hipMemcpyAsync(&rho_h, rho_dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-         hipStreamSynchronize(ctx->stream) != hipSuccess))
-      rc = fail("rho read-back failed", __FILE__, __LINE__);
-  }
+  ISPH_REQUIRE(hipMemcpyAsync(&rho_h, rho_dev, sizeof(double), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
+                   hipStreamSynchronize(ctx->stream) == hipSuccess,
+               "rho read-back failed");
   const double damp = lambda > 0.0 ? omega / lambda : rho_h > 0.0 ? omega / rho_h : 0.0;
   DCsr &P = L->P;
   P.n = n; P.m = nagg;
-  if (rc == ISPH_SUCCESS) rc = P.rp.reserve((size_t)n + 1);
+  ISPH_CHECK(P.rp.reserve((size_t)n + 1));
   const rp_t *arp = A.rp.p;
   const int *aci = A.ci.p;
   const double *av = A.v.p;
   const int *agg = L->agg.p;
-  long long nnz = 0;
   bool one_pass = false;
   const char *two = getenv("ISPH_AMG_PROLONG_TWO_PASS");
-  for (int attempt = 0; attempt < 2 && rc == ISPH_SUCCESS && !one_pass && !(two && two[0] == '1'); ++attempt) {
+  for (int attempt = 0; attempt < 2 && !one_pass && !(two && two[0] == '1'); ++attempt) {
     // one pass into scratch rows of 16 slots (four rows per wave), then of 64 (one row per wave)
     const int shift = attempt == 0 ? 4 : 6, lpr = 1 << shift;
     int herr = 0;
     DevTmp<int> ps_ci;
     DevTmp<double> ps_v;
-    rc = ps_ci.reserve((size_t)n << shift);
-    if (rc == ISPH_SUCCESS) rc = ps_v.reserve((size_t)n << shift);
-    if (rc != ISPH_SUCCESS) break;
-    if (hipMemsetAsync(cnt.p + n, 0, sizeof(int), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
+    ISPH_CHECK(ps_ci.reserve((size_t)n << shift));
+    ISPH_CHECK(ps_v.reserve((size_t)n << shift));
+    ISPH_CHECK_HIP(hipMemsetAsync(cnt.p + n, 0, sizeof(int), ctx->stream));
     const int rows_wg = kAmgWaves * (64 / lpr), grid = (n + rows_wg - 1) / rows_wg;
     if (attempt == 0)
       hipLaunchKernelGGL((k_prolong_rows<16>), dim3(grid), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
@@ -1900,46 +1878,40 @@ inline int amg_prolongator(isph_ctx *ctx, AmgLevel *L, const double *dg, unsigne
     else
       hipLaunchKernelGGL((k_prolong_rows<64>), dim3(grid), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
                          cnt.p, ps_ci.p, ps_v.p, derr);
-    if (rc == ISPH_SUCCESS) rc = amg_scan(ctx, cnt.p, P.rp.p, n + 1, tmp);
-    if (rc == ISPH_SUCCESS && hipMemcpyAsync(&nnz, P.rp.p + n, sizeof(rp_t), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-      rc = fail("copy failed", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr, &herr);
-    if (rc == ISPH_SUCCESS && (herr & 8)) {   // a row longer than the scratch rows
+    ISPH_CHECK(amg_scan(ctx, cnt.p, P.rp.p, n + 1, tmp));
+    ISPH_CHECK_HIP(hipMemcpyAsync(&P.nnz, P.rp.p + n, sizeof(rp_t), hipMemcpyDeviceToHost, ctx->stream));
+    ISPH_CHECK(amg_read_int(ctx, derr, &herr));
+    if (herr & 8) {   // a row longer than the scratch rows
       herr &= ~8;
-      if (hipMemcpyAsync(derr, &herr, sizeof(int), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess)
-        rc = fail("copy failed", __FILE__, __LINE__);
-    } else if (rc == ISPH_SUCCESS) {
-      one_pass = true;
-      L->path[AMG_PATH_PROLONG] = lpr;
-      P.nnz = nnz;
-      rc = P.ci.reserve((size_t)(nnz > 0 ? nnz : 1));
-      if (rc == ISPH_SUCCESS) rc = P.v.reserve((size_t)(nnz > 0 ? nnz : 1));
-      if (rc == ISPH_SUCCESS && n > 0) {
-        const long long total = (long long)n * 16;
-        hipLaunchKernelGGL(k_rows_compact, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, n, shift,
-                           (const rp_t *)P.rp.p, (const int *)ps_ci.p, (const double *)ps_v.p, P.ci.p, P.v.p);
-      }
+      ISPH_CHECK_HIP(hipMemcpyAsync(derr, &herr, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+      ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+      continue;
+    }
+    one_pass = true;
+    L->path[AMG_PATH_PROLONG] = lpr;
+    ISPH_CHECK(P.ci.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+    ISPH_CHECK(P.v.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+    if (n > 0) {
+      const long long total = (long long)n * 16;
+      hipLaunchKernelGGL(k_rows_compact, dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, n, shift,
+                         (const rp_t *)P.rp.p, (const int *)ps_ci.p, (const double *)ps_v.p, P.ci.p, P.v.p);
     }
   }
-  if (rc == ISPH_SUCCESS && !one_pass) {
+  if (!one_pass) {
     L->path[AMG_PATH_PROLONG] = 2;   // the two passes
-    if (hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)n + 1), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
+    ISPH_CHECK_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)n + 1), ctx->stream));
     hipLaunchKernelGGL((k_prolong<0>), dim3(gw), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
                        cnt.p, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
-    if (rc == ISPH_SUCCESS) rc = amg_scan(ctx, cnt.p, P.rp.p, n + 1, tmp);
-    if (rc == ISPH_SUCCESS) rc = amg_read_off(ctx, P.rp.p + n, &nnz);
-    P.nnz = nnz;
-    if (rc == ISPH_SUCCESS) rc = P.ci.reserve((size_t)(nnz > 0 ? nnz : 1));
-    if (rc == ISPH_SUCCESS) rc = P.v.reserve((size_t)(nnz > 0 ? nnz : 1));
-    if (rc == ISPH_SUCCESS)
-      hipLaunchKernelGGL((k_prolong<1>), dim3(gw), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
-                         (int *)nullptr, (const rp_t *)P.rp.p, P.ci.p, P.v.p, derr);
+    ISPH_CHECK(amg_scan(ctx, cnt.p, P.rp.p, n + 1, tmp));
+    ISPH_CHECK(amg_read_off(ctx, P.rp.p + n, &P.nnz));
+    ISPH_CHECK(P.ci.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+    ISPH_CHECK(P.v.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
+    hipLaunchKernelGGL((k_prolong<1>), dim3(gw), dim3(256), 0, ctx->stream, n, arp, aci, av, dg, agg, (const double *)pt.p, damp,
+                       (int *)nullptr, (const rp_t *)P.rp.p, P.ci.p, P.v.p, derr);
   }
-  if (rc == ISPH_SUCCESS && hipGetLastError() != hipSuccess) rc = fail("prolongator kernels failed", __FILE__, __LINE__);
-  if (rc == ISPH_SUCCESS && keep) { dev_move(L->mkeys, k1); dev_move(L->mstart, start); }
-  k0.release(); k1.release(); start.release(); cnt.release(); pt.release();
-  return rc;
+  ISPH_REQUIRE(hipGetLastError() == hipSuccess, "prolongator kernels failed");
+  if (keep) { dev_move(L->mkeys, k1); dev_move(L->mstart, start); }
+  return ISPH_SUCCESS;
 }
 
 
@@ -2015,8 +1987,8 @@ __global__ void k_amg_ext_fill(int n, int nrecv, const rp_t *__restrict__ prp, c
 // lists.  K: longest P row on any send list of any rank (agreed by the caller).
 // Two halves, so that the ranks can agree between them: everything of the first half that can fail on one rank alone
 // (allocations, scans, read-backs) happens BEFORE any rank enters the point-to-point exchange of the second half -- a rank
-// that returned early from a single function left its peers waiting in that exchange for ever (amg_create holds a
-// consensus all-reduce between the halves).
+// that returned early from a single function left its peers waiting in that exchange for ever (amg_extend_prolongator holds a
+// consensus between the halves).
 struct AmgExtendState {
   DevTmp<double> sbuf, rbuf;
   DevTmp<int> flag, pos, list;
@@ -2192,15 +2164,9 @@ inline int amg_level_buffers(AmgLevel *L, bool f32 = false) {
 // (the diagonal and the bound rho from the level's SELL matrix).  dist: collective, rho is the all-reduced maximum.
 inline int amg_level_estimate(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int level, bool dist) {
   DevTmp<double> dinv;
-  double rho = 0.0;
+  double rho = 0.0;   // (stays 0 when the rank fails)
   int rc = cheb_diag_rho(ctx, L->Am, dinv, &rho);
-  if (dist) {
-    double h[2] = {rc == ISPH_SUCCESS ? rho : 0.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-    if (comm_host_allreduce(ctx, h, 2, /*max*/ 1) != ISPH_SUCCESS) return fail("AMG: the all-reduce of rho failed", __FILE__, __LINE__);
-    if (h[1] != 0.0) return rc != ISPH_SUCCESS ? rc : fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
-    rho = h[0];
-  }
-  if (rc != ISPH_SUCCESS) return rc;
+  if (!comm_consensus(ctx, dist, "AMG", "AMG: the all-reduce of rho failed", &rho, 1, rc)) return rc;
   return eig_estimate(ctx, L->Am, nullptr, dinv.p, rho, G->eig_iters, level, eig_unfused_env(), dist, &L->eig);
 }
 
@@ -2274,7 +2240,7 @@ inline int amg_ilu_smoother(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, int l
 // dense block inverses are written again).  rc: the outcome of the set-up so far.
 inline int amg_smoothers(isph_ctx *ctx, isph_amg *G, bool dist, int *derr, int rc) {
   // Chebyshev across ranks: rho of a level is all-reduced, one collective call per level.  The walk is entered only
-  // when the set-up has succeeded so far -- after the consensus above that is all ranks or none, and with success on all
+  // when the set-up has succeeded so far -- after the comm_rank_offsets of amg_create that is all ranks or none, and with success on all
   // ranks every rank has gone through the same coarsening steps, so nlev is agreed here (a rank that failed in a step
   // holds one level less than its peers; none of them walks).  A failure that arises INSIDE the walk is carried through
   // the remaining levels' all-reduces (prior_failure), so that the ranks' calls still pair up.
@@ -2331,21 +2297,51 @@ inline int amg_smoothers(isph_ctx *ctx, isph_amg *G, bool dist, int *derr, int r
   return rc;
 }
 
-// the dense inverse of the coarsest operator on one rank (err bit 4: singular)
+// aug = [A | I] -> [A^-1 | .], or the refusal of a singular A (err bit 4)
+inline int amg_invert_or_refuse(isph_ctx *ctx, double *aug, int n, int *derr) {
+  if (n <= 0) return ISPH_SUCCESS;
+  ISPH_CHECK(amg_dense_invert(ctx, aug, n, derr));
+  int herr = 0;
+  ISPH_CHECK(amg_read_int(ctx, derr, &herr));
+  ISPH_REQUIRE(!(herr & 4), "AMG: coarsest operator is singular (pass the null vector)");
+  return ISPH_SUCCESS;
+}
+
+// the dense inverse of the coarsest operator on one rank
 inline int amg_coarse_inverse(isph_ctx *ctx, isph_amg *G, int *derr) {
   AmgLevel *L = G->L.back();
   const int nc = L->A.n;
   G->nc = nc;
-  int rc = G->cinv.reserve((size_t)2 * nc * nc + (size_t)nc + 1);
-  if (rc == ISPH_SUCCESS && nc > 0) {
+  ISPH_CHECK(G->cinv.reserve((size_t)2 * nc * nc + (size_t)nc + 1));
+  if (nc > 0)
     hipLaunchKernelGGL(k_dense_from_csr, dim3(nc), dim3(kBlock), 0, ctx->stream, nc, (const rp_t *)L->A.rp.p,
                        (const int *)L->A.ci.p, (const double *)L->A.v.p, G->cinv.p);
-    rc = amg_dense_invert(ctx, G->cinv.p, nc, derr);
-    int herr = 0;
-    if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr, &herr);
-    if (rc == ISPH_SUCCESS && (herr & 4)) rc = fail("AMG: coarsest operator is singular (pass the null vector)", __FILE__, __LINE__);
-  }
-  return rc;
+  return amg_invert_or_refuse(ctx, G->cinv.p, nc, derr);
+}
+
+// ... across ranks: the coarsest operators of all ranks form ONE system of N rows (ML gathers it for its direct solver),
+// rows off .. off + L->A.n are this rank's; every rank inverts it.  All ranks enter together (the consensus of amg_create).
+inline int amg_coarse_inverse_dist(isph_ctx *ctx, isph_amg *G, int N, int off, int *derr) {
+  AmgLevel *L = G->L.back();
+  const int ncl = L->A.n;
+  G->nc = N; G->nc_off = off; G->nc_loc = ncl;
+  const isph_halo &Hc = L->Am->halo;
+  DevTmp<double> gs, gr;
+  ISPH_CHECK(G->cinv.reserve((size_t)2 * N * N + (size_t)N + 1));
+  ISPH_CHECK(G->bglob.reserve((size_t)std::max(N, 1)));
+  ISPH_CHECK(gs.reserve((size_t)std::max(Hc.nsend, 1)));
+  ISPH_CHECK(gr.reserve((size_t)std::max(Hc.nrecv, 1)));
+  ISPH_CHECK_HIP(hipMemsetAsync(G->cinv.p, 0, sizeof(double) * (size_t)2 * N * N, ctx->stream));
+  if (Hc.nsend > 0)
+    hipLaunchKernelGGL(k_amg_gid, dim3((Hc.nsend + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, Hc.nsend, off, (const int *)Hc.send_idx.p, gs.p);
+  ISPH_CHECK(comm_exchange(ctx, Hc, gs.p, gr.p, 1, false, ctx->stream));   // global numbers of the ghost columns
+  if (ncl > 0)
+    hipLaunchKernelGGL(k_dense_from_csr_glob, dim3(ncl), dim3(kBlock), 0, ctx->stream, ncl, N, off, (const rp_t *)L->A.rp.p,
+                       (const int *)L->A.ci.p, (const double *)L->A.v.p, (const double *)gr.p, G->cinv.p);
+  ISPH_CHECK(comm_allreduce(ctx, G->cinv.p, 2 * N * N, 0, ctx->stream));
+  ISPH_CHECK(amg_invert_or_refuse(ctx, G->cinv.p, N, derr));
+  ISPH_REQUIRE(hipStreamSynchronize(ctx->stream) == hipSuccess, "AMG setup failed");   // gs, gr leave scope
+  return ISPH_SUCCESS;
 }
 
 // held hierarchy: tmap of level L (k_transpose_map)
@@ -2370,8 +2366,46 @@ inline int amg_sort_rows(isph_ctx *ctx, DCsr &C, DevBuf<char> &tmp) {
   return rc;
 }
 
-inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
-                      isph_amg **out) {
+// ---- amg_create and its steps ------------------------------------------------------------------------------------------
+// On more than one rank every decision about the depth of the hierarchy is taken by all ranks together (the set-up and
+// the cycle exchange with the neighbours on every level) and a failure on one rank is a failure on all: the steps that
+// hold a collective call -- amg_create, amg_coarsen_step, amg_extend_prolongator, amg_level_estimate, amg_smoothers --
+// carry rc past a local failure to their next comm_consensus / comm_rank_offsets (comm.hpp).  Everything else is local to
+// the rank and returns at its first failure.
+constexpr const char *kAmgNoConsensus = "AMG: consensus between the ranks failed";
+
+// the scratch of one set-up
+struct AmgSetup {
+  DevTmp<char> tmp;
+  DevTmp<int> derr;                 // the error word of the set-up kernels (amg_error_word; bit 4: amg_invert_or_refuse)
+  DevTmp<double> dg;
+  DevTmp<unsigned long long> rho;
+  // threshold 0: what the SELL -> CSR sweep of the fine level prepares for its aggregation (k_sell_to_csr_i32<true>)
+  bool prep0 = false;
+  DevTmp<int> sc0;
+  DevTmp<unsigned long long> key0;
+};
+struct DCsrTmp : DCsr {
+  ~DCsrTmp() { release(); }
+};
+typedef std::unique_ptr<AmgLevel, void (*)(AmgLevel *)> AmgLevelPtr;
+
+// the error word of the prolongator and SpGEMM kernels -> the library's messages
+inline int amg_error_word(int herr) {
+  if (herr & 1) return fail("AMG: a row touches more than 512 aggregates", __FILE__, __LINE__);
+  if (herr & 2) return fail("AMG: coarse operator row too dense for the SpGEMM table", __FILE__, __LINE__);
+  return ISPH_SUCCESS;
+}
+
+// the fine-level CSR copy only serves the set-up (the cycle runs on the SELL matrix): 12 B per entry go back to the
+// pool before the smoother is built; isph_prec_amg_export rebuilds it on demand
+inline void amg_release_fine_csr(isph_amg *G) {
+  AmgLevel *L0 = G->L[0];
+  if (G->nlev > 1) { L0->A.ci.release(); L0->A.v.release(); L0->A.rp.release(); }
+}
+
+// the parameters, checked, in a new isph_amg
+inline int amg_new(const isph_amg_params *prm, bool singular, isph_amg **out) {
   ISPH_REQUIRE(prm->max_levels >= 1 && prm->max_levels <= 8, "max_levels must be in [1,8]");
   ISPH_REQUIRE(prm->smoother == 2 || (prm->block >= 64 && prm->block <= 1024 && prm->block % 64 == 0),
                "smoother block must be a multiple of 64 in [64,1024]");   // (Chebyshev has no blocks: the field is not read)
@@ -2399,225 +2433,210 @@ inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *
   G->cycle_bits = (prm->smoother == 2 && prm->cycle_bits == 32) ? 32 : 64;
   // (cycle_bits 32: the float plane of every level operator is the one cheb_value_bits 32 makes, whatever that field says)
   G->cheb_value_bits = (prm->smoother == 2 && (prm->cheb_value_bits == 32 || G->cycle_bits == 32)) ? 32 : 64;
-  G->block = prm->block; G->sweeps = prm->sweeps; G->singular = nullvec_dev != nullptr;
+  G->block = prm->block; G->sweeps = prm->sweeps; G->singular = singular;
   G->gs_eff = prm->smoother == 1;
   G->cheb = prm->smoother == 2;
   G->ilu = prm->smoother == 4;
   G->ilu_fill = G->ilu ? prm->ilu_fill : 0;
   G->omega = prm->omega; G->cheb_ratio = prm->cheb_ratio;
-  DevTmp<char> tmp;
-  DevTmp<int> derr;
-  DevTmp<double> dg;
-  DevTmp<unsigned long long> rho;
-  int rc = derr.reserve(1);
-  if (rc == ISPH_SUCCESS) rc = rho.reserve(1);
-  if (rc == ISPH_SUCCESS && hipMemsetAsync(derr.p, 0, sizeof(int), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
+  *out = G;
+  return ISPH_SUCCESS;
+}
+
+// level 0: the device CSR copy of Am and the null vector (the level is in G whatever the outcome)
+inline int amg_fine_level(isph_ctx *ctx, isph_amg *G, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
+                          AmgSetup &S) {
   AmgLevel *L0 = new AmgLevel();
   G->L.push_back(L0);
   G->nlev = 1;
   L0->Am = Am;
   const int n0 = Am->S.nrow;
+  ISPH_CHECK(S.derr.reserve(1));
+  ISPH_CHECK(S.rho.reserve(1));
+  ISPH_CHECK_HIP(hipMemsetAsync(S.derr.p, 0, sizeof(int), ctx->stream));
   // threshold 0: the SELL -> CSR sweep of the fine level prepares the aggregation on the way (k_sell_to_csr_i32<true>)
-  DevTmp<int> sc0;
-  DevTmp<unsigned long long> key0;
-  bool prep0 = prm->theta == 0.0 && n0 > 0 && prm->max_levels > 1 && n0 > prm->coarse_max && !(getenv("ISPH_AMG_NO_FUSED_PREP") != nullptr);
-  if (rc == ISPH_SUCCESS && prep0) {
-    rc = sc0.reserve((size_t)(Am->S.nnz > 0 ? Am->S.nnz : 1));
-    if (rc == ISPH_SUCCESS) rc = key0.reserve((size_t)n0);
-    if (rc == ISPH_SUCCESS) rc = dg.reserve((size_t)n0);
+  S.prep0 = prm->theta == 0.0 && n0 > 0 && prm->max_levels > 1 && n0 > prm->coarse_max && !(getenv("ISPH_AMG_NO_FUSED_PREP") != nullptr);
+  if (S.prep0) {
+    ISPH_CHECK(S.sc0.reserve((size_t)(Am->S.nnz > 0 ? Am->S.nnz : 1)));
+    ISPH_CHECK(S.key0.reserve((size_t)n0));
+    ISPH_CHECK(S.dg.reserve((size_t)n0));
+    ISPH_CHECK(amg_csr_from_sell(ctx, Am->S, L0->A, S.tmp, S.dg.p, S.sc0.p, S.key0.p, S.rho.p));
+  } else {
+    ISPH_CHECK(amg_csr_from_sell(ctx, Am->S, L0->A, S.tmp));
   }
-  if (rc == ISPH_SUCCESS) rc = prep0 ? amg_csr_from_sell(ctx, Am->S, L0->A, tmp, dg.p, sc0.p, key0.p, rho.p) : amg_csr_from_sell(ctx, Am->S, L0->A, tmp);
-  if (rc == ISPH_SUCCESS) rc = L0->nv.reserve((size_t)(n0 > 0 ? n0 : 1));
-  if (rc == ISPH_SUCCESS) {
-    if (nullvec_dev) {
-      if (hipMemcpyAsync(L0->nv.p, nullvec_dev, sizeof(double) * (size_t)n0, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-        rc = fail("copy failed", __FILE__, __LINE__);
-    } else if (n0 > 0) {
-      hipLaunchKernelGGL(k_fill, dim3(stream_grid(n0)), dim3(kBlock), 0, ctx->stream, n0, L0->nv.p, 1.0);
-    }
+  ISPH_CHECK(L0->nv.reserve((size_t)(n0 > 0 ? n0 : 1)));
+  if (nullvec_dev)
+    ISPH_CHECK_HIP(hipMemcpyAsync(L0->nv.p, nullvec_dev, sizeof(double) * (size_t)n0, hipMemcpyDeviceToDevice, ctx->stream));
+  else if (n0 > 0)
+    hipLaunchKernelGGL(k_fill, dim3(stream_grid(n0)), dim3(kBlock), 0, ctx->stream, n0, L0->nv.p, 1.0);
+  return ISPH_SUCCESS;
+}
+
+// The halo extension of P on more than one rank: the P rows behind A's ghost columns (amg_extend_pack /
+// amg_extend_finish) into X.Pext, and the coarse level's halo lists.  Returns false when the ranks agree to end the
+// set-up here (rc says why).
+struct AmgExtension {
+  DCsrTmp Pext;
+  std::vector<int> cs_ptr, cs_idx, cr_ptr;
+  bool extended = false;
+};
+inline int amg_send_rowmax(isph_ctx *ctx, const isph_halo &H, const DCsr &P, int *hk) {
+  DevTmp<int> kmax;
+  ISPH_CHECK(kmax.reserve(1));
+  ISPH_CHECK_HIP(hipMemsetAsync(kmax.p, 0, sizeof(int), ctx->stream));
+  if (H.nsend > 0)
+    hipLaunchKernelGGL(k_amg_send_rowmax, dim3((H.nsend + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, H.nsend,
+                       (const int *)H.send_idx.p, (const rp_t *)P.rp.p, kmax.p);
+  return amg_read_int(ctx, kmax.p, hk);
+}
+inline bool amg_extend_prolongator(isph_ctx *ctx, AmgLevel *L, AmgSetup &S, AmgExtension &X, int &rc) {
+  const isph_halo &H = L->Am->halo;
+  // K is agreed first, by all ranks
+  int hk = 0;
+  if (rc == ISPH_SUCCESS) rc = amg_send_rowmax(ctx, H, L->P, &hk);
+  double K = (double)hk;
+  if (!comm_consensus(ctx, true, "AMG", kAmgNoConsensus, &K, 1, rc)) return false;
+  AmgExtendState est;
+  const int Kx = std::max((int)K, 1);
+  // (a rank without ghost columns of its own still owes its neighbours their rows)
+  if (H.npeers > 0) rc = amg_extend_pack(ctx, H, L->P, Kx, est, X.cs_ptr, X.cs_idx, S.tmp);
+  // nobody enters the exchange unless everybody can
+  if (!comm_consensus(ctx, true, "AMG", kAmgNoConsensus, nullptr, 0, rc)) return false;
+  if (H.npeers > 0) {
+    rc = amg_extend_finish(ctx, H, L->P, Kx, est, X.Pext, X.cr_ptr, S.tmp);
+    X.extended = rc == ISPH_SUCCESS;
   }
-  // more than one rank: every decision about the depth of the hierarchy is taken by all ranks together (the set-up and
-  // the cycle exchange with the neighbours on every level), a failure on one rank is a failure on all
-  // (ISPH_AMG_RANK_LOCAL=1: the hierarchy of rounds 1-3, P^T A P with the rank's own columns only -- kept for comparisons)
-  const char *env_local = getenv("ISPH_AMG_RANK_LOCAL");
-  const bool dist = comm_active(ctx) && ctx->nranks > 1 && !(env_local && env_local[0] == '1');
+  return true;
+}
+
+// The operators of a level whose P is there: R, A P, the coarse operator Lc->A = R (A P) and the SELL images the cycle runs on
+inline int amg_level_operators(isph_ctx *ctx, const isph_amg *G, AmgLevel *L, AmgLevel *Lc, AmgExtension &X, AmgSetup &S) {
+  DCsrTmp AP;
+  const isph_halo &H = L->Am->halo;
+  ISPH_CHECK(amg_transpose(ctx, L->P, L->R, S.tmp));
+  if (G->held) ISPH_CHECK(amg_transpose_map(ctx, L));
+  ISPH_CHECK(amg_spgemm_ap(ctx, L->A, X.extended ? X.Pext : L->P, AP, S.tmp, S.derr.p, &L->path[AMG_PATH_AP]));
+  // held: the kept rows of A P must ascend; the table kernels (stages 3-5) leave them in table order
+  if (G->held && L->path[AMG_PATH_AP] >= 3) ISPH_CHECK(amg_sort_rows(ctx, AP, S.tmp));
+  L->path[AMG_PATH_GALERKIN] = AP.m <= kGalerkinTable ? 1 : 2;   // k_spgemm's ycols <= TABLE: direct-addressed / open addressing
+  ISPH_CHECK((amg_spgemm_t<kGalerkinTable, 64>(ctx, L->R, AP, Lc->A, S.tmp, S.derr.p)));
+  X.Pext.release();
+  int herr = 0;
+  ISPH_CHECK(amg_read_int(ctx, S.derr.p, &herr));
+  ISPH_CHECK(amg_error_word(herr));
+  ISPH_CHECK(mat_from_device_csr(ctx, L->P.n, L->P.m, L->P.rp.p, L->P.ci.p, L->P.v.p, L->P.nnz, &L->Pm, /*rows_sorted=*/true));
+  ISPH_CHECK(mat_from_device_csr(ctx, Lc->A.n, Lc->A.m, Lc->A.rp.p, Lc->A.ci.p, Lc->A.v.p, Lc->A.nnz, &Lc->Aown));
+  // without ghost columns A (x + P e) = A x + (A P) e: the cycle updates the residual with the product already at hand
+  // (a fifth of A's entries) instead of a second sweep over A
+  // (not on a rank that sends to neighbours: the product it saves is also this rank's part of their exchange)
+  // (not with cheb_value_bits 32 either: the post-smoother is the polynomial of fl32(A) and forms b - fl32(A) x itself)
+  // (cycle_bits 32 keeps it: every operator of that cycle is a float plane, fl32(A P) among them)
+  if ((G->cheb_value_bits != 32 || G->cycle_bits == 32) &&
+      ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
+    ISPH_CHECK(mat_from_device_csr(ctx, AP.n, AP.m, AP.rp.p, AP.ci.p, AP.v.p, AP.nnz, &L->APm, /*rows_sorted=*/true));
+    L->APm->local = true;
+  }
+  if (G->held) {
+    // the pattern of A P stays; so does the coarse operator in the row order of its SELL image (columns ascending)
+    L->AP.n = AP.n; L->AP.m = AP.m; L->AP.nnz = AP.nnz;
+    dev_move(L->AP.rp, AP.rp); dev_move(L->AP.ci, AP.ci);
+    Lc->A.release();
+    ISPH_CHECK(amg_csr_from_sell(ctx, Lc->Aown->S, Lc->A, S.tmp));
+  }
+  AP.release();
+  if (X.extended) {   // the coarse operator exchanges with the same peers (lists: amg_extend_pack / amg_extend_finish)
+    ISPH_CHECK(isph_mat_set_halo(ctx, Lc->Aown, H.npeers, H.peer.data(), X.cs_ptr.data(), X.cs_idx.empty() ? nullptr : X.cs_idx.data(),
+                                 X.cr_ptr.data()));
+    Lc->Aown->aux = true;
+  }
+  L->Pm->local = true;
+  if (!X.extended) Lc->Aown->local = true;
+  Lc->Am = Lc->Aown;
+  return ISPH_SUCCESS;
+}
+
+// One step of the coarsening loop on the last level of G: agree to go on, aggregate, agree to stop or to pass the level on
+// unchanged, estimate, prolongator, extension, operators.  AMG_STEP_FAILED: this rank failed after the step's last
+// consensus (rc); on more than one rank it goes on to the next step, whose first consensus ends the loop on all ranks.
+enum AmgStep { AMG_STEP_LEVEL, AMG_STEP_STOP, AMG_STEP_FAILED };
+inline AmgStep amg_coarsen_step(isph_ctx *ctx, isph_amg *G, const isph_amg_params *prm, AmgSetup &S, int &rc) {
+  const bool dist = G->dist != 0;
+  AmgLevel *L = G->L.back();
+  const int n = L->A.n;
+  // go on while any rank is above coarse_max (and none has failed)
+  double more = rc == ISPH_SUCCESS && n > prm->coarse_max ? 1.0 : 0.0;
+  if (!comm_consensus(ctx, dist, "AMG", kAmgNoConsensus, &more, 1, rc) || more == 0.0) return AMG_STEP_STOP;
+  rc = S.dg.reserve((size_t)(n > 0 ? n : 1));
+  int nagg = 0;
+  if (rc == ISPH_SUCCESS && n > 0) {
+    if (prm->theta != 0.0)
+      hipLaunchKernelGGL(k_amg_diag, dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, (const rp_t *)L->A.rp.p,
+                         (const int *)L->A.ci.p, (const double *)L->A.v.p, S.dg.p);
+    const bool use_prep = S.prep0 && L == G->L[0];
+    rc = amg_aggregate(ctx, L, S.dg.p, S.rho.p, prm->theta, S.tmp, &nagg, use_prep ? S.sc0.p : nullptr, use_prep ? S.key0.p : nullptr);
+    if (use_prep) { S.sc0.release(); S.key0.release(); }
+  }
+  // no coarsening, or a coarse space too small to carry anything but the null vector: stop here -- across ranks, when no
+  // rank can go on; a rank that cannot while others can passes its level on unchanged (P = I)
+  const bool cannot = rc != ISPH_SUCCESS || nagg < 8 || nagg >= n;
+  double any_can = cannot ? 0.0 : 1.0;
+  const bool ok = comm_consensus(ctx, dist, "AMG", kAmgNoConsensus, &any_can, 1, rc);
+  if (!ok || any_can == 0.0) {
+    L->agg.release();
+    L->path[AMG_PATH_MIS_ROUNDS] = L->path[AMG_PATH_MIS_LIST_ROUNDS] = L->path[AMG_PATH_PREP] = 0;
+    return AMG_STEP_STOP;
+  }
+  const bool identity = cannot;
+  // eig_type 1: the damping is omega / lambda of this level (dist: all ranks are here together and none has failed;
+  // a rank that passes its level on unchanged still takes part in the collective estimate)
+  if (G->eig_type == 1) rc = amg_level_estimate(ctx, G, L, G->nlev - 1, dist);
+  AmgLevelPtr Lc(new AmgLevel(), amg_level_destroy);
+  if (rc == ISPH_SUCCESS && identity) rc = amg_identity_prolongator(ctx, L, Lc->nv);
+  else if (rc == ISPH_SUCCESS) rc = amg_prolongator(ctx, L, S.dg.p, S.rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, S.tmp, S.derr.p,
+                                                    G->eig_type == 1 ? L->eig.lambda_used : 0.0, G->held != 0);
+  AmgExtension X;
+  if (dist && !amg_extend_prolongator(ctx, L, S, X, rc)) return AMG_STEP_STOP;
+  if (rc == ISPH_SUCCESS) rc = amg_level_operators(ctx, G, L, Lc.get(), X, S);
+  if (rc != ISPH_SUCCESS) return AMG_STEP_FAILED;
+  G->L.push_back(Lc.release());
+  ++G->nlev;
+  return AMG_STEP_LEVEL;
+}
+
+inline int amg_create(isph_ctx *ctx, const isph_mat *Am, const isph_amg_params *prm, const double *nullvec_dev,
+                      isph_amg **out) {
+  isph_amg *G = nullptr;
+  ISPH_CHECK(amg_new(prm, nullvec_dev != nullptr, &G));
+  AmgSetup S;
+  int rc = amg_fine_level(ctx, G, Am, prm, nullvec_dev, S);
+  const bool dist = comm_active(ctx) && ctx->nranks > 1;
   G->dist = dist ? 1 : 0;
   // isph_ctx_hold_pattern, one rank: the levels keep what amg_refactor needs (AmgLevel); off: nothing below changes
   G->held = ctx->pattern_hold && !dist && !mat_has_halo(Am);
   while ((dist || rc == ISPH_SUCCESS) && G->nlev < prm->max_levels) {
-    AmgLevel *L = G->L.back();
-    const int n = L->A.n;
-    if (dist) {   // go on while any rank is above coarse_max (and none has failed)
-      double h[2] = {rc == ISPH_SUCCESS && n > prm->coarse_max ? 1.0 : 0.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
-      if (h[1] != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); break; }
-      if (h[0] == 0.0) break;
-    } else if (n <= prm->coarse_max) break;
-    rc = dg.reserve((size_t)(n > 0 ? n : 1));
-    if (rc != ISPH_SUCCESS && !dist) break;
-    int nagg = 0;
-    if (rc == ISPH_SUCCESS && n > 0) {
-      if (prm->theta != 0.0)
-        hipLaunchKernelGGL(k_amg_diag, dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, (const rp_t *)L->A.rp.p,
-                           (const int *)L->A.ci.p, (const double *)L->A.v.p, dg.p);
-      const bool use_prep = prep0 && L == L0;
-      rc = amg_aggregate(ctx, L, dg.p, rho.p, prm->theta, tmp, &nagg, use_prep ? sc0.p : nullptr, use_prep ? key0.p : nullptr);
-      if (use_prep) { sc0.release(); key0.release(); }
-    }
-    if (rc != ISPH_SUCCESS && !dist) break;
-    // no coarsening, or a coarse space too small to carry anything but the null vector: stop here
-    bool stop = rc != ISPH_SUCCESS || nagg < 8 || nagg >= n;
-    bool identity = false;
-    if (dist) {   // ... when no rank can go on; a rank that cannot while others can passes its level on unchanged (P = I)
-      double h[2] = {stop ? 0.0 : 1.0, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); break; }
-      if (h[1] != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
-      identity = stop && h[0] != 0.0 && rc == ISPH_SUCCESS;
-      stop = h[0] == 0.0 || rc != ISPH_SUCCESS;
-    }
-    if (stop) { L->agg.release(); L->path[AMG_PATH_MIS_ROUNDS] = L->path[AMG_PATH_MIS_LIST_ROUNDS] = L->path[AMG_PATH_PREP] = 0; break; }
-    // eig_type 1: the damping is omega / lambda of this level (dist: all ranks are here together and none has failed;
-    // a rank that passes its level on unchanged still takes part in the collective estimate)
-    if (G->eig_type == 1) rc = amg_level_estimate(ctx, G, L, G->nlev - 1, dist);
-    AmgLevel *Lc = new AmgLevel();
-    if (rc == ISPH_SUCCESS && identity) { nagg = n; rc = amg_identity_prolongator(ctx, L, Lc->nv); }
-    else if (rc == ISPH_SUCCESS) rc = amg_prolongator(ctx, L, dg.p, rho.p, prm->theta == 0.0, nagg, prm->omega, Lc->nv, tmp, derr.p,
-                              G->eig_type == 1 ? L->eig.lambda_used : 0.0, G->held != 0);
-    DCsr AP, Pext;
-    DCsr &R = L->R;
-    const isph_halo &H = L->Am->halo;
-    std::vector<int> cs_ptr, cs_idx, cr_ptr;
-    bool extended = false;
-    if (dist) {
-      // the P rows behind A's ghost columns (amg_extend_pack / amg_extend_finish); K is agreed first, by all ranks
-      DevTmp<int> kmax;
-      int hk = 0;
-      if (rc == ISPH_SUCCESS) rc = kmax.reserve(1);
-      if (rc == ISPH_SUCCESS && hipMemsetAsync(kmax.p, 0, sizeof(int), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-      if (rc == ISPH_SUCCESS && H.nsend > 0)
-        hipLaunchKernelGGL(k_amg_send_rowmax, dim3((H.nsend + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, H.nsend,
-                           (const int *)H.send_idx.p, (const rp_t *)L->P.rp.p, kmax.p);
-      if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, kmax.p, &hk);
-      double h[2] = {(double)hk, rc == ISPH_SUCCESS ? 0.0 : 1.0};
-      if (comm_host_allreduce(ctx, h, 2, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
-      if (h[1] != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
-      AmgExtendState est;
-      const int Kx = std::max((int)h[0], 1);
-      // (a rank without ghost columns of its own still owes its neighbours their rows)
-      if (H.npeers > 0) rc = amg_extend_pack(ctx, H, L->P, Kx, est, cs_ptr, cs_idx, tmp);
-      double h2 = rc == ISPH_SUCCESS ? 0.0 : 1.0;   // nobody enters the exchange unless everybody can
-      if (comm_host_allreduce(ctx, &h2, 1, 1) != ISPH_SUCCESS) { rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
-      if (h2 != 0.0) { if (rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__); amg_level_destroy(Lc); break; }
-      if (H.npeers > 0) {
-        rc = amg_extend_finish(ctx, H, L->P, Kx, est, Pext, cr_ptr, tmp);
-        extended = rc == ISPH_SUCCESS;
-      }
-    }
-    if (rc == ISPH_SUCCESS) rc = amg_transpose(ctx, L->P, R, tmp);
-    if (rc == ISPH_SUCCESS && G->held) rc = amg_transpose_map(ctx, L);
-    if (rc == ISPH_SUCCESS) rc = amg_spgemm_ap(ctx, L->A, extended ? Pext : L->P, AP, tmp, derr.p, &L->path[AMG_PATH_AP]);
-    // held: the kept rows of A P must ascend; the table kernels (stages 3-5) leave them in table order
-    if (rc == ISPH_SUCCESS && G->held && L->path[AMG_PATH_AP] >= 3) rc = amg_sort_rows(ctx, AP, tmp);
-    if (rc == ISPH_SUCCESS) {
-      L->path[AMG_PATH_GALERKIN] = AP.m <= kGalerkinTable ? 1 : 2;   // k_spgemm's ycols <= TABLE: direct-addressed / open addressing
-      rc = amg_spgemm_t<kGalerkinTable, 64>(ctx, R, AP, Lc->A, tmp, derr.p);
-    }
-    Pext.release();
-    int herr = 0;
-    if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr.p, &herr);
-    if (rc == ISPH_SUCCESS && (herr & 1)) rc = fail("AMG: a row touches more than 512 aggregates", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS && (herr & 2)) rc = fail("AMG: coarse operator row too dense for the SpGEMM table", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS) rc = mat_from_device_csr(ctx, L->P.n, L->P.m, L->P.rp.p, L->P.ci.p, L->P.v.p, L->P.nnz, &L->Pm, /*rows_sorted=*/true);
-    if (rc == ISPH_SUCCESS) rc = mat_from_device_csr(ctx, Lc->A.n, Lc->A.m, Lc->A.rp.p, Lc->A.ci.p, Lc->A.v.p, Lc->A.nnz, &Lc->Aown);
-    // without ghost columns A (x + P e) = A x + (A P) e: the cycle updates the residual with the product already at hand
-    // (a fifth of A's entries) instead of a second sweep over A
-    // (not on a rank that sends to neighbours: the product it saves is also this rank's part of their exchange)
-    // (not with cheb_value_bits 32 either: the post-smoother is the polynomial of fl32(A) and forms b - fl32(A) x itself)
-    // (cycle_bits 32 keeps it: every operator of that cycle is a float plane, fl32(A P) among them)
-    if (rc == ISPH_SUCCESS && (G->cheb_value_bits != 32 || G->cycle_bits == 32) &&
-        ((L->Am->S.ncol == L->Am->S.nrow && L->Am->halo.nsend == 0) || L->Am->local)) {
-      rc = mat_from_device_csr(ctx, AP.n, AP.m, AP.rp.p, AP.ci.p, AP.v.p, AP.nnz, &L->APm, /*rows_sorted=*/true);
-      if (rc == ISPH_SUCCESS) L->APm->local = true;
-    }
-    if (rc == ISPH_SUCCESS && G->held) {
-      // the pattern of A P stays; so does the coarse operator in the row order of its SELL image (columns ascending)
-      L->AP.n = AP.n; L->AP.m = AP.m; L->AP.nnz = AP.nnz;
-      dev_move(L->AP.rp, AP.rp); dev_move(L->AP.ci, AP.ci);
-      Lc->A.release();
-      rc = amg_csr_from_sell(ctx, Lc->Aown->S, Lc->A, tmp);
-    }
-    AP.release();
-    if (rc == ISPH_SUCCESS && extended) {   // the coarse operator exchanges with the same peers (lists: amg_extend_pack / amg_extend_finish)
-      rc = isph_mat_set_halo(ctx, Lc->Aown, H.npeers, H.peer.data(), cs_ptr.data(), cs_idx.empty() ? nullptr : cs_idx.data(), cr_ptr.data());
-      if (rc == ISPH_SUCCESS) Lc->Aown->aux = true;
-    }
-    if (rc != ISPH_SUCCESS) { amg_level_destroy(Lc); if (dist) continue; break; }   // dist: the next consensus ends the loop on all ranks
-    L->Pm->local = true;
-    if (!extended) Lc->Aown->local = true;
-    Lc->Am = Lc->Aown;
-    G->L.push_back(Lc);
-    ++G->nlev;
+    const AmgStep step = amg_coarsen_step(ctx, G, prm, S, rc);
+    if (step == AMG_STEP_STOP || (step == AMG_STEP_FAILED && !dist)) break;
   }
-  // the fine-level CSR copy only serves the set-up (the cycle runs on the SELL matrix): 12 B per entry go back to the
-  // pool before the smoother is built; isph_prec_amg_export rebuilds it on demand
-  if (G->nlev > 1) { L0->A.ci.release(); L0->A.v.release(); L0->A.rp.release(); }
-  // smoothers, work vectors, coarse solve
-  G->coarse_smooth = G->singular || G->L.back()->A.n > kAmgDenseMax;
-  int nc_off = 0, nc_glob = G->L.back()->A.n;
-  if (dist) {
-    // the coarsest operators of all ranks form ONE system (ML gathers it for its direct solver): every rank inverts it
-    std::vector<double> h((size_t)ctx->nranks + 1, 0.0);
-    h[(size_t)ctx->rank] = (double)G->L.back()->A.n;
-    h[(size_t)ctx->nranks] = rc == ISPH_SUCCESS ? 0.0 : 1.0;
-    if (comm_host_allreduce(ctx, h.data(), ctx->nranks + 1, 0) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
-    else if (h[(size_t)ctx->nranks] != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
-    double tot = 0.0;
-    for (int r = 0; r < ctx->nranks; ++r) { if (r == ctx->rank) nc_off = (int)tot; tot += h[(size_t)r]; }
-    nc_glob = tot > 2.0e9 ? 2000000000 : (int)tot;
-    G->coarse_smooth = G->singular || nc_glob > kAmgDenseMax;
-  }
+  amg_release_fine_csr(G);
+  // the coarse system: the coarsest operators of all ranks together (amg_coarse_inverse_dist), solved by the smoother when
+  // the null vector makes it singular or when it is too large for the dense inverse (no coarsening possible: isolated /
+  // Dirichlet rows dominate)
+  long long nc_off = 0, nc_all = 0;
+  comm_rank_offsets(ctx, dist, "AMG", kAmgNoConsensus, G->L.back()->A.n, &nc_off, &nc_all, rc);
+  const int nc_glob = nc_all > 2000000000LL ? 2000000000 : (int)nc_all;
+  G->coarse_smooth = G->singular || nc_glob > kAmgDenseMax;
   // eig_type 1: the coarsest level has no prolongator but its estimate serves the polynomial that "solves" it and
   // isph_prec_eig_estimate (dist: rc is agreed between the ranks here)
   if (G->eig_type == 1 && rc == ISPH_SUCCESS) rc = amg_level_estimate(ctx, G, G->L.back(), G->nlev - 1, dist);
-  rc = amg_smoothers(ctx, G, dist, derr.p, rc);
+  rc = amg_smoothers(ctx, G, dist, S.derr.p, rc);
   // cycle_bits 32: the float planes of P, P^T and A P (A_l's is the smoother's); rank-local, agreed on just below
   if (rc == ISPH_SUCCESS && G->cycle_bits == 32) rc = amg_float_planes(ctx, G);
-  if (dist) {   // the smoothers are built per rank: a failure there must keep every rank out of the collective steps below
-    double h = rc == ISPH_SUCCESS ? 0.0 : 1.0;
-    if (comm_host_allreduce(ctx, &h, 1, 1) != ISPH_SUCCESS) rc = fail("AMG: consensus between the ranks failed", __FILE__, __LINE__);
-    else if (h != 0.0 && rc == ISPH_SUCCESS) rc = fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
-  }
-  if (rc == ISPH_SUCCESS && !G->coarse_smooth && dist && G->nlev > 1) {
-    AmgLevel *L = G->L.back();
-    const int ncl = L->A.n, N = nc_glob;
-    G->nc = N; G->nc_off = nc_off; G->nc_loc = ncl;
-    const isph_halo &Hc = L->Am->halo;
-    DevTmp<double> gs, gr;
-    rc = G->cinv.reserve((size_t)2 * N * N + (size_t)N + 1);
-    if (rc == ISPH_SUCCESS) rc = G->bglob.reserve((size_t)std::max(N, 1));
-    if (rc == ISPH_SUCCESS) rc = gs.reserve((size_t)std::max(Hc.nsend, 1));
-    if (rc == ISPH_SUCCESS) rc = gr.reserve((size_t)std::max(Hc.nrecv, 1));
-    if (rc == ISPH_SUCCESS && hipMemsetAsync(G->cinv.p, 0, sizeof(double) * (size_t)2 * N * N, ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-    if (rc == ISPH_SUCCESS && Hc.nsend > 0)
-      hipLaunchKernelGGL(k_amg_gid, dim3((Hc.nsend + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, Hc.nsend, nc_off, (const int *)Hc.send_idx.p, gs.p);
-    if (rc == ISPH_SUCCESS) rc = comm_exchange(ctx, Hc, gs.p, gr.p, 1, false, ctx->stream);   // global numbers of the ghost columns
-    if (rc == ISPH_SUCCESS && ncl > 0)
-      hipLaunchKernelGGL(k_dense_from_csr_glob, dim3(ncl), dim3(kBlock), 0, ctx->stream, ncl, N, nc_off, (const rp_t *)L->A.rp.p,
-                         (const int *)L->A.ci.p, (const double *)L->A.v.p, (const double *)gr.p, G->cinv.p);
-    if (rc == ISPH_SUCCESS) rc = comm_allreduce(ctx, G->cinv.p, 2 * N * N, 0, ctx->stream);
-    if (rc == ISPH_SUCCESS && N > 0) {
-      rc = amg_dense_invert(ctx, G->cinv.p, N, derr.p);
-      int herr = 0;
-      if (rc == ISPH_SUCCESS) rc = amg_read_int(ctx, derr.p, &herr);
-      if (rc == ISPH_SUCCESS && (herr & 4)) rc = fail("AMG: coarsest operator is singular (pass the null vector)", __FILE__, __LINE__);
-    }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == ISPH_SUCCESS) rc = fail("AMG setup failed", __FILE__, __LINE__);   // gs, gr leave scope
-  } else if (rc == ISPH_SUCCESS && !G->coarse_smooth) {
-    rc = amg_coarse_inverse(ctx, G, derr.p);
-  }
+  // the smoothers are built per rank: a failure there must keep every rank out of the collective steps of the inverse
+  comm_consensus(ctx, dist, "AMG", kAmgNoConsensus, nullptr, 0, rc);
+  if (rc == ISPH_SUCCESS && !G->coarse_smooth)
+    rc = dist && G->nlev > 1 ? amg_coarse_inverse_dist(ctx, G, nc_glob, (int)nc_off, S.derr.p) : amg_coarse_inverse(ctx, G, S.derr.p);
   if (rc == ISPH_SUCCESS && (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess))
     rc = fail("AMG setup failed", __FILE__, __LINE__);
-  tmp.release(); derr.release(); dg.release();
   if (rc != ISPH_SUCCESS) { amg_destroy(G); return rc; }
   *out = G;
   return ISPH_SUCCESS;
@@ -2671,9 +2690,27 @@ inline int amg_refresh_check(isph_ctx *ctx, int *derr, int level, const char *wh
                                "couples what the hierarchy was not built for): rebuild", level, h[1], what);
     return fail(msg, __FILE__, __LINE__);
   }
-  if (h[0] & 1) return fail("AMG: a row touches more than 512 aggregates", __FILE__, __LINE__);
-  if (h[0] & 2) return fail("AMG: coarse operator row too dense for the SpGEMM table", __FILE__, __LINE__);
-  return ISPH_SUCCESS;
+  return amg_error_word(h[0]);
+}
+
+// ISPH_AMG_REFRESH_TWO_PASS: the values v of a kept pattern (rp, ci: n rows, nnz entries) from a pair of kernels that
+// counts a row's entries and then writes them in any column order -- count(cnt), the counts must fit the kept rows
+// (k_row_counts_fit), fill(tci, tcv) at the kept offsets, and every value goes to the slot of its column (k_match_columns)
+template <class COUNT, class FILL>
+inline int amg_refresh_two_pass(isph_ctx *ctx, int n, long long nnz, const rp_t *rp, const int *ci, double *v, int *derr, int level,
+                                const char *what, COUNT &&count, FILL &&fill) {
+  DevTmp<int> cnt, tci;
+  DevTmp<double> tcv;
+  ISPH_CHECK(cnt.reserve((size_t)n + 1));
+  ISPH_CHECK(tci.reserve((size_t)(nnz > 0 ? nnz : 1)));
+  ISPH_CHECK(tcv.reserve((size_t)(nnz > 0 ? nnz : 1)));
+  ISPH_CHECK(count(cnt.p));
+  hipLaunchKernelGGL(k_row_counts_fit, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, (const int *)cnt.p, rp, derr);
+  ISPH_CHECK(amg_refresh_check(ctx, derr, level, what));   // the fill pass only writes rows that fit
+  fill(tci.p, tcv.p);
+  hipLaunchKernelGGL(k_match_columns, dim3(amg_wave_grid(n)), dim3(256), 0, ctx->stream, n, rp, ci, (const int *)cnt.p,
+                     (const int *)tci.p, (const double *)tcv.p, v, derr);
+  return amg_refresh_check(ctx, derr, level, what);   // (synchronises: the temporaries leave scope)
 }
 
 // C.v = X * Y on the kept pattern of C (rows ascending)
@@ -2686,24 +2723,20 @@ inline int amg_spgemm_values(isph_ctx *ctx, const DCsr &X, const DCsr &Y, DCsr &
                        (const rp_t *)C.rp.p, (const int *)C.ci.p, C.v.p, derr);
     return amg_refresh_check(ctx, derr, level, what);
   }
-  DevTmp<int> cnt, tci;
-  DevTmp<double> tcv;
-  ISPH_CHECK(cnt.reserve((size_t)C.n + 1));
-  ISPH_CHECK(tci.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
-  ISPH_CHECK(tcv.reserve((size_t)(C.nnz > 0 ? C.nnz : 1)));
-  ISPH_CHECK_HIP(hipMemsetAsync(cnt.p, 0, sizeof(int) * ((size_t)C.n + 1), ctx->stream));
-  hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, false>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
-                     (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
-                     cnt.p, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
-  hipLaunchKernelGGL(k_row_counts_fit, dim3((C.n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, C.n, (const int *)cnt.p,
-                     (const rp_t *)C.rp.p, derr);
-  ISPH_CHECK(amg_refresh_check(ctx, derr, level, what));   // the fill pass only writes rows that fit
-  hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, true>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
-                     (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
-                     (int *)nullptr, (const rp_t *)C.rp.p, tci.p, tcv.p, derr);
-  hipLaunchKernelGGL(k_match_columns, dim3(amg_wave_grid(C.n)), dim3(256), 0, ctx->stream, C.n, (const rp_t *)C.rp.p,
-                     (const int *)C.ci.p, (const int *)cnt.p, (const int *)tci.p, (const double *)tcv.p, C.v.p, derr);
-  return amg_refresh_check(ctx, derr, level, what);   // (synchronises: the temporaries leave scope)
+  return amg_refresh_two_pass(
+      ctx, C.n, C.nnz, C.rp.p, C.ci.p, C.v.p, derr, level, what,
+      [&](int *cnt) {
+        ISPH_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)C.n + 1), ctx->stream));
+        hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, false>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
+                           (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
+                           cnt, (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr);
+        return (int)ISPH_SUCCESS;
+      },
+      [&](int *tci, double *tcv) {
+        hipLaunchKernelGGL((k_spgemm<kGalerkinTable, 64, true>), dim3(C.n), dim3(64), 0, ctx->stream, X.n, Y.m, Y.n, (const rp_t *)X.rp.p,
+                           (const int *)X.ci.p, (const double *)X.v.p, (const rp_t *)Y.rp.p, (const int *)Y.ci.p, (const double *)Y.v.p,
+                           (int *)nullptr, (const rp_t *)C.rp.p, tci, tcv, derr);
+      });
 }
 
 // the values of a CSR with ascending rows into its SELL image (S.val reserved again and zeroed when it was given back)
@@ -2735,7 +2768,7 @@ inline int amg_refactor(isph_ctx *ctx, isph_amg *G, const isph_mat *Am) {
   const char *env = getenv("ISPH_AMG_REFRESH_TWO_PASS");
   const bool two_pass = env && env[0] == '1';
   DevTmp<char> tmp;
-  DevTmp<int> derr, cnt;
+  DevTmp<int> derr;
   DevTmp<double> dg, pt;
   DevTmp<unsigned long long> rho;
   ISPH_CHECK(derr.reserve(2));
@@ -2747,8 +2780,7 @@ inline int amg_refactor(isph_ctx *ctx, isph_amg *G, const isph_mat *Am) {
   struct GiveBack {
     isph_amg *G;
     ~GiveBack() {
-      AmgLevel *F = G->L[0];
-      if (G->nlev > 1) { F->A.ci.release(); F->A.v.release(); F->A.rp.release(); }
+      amg_release_fine_csr(G);
       for (AmgLevel *L : G->L) L->AP.v.release();
     }
   } give_back{G};
@@ -2779,22 +2811,19 @@ inline int amg_refactor(isph_ctx *ctx, isph_amg *G, const isph_mat *Am) {
     const double damp = lambda > 0.0 ? G->omega / lambda : rho_h > 0.0 ? G->omega / rho_h : 0.0;
     // P_l
     if (two_pass) {
-      ISPH_CHECK(cnt.reserve((size_t)n + 1));
-      hipLaunchKernelGGL((k_prolong<0>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
-                         (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, cnt.p,
-                         (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr.p);
-      hipLaunchKernelGGL(k_row_counts_fit, dim3(gt), dim3(kBlock), 0, ctx->stream, n, (const int *)cnt.p, (const rp_t *)P.rp.p, derr.p);
-      ISPH_CHECK(amg_refresh_check(ctx, derr.p, l, "P"));   // the fill pass only writes rows that fit
-      DevTmp<int> tci;
-      DevTmp<double> tcv;
-      ISPH_CHECK(tci.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
-      ISPH_CHECK(tcv.reserve((size_t)(P.nnz > 0 ? P.nnz : 1)));
-      hipLaunchKernelGGL((k_prolong<1>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
-                         (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, (int *)nullptr,
-                         (const rp_t *)P.rp.p, tci.p, tcv.p, derr.p);
-      hipLaunchKernelGGL(k_match_columns, dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)P.rp.p, (const int *)P.ci.p,
-                         (const int *)cnt.p, (const int *)tci.p, (const double *)tcv.p, P.v.p, derr.p);
-      ISPH_CHECK(amg_refresh_check(ctx, derr.p, l, "P"));   // (synchronises: the temporaries leave scope)
+      ISPH_CHECK(amg_refresh_two_pass(
+          ctx, n, P.nnz, P.rp.p, P.ci.p, P.v.p, derr.p, l, "P",
+          [&](int *cnt) {
+            hipLaunchKernelGGL((k_prolong<0>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                               (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, cnt,
+                               (const rp_t *)nullptr, (int *)nullptr, (double *)nullptr, derr.p);
+            return (int)ISPH_SUCCESS;
+          },
+          [&](int *tci, double *tcv) {
+            hipLaunchKernelGGL((k_prolong<1>), dim3(gw), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p, (const int *)A.ci.p,
+                               (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p, damp, (int *)nullptr,
+                               (const rp_t *)P.rp.p, tci, tcv, derr.p);
+          }));
     } else if (L->path[AMG_PATH_PROLONG] == 16) {
       hipLaunchKernelGGL((k_prolong_values<16>), dim3((n + 15) / 16), dim3(256), 0, ctx->stream, n, (const rp_t *)A.rp.p,
                          (const int *)A.ci.p, (const double *)A.v.p, (const double *)dg.p, (const int *)L->agg.p, (const double *)pt.p,
@@ -2818,7 +2847,7 @@ inline int amg_refactor(isph_ctx *ctx, isph_amg *G, const isph_mat *Am) {
     ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     AP.v.release();
   }
-  if (G->nlev > 1) { L0->A.ci.release(); L0->A.v.release(); L0->A.rp.release(); }   // before the smoothers, as in amg_create
+  amg_release_fine_csr(G);   // before the smoothers, as in amg_create
   // the smoothers: polynomials and Gauss-Seidel streams are made again, a block ILU stream is refactored (amg_ilu_smoother)
   for (int l = 0; l < G->nlev; ++l) {
     AmgLevel *L = G->L[(size_t)l];

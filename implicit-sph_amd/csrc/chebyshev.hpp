@@ -528,7 +528,7 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
   const char *env = getenv("ISPH_CHEB_UNFUSED");
   C->unfused = env && env[0] == '1';
   DevTmp<unsigned long long> flag;
-  double h[2] = {0.0, prior_failure ? 1.0 : 0.0};   // rho, failure
+  double rho = 0.0;
   if (!prior_failure) {
     const size_t m = (size_t)(S.nrow > 0 ? S.nrow : 1) + 64;
     rc = flag.reserve(3);
@@ -562,16 +562,14 @@ inline int cheb_setup(isph_ctx *ctx, const isph_mat *A, int degree, double ratio
       rc = fail("Chebyshev: a matrix value exceeds the range of single precision (value_bits = 32 rounds the values to float)", __FILE__, __LINE__);
     if (rc == ISPH_SUCCESS && hb[1] != 0ull)
       rc = fail("Chebyshev: the matrix has a zero diagonal entry (the polynomial acts on D^-1 A)", __FILE__, __LINE__);
-    memcpy(&h[0], &hb[0], sizeof(double));
-    if (rc != ISPH_SUCCESS) h[1] = 1.0;
+    memcpy(&rho, &hb[0], sizeof(double));
   }
-  if (collective) {
-    if (comm_host_allreduce(ctx, h, 2, /*max*/ 1) != ISPH_SUCCESS) { if (rc == ISPH_SUCCESS) rc = fail("Chebyshev: the all-reduce of rho failed", __FILE__, __LINE__); }
-    else if (h[1] != 0.0 && rc == ISPH_SUCCESS) rc = fail("Chebyshev: set-up failed on another rank", __FILE__, __LINE__);
-  }
-  if (rc != ISPH_SUCCESS || prior_failure) { cheb_destroy(C); return rc != ISPH_SUCCESS ? rc : ISPH_FAILURE; }
-  C->rho = h[0];
-  C->lambda = lambda_max > 0.0 ? lambda_max : h[0];
+  if (prior_failure) rc = ISPH_FAILURE;   // what this rank brings to the vote
+  // (a rank that has failed keeps its message whatever becomes of the all-reduce)
+  comm_consensus(ctx, collective, "Chebyshev", rc == ISPH_SUCCESS ? "Chebyshev: the all-reduce of rho failed" : nullptr, &rho, 1, rc);
+  if (rc != ISPH_SUCCESS) { cheb_destroy(C); return rc; }
+  C->rho = rho;
+  C->lambda = lambda_max > 0.0 ? lambda_max : rho;
   if (eig_type == 1 && !(lambda_max > 0.0)) {
     // (every rank is here or none: a failure above has been all-reduced)
     EigResult e;

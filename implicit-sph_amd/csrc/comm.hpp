@@ -72,6 +72,54 @@ inline int comm_host_allreduce(isph_ctx *ctx, double *h, int count, int op) {
   return ISPH_SUCCESS;
 }
 
+// ---- a set-up that several ranks go through together ------------------------------------------------------------------
+// A rank that fails on its own must not leave: it carries its rc to the next of these calls, which every rank makes at
+// the same step, and there all ranks fail together.  `who` is the prefix of the caller's messages ("AMG", "Chebyshev").
+inline int comm_failed_elsewhere(const char *who) {
+  char msg[96];
+  snprintf(msg, sizeof(msg), "%s: set-up failed on another rank", who);
+  return fail(msg, __FILE__, __LINE__);
+}
+
+// The consensus: vals[0 .. nvals) (nvals <= 3) and a failure flag -- rc so far -- are all-reduced by max and the outcome
+// is folded into rc.  A rank that failed keeps its own message, one that did not while another did fails with
+// comm_failed_elsewhere, and when the all-reduce itself fails rc is `broken`, the caller's message for that (NULL, which
+// only a rank that has failed may pass: its rc stands).  !dist (one rank): nothing to do.  Returns whether all ranks may go on.
+inline bool comm_consensus(isph_ctx *ctx, bool dist, const char *who, const char *broken, double *vals, int nvals, int &rc) {
+  if (!dist) return rc == ISPH_SUCCESS;
+  double h[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int i = 0; i < nvals; ++i) h[i] = vals[i];
+  h[nvals] = rc == ISPH_SUCCESS ? 0.0 : 1.0;
+  if (comm_host_allreduce(ctx, h, nvals + 1, /*max*/ 1) != ISPH_SUCCESS) {
+    if (broken) rc = fail(broken, __FILE__, __LINE__);
+    return false;
+  }
+  for (int i = 0; i < nvals; ++i) vals[i] = h[i];
+  if (h[nvals] != 0.0 && rc == ISPH_SUCCESS) rc = comm_failed_elsewhere(who);
+  return rc == ISPH_SUCCESS;
+}
+
+// The rows of all ranks in rank order, n_own of them here: *offset of this rank's first row and the *total, from one sum
+// all-reduce of nranks + 1 doubles (every rank's count in its own slot, the failure flag behind them); rc as in
+// comm_consensus.  !dist: offset 0, total n_own.
+inline bool comm_rank_offsets(isph_ctx *ctx, bool dist, const char *who, const char *broken, long long n_own, long long *offset,
+                              long long *total, int &rc) {
+  *offset = 0; *total = n_own;
+  if (!dist) return rc == ISPH_SUCCESS;
+  const size_t nr = (size_t)ctx->nranks;
+  std::vector<double> h(nr + 1, 0.0);
+  h[(size_t)ctx->rank] = (double)n_own;
+  h[nr] = rc == ISPH_SUCCESS ? 0.0 : 1.0;
+  if (comm_host_allreduce(ctx, h.data(), ctx->nranks + 1, /*sum*/ 0) != ISPH_SUCCESS) {
+    rc = fail(broken, __FILE__, __LINE__);
+    return false;
+  }
+  *total = 0;
+  for (size_t r = 0; r < nr; ++r) { if (r == (size_t)ctx->rank) *offset = *total; *total += (long long)h[r]; }
+  if (h[nr] != 0.0 && rc == ISPH_SUCCESS) rc = comm_failed_elsewhere(who);
+  return rc == ISPH_SUCCESS;
+}
+
 // Point-to-point exchange with every peer of a halo plan, `ncomp` doubles per listed entry, on stream s.
 // reverse = false: send ranges -> peers, recv ranges <- peers (owners to ghosts); true: the roles swapped (ghost
 // contributions back to their owners, the "Add" of the overlapped Schwarz).

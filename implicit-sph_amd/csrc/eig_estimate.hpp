@@ -235,17 +235,9 @@ inline int eig_estimate(isph_ctx *ctx, const isph_mat *A, const float *val32, co
   if (rc == ISPH_SUCCESS) rc = V.reserve((size_t)(iters + 1) * (size_t)ld);
   if (rc == ISPH_SUCCESS) rc = w.reserve((size_t)ld);
   long long offset = 0, nglob = n;
-  if (collective) {
-    std::vector<double> h((size_t)ctx->nranks + 1, 0.0);
-    h[(size_t)ctx->rank] = (double)n;
-    h[(size_t)ctx->nranks] = rc == ISPH_SUCCESS ? 0.0 : 1.0;
-    if (comm_host_allreduce(ctx, h.data(), ctx->nranks + 1, /*sum*/ 0) != ISPH_SUCCESS)
-      return fail("eigenvalue estimate: the all-reduce of the row counts failed", __FILE__, __LINE__);
-    if (h[(size_t)ctx->nranks] != 0.0) return rc != ISPH_SUCCESS ? rc : fail("eigenvalue estimate: set-up failed on another rank", __FILE__, __LINE__);
-    nglob = 0;
-    for (int r = 0; r < ctx->nranks; ++r) { if (r == ctx->rank) offset = nglob; nglob += (long long)h[(size_t)r]; }
-  }
-  if (rc != ISPH_SUCCESS) return rc;
+  if (!comm_rank_offsets(ctx, collective, "eigenvalue estimate", "eigenvalue estimate: the all-reduce of the row counts failed", n,
+                         &offset, &nglob, rc))
+    return rc;
   const int k = (long long)iters < nglob ? iters : (int)nglob;
   if (k <= 0) return ISPH_SUCCESS;   // no rows anywhere: rho stands
   const int *perm = (level == 0 && A->order && n > 0) ? (const int *)A->order->perm.p : nullptr;

@@ -1818,16 +1818,9 @@ int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params
     // ranks that disagree would wait for each other forever -- fail on every rank together instead.
     double h[3] = {rc == ISPH_SUCCESS ? 1.0 : 0.0, (rc == ISPH_SUCCESS && M->amg->nlev > 1) ? 1.0 : 0.0,
                    (rc == ISPH_SUCCESS && M->amg->coarse_smooth) ? 1.0 : 0.0};
-    DevTmp<double> d;
-    int rc2 = d.reserve(3);
-    if (rc2 == ISPH_SUCCESS && hipMemcpyAsync(d.p, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc2 = ISPH_FAILURE;
-    if (rc2 == ISPH_SUCCESS) rc2 = allreduce_inplace(ctx, d.p, 3);
-    if (rc2 == ISPH_SUCCESS && (hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                                hipStreamSynchronize(ctx->stream) != hipSuccess)) rc2 = ISPH_FAILURE;
-    d.release();
     const double nr = (double)ctx->nranks;
-    if (rc2 != ISPH_SUCCESS) rc = fail("AMG: set-up consensus between the ranks failed", __FILE__, __LINE__);
-    else if (h[0] != nr) rc = rc != ISPH_SUCCESS ? rc : fail("AMG: set-up failed on another rank", __FILE__, __LINE__);
+    if (comm_host_allreduce(ctx, h, 3, /*sum*/ 0) != ISPH_SUCCESS) rc = fail("AMG: set-up consensus between the ranks failed", __FILE__, __LINE__);
+    else if (h[0] != nr) rc = rc != ISPH_SUCCESS ? rc : comm_failed_elsewhere("AMG");
     else if ((h[1] != 0.0 && h[1] != nr) || (h[1] == 0.0 && h[2] != 0.0 && h[2] != nr))
       rc = fail("AMG: the ranks built hierarchies of different depth; their fine-level halo exchanges would not match", __FILE__, __LINE__);
   }
