@@ -149,33 +149,3 @@ struct isph_mat {
   isph::DevBuf<unsigned> emap;
   long long n_updates = 0;  // isph_mat_update_values calls taken
 };
-
-struct isph_ilu;  // ilu.hpp
-struct isph_amg;  // amg.hpp
-struct isph_schwarz;  // schwarz.hpp
-struct isph_overlap;  // isph_capi.hip: overlap-1 Schwarz across ranks
-namespace isph {
-struct Cheb;  // chebyshev.hpp
-inline int prec_multi_single_env() {
-  const char *e = getenv("ISPH_PREC_MULTI_SINGLE");
-  return e && e[0] == '1';
-}
-}  // namespace isph
-
-struct isph_prec {
-  int type = 0;  // 0 none, 1 jacobi, 2 bjacobi-ilu<k> (block stream), 3 sa-amg, 4 additive Schwarz ILU(k) (schwarz.hpp),
-                 // 5 ILU(k) of the rank's rows + one layer of the neighbours' rows (isph_prec_create_overlap),
-                 // 6 Chebyshev polynomial in D^-1 A (chebyshev.hpp; applies the matrix it was built from: cheb_A must outlive it)
-  int n = 0;
-  isph::DevBuf<double> invdiag;
-  isph_ilu *ilu = nullptr;
-  isph_amg *amg = nullptr;
-  isph_schwarz *schwarz = nullptr;
-  isph_overlap *ovl = nullptr;
-  isph::Cheb *cheb = nullptr;
-  const isph_mat *cheb_A = nullptr;
-  isph::RowOrderPtr order;  // the numbering of the matrix it was built from (isph_prec_apply takes the caller's)
-  // ISPH_PREC_MULTI_SINGLE=1, read when the object is created: several vectors are applied one after the other whatever
-  // one-sweep form the type has (prec_apply_multi_dev) -- the cross-check and the timing baseline of those forms
-  int multi_single = isph::prec_multi_single_env();
-};

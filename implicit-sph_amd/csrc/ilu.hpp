@@ -1895,21 +1895,29 @@ __global__ __launch_bounds__(WAVES * 64) void k_ilu_solve_stream_multi(int n, in
   }
 }
 
-// z_k = U^-1 D^-1 L^-1 r_k for K = 2..4 vectors in one sweep of the factor stream (falls back to K sweeps otherwise)
-inline int ilu_apply(isph_ctx *ctx, const isph_ilu *F, const double *r, double *z, int part = 0, bool accumulate = false);
-inline int ilu_apply_multi(isph_ctx *ctx, const isph_ilu *F, int K, const double *const *rs, double *const *zs) {
-  ISPH_REQUIRE(F != nullptr, "ILU factor is NULL");
-  if (F->n == 0) return ISPH_SUCCESS;
-  constexpr int WV = 4;
-  const size_t lds = sizeof(double) * (size_t)(K + 1) * (size_t)F->B * WV;
-  // K sweeps when one sweep for all vectors does not fit the LDS this device gives a workgroup (asked, not assumed)
+// the LDS of one sweep for K vectors: K + 1 vectors of a block's rows for each of the workgroup's waves
+constexpr int kIluMultiWaves = 4;
+inline size_t ilu_multi_lds(const isph_ilu *F, int K) { return sizeof(double) * (size_t)(K + 1) * (size_t)F->B * kIluMultiWaves; }
+// whether K vectors share one sweep of the factor stream: 2..4 of them, and their LDS within what this device gives a
+// workgroup (asked, not assumed).  The one statement of the rule: ilu_apply_multi acts on it, isph_prec_multi_path reports it
+inline bool ilu_multi_shared(const isph_ilu *F, int K) {
   static const size_t lds_max = [] {
     int dev = 0, v = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
       return (size_t)64 * 1024;
     return (size_t)v;
   }();
-  if (K < 2 || K > 4 || lds > lds_max) {
+  return F && F->n > 0 && K >= 2 && K <= 4 && ilu_multi_lds(F, K) <= lds_max;
+}
+
+// z_k = U^-1 D^-1 L^-1 r_k for K = 2..4 vectors in one sweep of the factor stream (falls back to K sweeps otherwise)
+inline int ilu_apply(isph_ctx *ctx, const isph_ilu *F, const double *r, double *z, int part = 0, bool accumulate = false);
+inline int ilu_apply_multi(isph_ctx *ctx, const isph_ilu *F, int K, const double *const *rs, double *const *zs) {
+  ISPH_REQUIRE(F != nullptr, "ILU factor is NULL");
+  if (F->n == 0) return ISPH_SUCCESS;
+  constexpr int WV = kIluMultiWaves;
+  const size_t lds = ilu_multi_lds(F, K);
+  if (!ilu_multi_shared(F, K)) {
     for (int k = 0; k < K; ++k) ISPH_CHECK(ilu_apply(ctx, F, rs[k], zs[k]));
     return ISPH_SUCCESS;
   }

@@ -14,166 +14,12 @@
 #include "chebyshev.hpp"
 #include "amg.hpp"
 #include "schwarz.hpp"
+#include "prec.hpp"
 #include "gcrodr.hpp"
 #include "ingress.hpp"
 
 namespace isph {
 thread_local std::string g_last_error;
-
-}  // namespace isph (reopened below)
-
-// Ifpack_AdditiveSchwarz<ILU(k)> with "Overlap Level" 1 on more than one rank (precond_ifpack.h:43,60-74): the rank's
-// subdomain is its own rows plus the rows of its ghost columns (Ifpack_OverlappingRowMatrix); the extended matrix is
-// built by the caller (Epetra_Import of the rows; dist.extend_rows in the Python plumbing) and factored as one block by
-// the level-scheduled path of schwarz.hpp.  An application gathers the ghost part of r with the matrix' halo plan,
-// solves on the extended vector and -- combine mode Add, the wrapper's default -- sends the ghost part of the result
-// back to its owners, who add it; Zero keeps the owned part only (restricted additive Schwarz).
-struct isph_overlap {
-  int n = 0, next = 0, combine = 0;
-  isph_schwarz *inner = nullptr;
-  isph_halo H;
-  isph::DevBuf<double> rext, zext, sbuf, rbuf;
-};
-
-namespace isph {
-
-__global__ void k_scatter_add(int n, const int *__restrict__ idx, const double *__restrict__ v, double *__restrict__ z) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) z[idx[i]] += v[i];
-}
-
-inline void overlap_destroy(isph_overlap *O) {
-  if (!O) return;
-  if (O->inner) schwarz_destroy(O->inner);
-  O->H.send_idx.release();
-  O->rext.release(); O->zext.release(); O->sbuf.release(); O->rbuf.release();
-  delete O;
-}
-
-inline int overlap_exchange(isph_ctx *ctx, const isph_halo &H, const double *send, double *recv, bool reverse) {
-  // forward: send[send range p] -> peer p, recv[recv range p] <- peer p; reverse: the two roles swapped
-  return comm_exchange(ctx, H, send, recv, 1, reverse, ctx->stream);
-}
-
-inline int overlap_apply(isph_ctx *ctx, const isph_overlap *O, const double *r, double *z) {
-  const isph_halo &H = O->H;
-  const int n = O->n;
-  ISPH_CHECK_HIP(hipMemcpyAsync(O->rext.p, r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-  if (H.nsend > 0)
-    hipLaunchKernelGGL(k_gather, dim3(stream_grid(H.nsend)), dim3(kBlock), 0, ctx->stream, H.nsend, (const int *)H.send_idx.p, r,
-                       O->sbuf.p);
-  ISPH_CHECK(overlap_exchange(ctx, H, O->sbuf.p, O->rext.p + n, false));
-  ISPH_CHECK(schwarz_apply(ctx, O->inner, O->rext.p, O->zext.p));
-  ISPH_CHECK_HIP(hipMemcpyAsync(z, O->zext.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-  if (O->combine == 0 && H.npeers > 0) {  // Add: the neighbours' corrections of my rows come home (a rank may only send or only receive)
-    ISPH_CHECK(overlap_exchange(ctx, H, O->zext.p + n, O->rbuf.p, true));
-    for (int p = 0; p < H.npeers; ++p) {  // one launch per peer: a row can be in several peers' lists, never twice in one
-      const int s0 = H.send_ptr[(size_t)p], cnt = H.send_ptr[(size_t)p + 1] - s0;
-      if (cnt > 0)
-        hipLaunchKernelGGL(k_scatter_add, dim3(stream_grid(cnt)), dim3(kBlock), 0, ctx->stream, cnt, (const int *)H.send_idx.p + s0,
-                           (const double *)O->rbuf.p + s0, z);
-    }
-  }
-  ISPH_CHECK_HIP(hipGetLastError());
-  return ISPH_SUCCESS;
-}
-
-// The persistent triangular sweeps of the Schwarz path (schwarz.hpp k_gilu_solve_run) give up after a spin limit, store
-// zeros and raise a word that the application copies to S->h_tmo.  Called with the stream DRAINED at the end of every
-// solve / host-side application: a raised word fails the call -- on every rank together (one small max-reduction per
-// solve; a rank that returned alone would leave the others waiting in their next collective) -- and is cleared, so one
-// spurious time-out (a shared device, a debugger) does not poison the object.  A silently zeroed M^-1 r is never
-// reported as a converged solve.
-int prec_health(isph_ctx *ctx, const isph_prec *M) {
-  if (!M || (M->type != 4 && M->type != 5)) return ISPH_SUCCESS;
-  const isph_schwarz *S = M->type == 4 ? M->schwarz : (M->ovl ? M->ovl->inner : nullptr);
-  double bad = 0.0;
-  if (S && S->syncfree && S->h_tmo && *S->h_tmo != 0) {
-    bad = 1.0;
-    *S->h_tmo = 0;
-    ISPH_CHECK_HIP(hipMemsetAsync(S->ctr.p + 3, 0, sizeof(int), ctx->stream));
-  }
-  if (comm_active(ctx) && ctx->nranks > 1) {
-    ISPH_CHECK(ensure_scalars(ctx));
-    double *d = ctx->dscal.p + SC_MISC + 30;
-    ISPH_CHECK_HIP(hipMemcpyAsync(d, &bad, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    ISPH_CHECK(comm_allreduce(ctx, d, 1, /*max*/ 1, ctx->stream));
-    ISPH_CHECK_HIP(hipMemcpyAsync(&bad, d, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  }
-  if (bad != 0.0)
-    return fail("Schwarz ILU sweep: a row waited for a dependency beyond the spin limit; the result of this call is not valid", __FILE__, __LINE__);
-  return ISPH_SUCCESS;
-}
-
-int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, double *z) {
-  ISPH_REQUIRE(M != nullptr, "preconditioner is NULL");
-  const int n = M->n;
-  ProfScope prof(ctx, PROF_PREC_APPLY);
-  if (M->type == 0) {
-    // identity: callers pass distinct buffers
-    if (r != z) ISPH_CHECK_HIP(hipMemcpyAsync(z, r, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-    return ISPH_SUCCESS;
-  }
-  if (M->type == 1) {
-    hipLaunchKernelGGL(k_mul_elem, dim3(stream_grid(n)), dim3(kBlock), 0, ctx->stream, n, r, M->invdiag.p, z);
-    return ISPH_SUCCESS;
-  }
-  if (M->type == 3) return amg_apply(ctx, M->amg, r, z);
-  if (M->type == 4) return schwarz_apply(ctx, M->schwarz, r, z);
-  if (M->type == 5) return overlap_apply(ctx, M->ovl, r, z);
-  if (M->type == 6) return cheb_apply(ctx, M->cheb_A, M->cheb, r, z, /*zero_guess=*/true);
-  return ilu_apply(ctx, M->ilu, r, z);
-}
-
-// whether K vectors share the sweeps of M (isph_prec_multi_path).  Block ILU(k): 2..4 vectors in one sweep of the factor
-// stream (ilu_apply_multi decides on the LDS a workgroup gets; this repeats its rule).  The Chebyshev polynomial and the
-// fp64 V cycle of the Chebyshev-smoothed AMG: any K >= 2, in groups of up to kPrecMultiMax.
-constexpr int kPrecMultiMax = 4;
-bool prec_multi_shared(const isph_prec *M, int K) {
-  if (!M || K < 2 || M->multi_single) return false;
-  if (M->type == 2 && M->ilu) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || v <= 0)
-      v = 64 * 1024;
-    return K <= 4 && M->ilu->n > 0 && sizeof(double) * (size_t)(K + 1) * (size_t)M->ilu->B * 4 <= (size_t)v;
-  }
-  if (M->type == 6) return cheb_multi_ok(M->cheb_A, M->cheb);
-  if (M->type == 3) return amg_multi_ok(M->amg);
-  return false;
-}
-
-// K applications of one preconditioner: block ILU(k) sweeps its factor stream once for all vectors, the Chebyshev
-// polynomial and the Chebyshev-smoothed fp64 V cycle sweep every operator once per group of up to four vectors
-// (cheb_apply_multi, amg_apply_multi).  Everything else -- and everything under ISPH_PREC_MULTI_SINGLE=1 -- applies the
-// vectors one after the other; the bits are the same either way.
-int prec_apply_multi_dev(isph_ctx *ctx, const isph_prec *M, int K, const double *const *rs, double *const *zs) {
-  ISPH_REQUIRE(M != nullptr, "preconditioner is NULL");
-  if (!M->multi_single && M->type == 2 && M->ilu) return ilu_apply_multi(ctx, M->ilu, K, rs, zs);
-  if ((M->type == 6 || M->type == 3) && prec_multi_shared(M, K)) {
-    ProfScope prof(ctx, PROF_PREC_APPLY);
-    for (int k0 = 0; k0 < K; k0 += kPrecMultiMax) {
-      const int g = std::min(kPrecMultiMax, K - k0);
-      if (g == 1) ISPH_CHECK(M->type == 6 ? cheb_apply(ctx, M->cheb_A, M->cheb, rs[k0], zs[k0], /*zero_guess=*/true)
-                                          : amg_apply(ctx, M->amg, rs[k0], zs[k0]));
-      else if (M->type == 6) ISPH_CHECK(cheb_apply_multi(ctx, M->cheb_A, M->cheb, g, rs + k0, zs + k0, /*zero_guess=*/true));
-      else ISPH_CHECK(amg_apply_multi(ctx, M->amg, g, rs + k0, zs + k0));
-    }
-    return ISPH_SUCCESS;
-  }
-  for (int k = 0; k < K; ++k) ISPH_CHECK(prec_apply_dev(ctx, M, rs[k], zs[k]));
-  return ISPH_SUCCESS;
-}
-
-// upload helper: returns device pointer (either the caller's or a staged copy)
-template <class T>
-int stage_in(isph_ctx *ctx, const T *src, size_t n, int on_device, DevBuf<T> &tmp, const T **out) {
-  if (on_device) { *out = src; return ISPH_SUCCESS; }
-  ISPH_REQUIRE(!is_device_pointer(src), "device pointer passed with on_device = 0");
-  ISPH_CHECK(tmp.reserve(n > 0 ? n : 1));
-  ISPH_CHECK_HIP(hipMemcpyAsync(tmp.p, src, sizeof(T) * n, hipMemcpyHostToDevice, ctx->stream));
-  *out = tmp.p;
-  return ISPH_SUCCESS;
-}
 
 int sell_finalize_offsets(isph_ctx *ctx, Sell &S) {
   // slice_off currently holds per-slice entry counts in [0,nslices)
@@ -354,9 +200,7 @@ struct OrderedAssembly {
     if (n == 0) return ISPH_SUCCESS;
     double *d = out;
     if (!on_device) ISPH_CHECK(alloc((size_t)lda * ncols, &d));
-    for (int c = 0; c < ncols; ++c)
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, n, (const int *)O->perm.p,
-                         internal + (size_t)c * n, d + (size_t)c * lda);
+    order_scatter(ctx, *O, n, ncols, internal, (size_t)n, d, (size_t)lda);
     if (!on_device) {
       // rows lda > n of a column are not the library's to write: copy column by column
       for (int c = 0; c < ncols; ++c)
@@ -376,8 +220,7 @@ int sell_permute(isph_ctx *ctx, const Sell &S0, const RowOrder &O, Sell &S) {
   ISPH_CHECK(S.slice_off.reserve((size_t)S.nslices + 1));
   if (n == 0) return ISPH_SUCCESS;
   const int grid = (n + kBlock - 1) / kBlock;
-  hipLaunchKernelGGL((k_perm_gather<int>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1, (const int *)O.perm.p,
-                     (const int *)S0.rowlen.p, S.rowlen.p);
+  order_gather(ctx, O, n, 1, (const int *)S0.rowlen.p, 0, S.rowlen.p, 0);
   hipLaunchKernelGGL(k_slicew_from_rowlen, dim3(grid), dim3(kBlock), 0, ctx->stream, n, (const int *)S.rowlen.p, S.slice_off.p);
   ISPH_CHECK(sell_finalize_offsets(ctx, S));
   const int wmax = S.wmax;
@@ -821,23 +664,15 @@ int isph_mat_create_csr_coords_bjacobi(isph_ctx *ctx, int nrow, int ncol, const 
     ISPH_REQUIRE(run == (long long)rowptr[nrow], "row pointers and entry count disagree");
   }
   const std::vector<int> &bp = O->block_ptr;
-  int cap = 64;
-  for (size_t b = 0; b + 1 < bp.size(); ++b) cap = std::max(cap, bp[b + 1] - bp[b]);
-  cap = (cap + 63) / 64 * 64;
   IngressGather gat;
   gat.perm = hperm.data(); gat.src_rowptr = rowptr; gat.colren = O->iperm.p; gat.nren = nrow;
   isph_mat *A = nullptr;
-  isph_ilu *F = nullptr;
-  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rp2.data(), colidx, val, cap, &A, &F, (int)bp.size() - 1, bp.data(), &gat));
+  PrecNew M(nrow, PREC_BJACOBI_ILU);
+  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rp2.data(), colidx, val, ilu_block_cap(O->nblocks(), bp.data()), &A, &M->ilu,
+                                      O->nblocks(), bp.data(), &gat));
   A->order = O;
-  isph_prec *M = new isph_prec();
-  M->n = nrow;
-  M->type = 2;
-  M->ilu = F;
-  M->order = O;
   *Aout = A;
-  *Mout = M;
-  return ISPH_SUCCESS;
+  return M.finish(O, Mout);
 }
 
 int isph_mat_create_csr_blocks(isph_ctx *ctx, int nrow, int ncol, const int *rowptr, const int *colidx, const double *val,
@@ -846,36 +681,20 @@ int isph_mat_create_csr_blocks(isph_ctx *ctx, int nrow, int ncol, const int *row
   ISPH_REQUIRE(nrow >= 0 && ncol >= nrow, "need 0 <= nrow <= ncol");
   ISPH_REQUIRE(!is_device_pointer(block_ptr), "block_ptr must be a host array");
   ISPH_REQUIRE(block_ptr[0] == 0 && block_ptr[nblocks] == nrow, "subdomain table must run from 0 to the number of rows");
-  int cap = 64;
-  for (int b = 0; b < nblocks; ++b) cap = std::max(cap, block_ptr[b + 1] - block_ptr[b]);
-  cap = (cap + 63) / 64 * 64;
+  const int cap = ilu_block_cap(nblocks, block_ptr);
   ISPH_REQUIRE(cap <= 1024, "a subdomain of the block stream holds at most 1024 rows");
-  isph_mat *A = nullptr;
-  isph_ilu *F = nullptr;
-  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rowptr, colidx, val, cap, &A, &F, nblocks, block_ptr));
-  isph_prec *M = new isph_prec();
-  M->n = nrow;
-  M->type = 2;
-  M->ilu = F;
-  *Aout = A;
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(nrow, PREC_BJACOBI_ILU);
+  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rowptr, colidx, val, cap, Aout, &M->ilu, nblocks, block_ptr));
+  return M.finish(nullptr, Mout);  // a host CSR without coordinates stays in the caller's numbering
 }
 
 int isph_mat_create_csr_bjacobi(isph_ctx *ctx, int nrow, int ncol, const int *rowptr, const int *colidx, const double *val,
                                 int block_size, isph_mat **Aout, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && Aout && Mout && rowptr && colidx && val, "NULL argument");
   ISPH_REQUIRE(nrow >= 0 && ncol >= nrow, "need 0 <= nrow <= ncol");
-  isph_mat *A = nullptr;
-  isph_ilu *F = nullptr;
-  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rowptr, colidx, val, block_size, &A, &F));
-  isph_prec *M = new isph_prec();
-  M->n = nrow;
-  M->type = 2;
-  M->ilu = F;
-  *Aout = A;
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(nrow, PREC_BJACOBI_ILU);
+  ISPH_CHECK(csr_ingress_host_bjacobi(ctx, nrow, ncol, rowptr, colidx, val, block_size, Aout, &M->ilu));
+  return M.finish(nullptr, Mout);  // a host CSR without coordinates stays in the caller's numbering
 }
 
 int isph_mat_update_values(isph_ctx *ctx, isph_mat *A, const double *val, int on_device) {
@@ -1181,60 +1000,43 @@ void isph_mat_destroy(isph_mat *A) {
   delete A;
 }
 
+// y = A x on device vectors in the matrix' numbering.  Ghost columns without a halo plan: the caller supplied all ncol
+// entries (ghost values included) and the plain kernel reads them
+static int spmv_operand(isph_ctx *ctx, const isph_mat *A, bool ghosts_given, const double *x, double *y) {
+  if (!ghosts_given) return spmv_dev(ctx, A, x, y, nullptr);
+  const Sell &S = A->S;
+  int nbp = 0;
+  const int grid = spmv_grid(S.nslices, &nbp);
+  hipLaunchKernelGGL((k_sell_spmv<8, false, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices, nbp,
+                     S.slice_off.p, S.col.p, S.val.p, x, y, (const double *)nullptr, (double *)nullptr);
+  return ISPH_SUCCESS;
+}
+
 int isph_spmv(isph_ctx *ctx, const isph_mat *A, const double *x, double *y, int on_device) {
   ISPH_REQUIRE(ctx && A && x && y, "NULL argument");
   const Sell &S = A->S;
-  const size_t nx = (S.ncol > S.nrow && A->halo.npeers == 0) ? (size_t)S.ncol : (size_t)S.nrow;
-  if (A->order) {
-    // x and y are the caller's: x into the matrix' numbering (ghost entries, when the caller supplies them, in place),
-    // the product back out
-    DevTmp<double> xc, xi, yi;
-    const double *dxc = x;
-    if (!on_device) {
-      ISPH_CHECK(xc.reserve(nx));
-      ISPH_CHECK_HIP(hipMemcpyAsync(xc.p, x, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
-      dxc = xc.p;
-    }
+  const bool ghosts_given = S.ncol > S.nrow && A->halo.npeers == 0, ordered = (bool)A->order;
+  const size_t nx = ghosts_given ? (size_t)S.ncol : (size_t)S.nrow;
+  if (!ordered && on_device) return spmv_dev(ctx, A, x, y, nullptr);
+  // host operands are staged: a pool temporary beside the gathered copies of an ordered matrix (x and y are the caller's,
+  // in its numbering; ghost entries stay in place), the context's own vectors otherwise
+  DevTmp<double> xc, xi, yi;
+  if (!ordered) ISPH_CHECK(ctx->xdev.reserve((size_t)S.ncol));
+  if (!ordered) ISPH_CHECK(ctx->bdev.reserve((size_t)(S.nrow > 0 ? S.nrow : 1)));
+  const double *dx = nullptr;
+  ISPH_CHECK(stage_in(ctx, x, nx, on_device, ordered ? static_cast<DevBuf<double> &>(xc) : ctx->xdev, &dx));
+  double *dy = on_device ? y : ordered ? xc.p : ctx->bdev.p;  // the product on the device, the caller's numbering
+  if (ordered) {
     ISPH_CHECK(xi.reserve((size_t)S.ncol + 64));
     ISPH_CHECK(yi.reserve((size_t)S.nrow + 64));
-    hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid((long long)nx)), dim3(kBlock), 0, ctx->stream, (long long)nx, S.nrow, 1,
-                       (const int *)A->order->perm.p, dxc, xi.p);
-    if (S.ncol > S.nrow && A->halo.npeers == 0) {
-      int nbp = 0;
-      const int grid = spmv_grid(S.nslices, &nbp);
-      hipLaunchKernelGGL((k_sell_spmv<8, false, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices, nbp,
-                         S.slice_off.p, S.col.p, S.val.p, (const double *)xi.p, yi.p, (const double *)nullptr, (double *)nullptr);
-    } else {
-      ISPH_CHECK(spmv_dev(ctx, A, xi.p, yi.p, nullptr));
-    }
-    double *dy = y;
-    if (!on_device) { ISPH_CHECK(xc.reserve((size_t)S.nrow)); dy = xc.p; }
-    hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(S.nrow)), dim3(kBlock), 0, ctx->stream, S.nrow,
-                       (const int *)A->order->perm.p, (const double *)yi.p, dy);
-    if (!on_device) ISPH_CHECK_HIP(hipMemcpyAsync(y, dy, sizeof(double) * (size_t)S.nrow, hipMemcpyDeviceToHost, ctx->stream));
-    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // the temporaries go back to the pool
-    ISPH_CHECK_HIP(hipGetLastError());
-    return ISPH_SUCCESS;
-  }
-  if (on_device) {
-    ISPH_CHECK(spmv_dev(ctx, A, x, y, nullptr));
-    return ISPH_SUCCESS;
-  }
-  ISPH_CHECK(ctx->xdev.reserve((size_t)S.ncol));
-  ISPH_CHECK(ctx->bdev.reserve((size_t)(S.nrow > 0 ? S.nrow : 1)));
-  ISPH_CHECK_HIP(hipMemcpyAsync(ctx->xdev.p, x, sizeof(double) * nx, hipMemcpyHostToDevice, ctx->stream));
-  if (S.ncol > S.nrow && A->halo.npeers == 0) {
-    // caller supplied all ncol entries (ghost values included): plain kernel
-    int nbp = 0;
-    const int grid = spmv_grid(S.nslices, &nbp);
-    hipLaunchKernelGGL((k_sell_spmv<8, false, true>), dim3(grid), dim3(kBlock), 0, ctx->stream, S.nrow, S.nslices, nbp,
-                       S.slice_off.p, S.col.p, S.val.p, (const double *)ctx->xdev.p, ctx->bdev.p, (const double *)nullptr,
-                       (double *)nullptr);
+    order_gather(ctx, *A->order, S.nrow, 1, dx, 0, xi.p, 0, /*nghost=*/(int)(nx - (size_t)S.nrow));
+    ISPH_CHECK(spmv_operand(ctx, A, ghosts_given, xi.p, yi.p));
+    order_scatter(ctx, *A->order, S.nrow, 1, (const double *)yi.p, 0, dy, 0);
   } else {
-    ISPH_CHECK(spmv_dev(ctx, A, ctx->xdev.p, ctx->bdev.p, nullptr));
+    ISPH_CHECK(spmv_operand(ctx, A, ghosts_given, dx, dy));
   }
-  ISPH_CHECK_HIP(hipMemcpyAsync(y, ctx->bdev.p, sizeof(double) * (size_t)S.nrow, hipMemcpyDeviceToHost, ctx->stream));
-  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  if (!on_device) ISPH_CHECK_HIP(hipMemcpyAsync(y, dy, sizeof(double) * (size_t)S.nrow, hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // the temporaries go back to the pool
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
 }
@@ -1288,47 +1090,12 @@ int isph_prec_create_blocks(isph_ctx *ctx, const isph_mat *A, int nblocks, const
   return isph_prec_create_blocks_fill(ctx, A, nblocks, block_ptr, 0, Mout);
 }
 
-// the three routes of the block stream: the caller's table (nblocks > 0), the matrix' own subdomains (block_size <= 0), one
-// block per block_size rows.  value_bits: 64 or 32 (checked by the caller)
-static int prec_ilu_init(isph_ctx *ctx, const isph_mat *A, int level_of_fill, int block_size, int nblocks, const int *block_ptr,
-                         int value_bits, isph_prec *M) {
-  M->type = 2;
-  if (nblocks > 0) {
-    ISPH_REQUIRE(block_ptr, "NULL argument or no subdomains");
-    ISPH_REQUIRE(level_of_fill >= 0 && level_of_fill <= 8, "level of fill must be in [0,8]");
-    ISPH_REQUIRE(!is_device_pointer(block_ptr), "block_ptr must be a host array");
-    ISPH_REQUIRE(!A->order, "the matrix was assembled in the library's own row numbering: its subdomains are the library's "
-                            "bricks (isph_prec_create with block_size 0); a table over the caller's rows needs "
-                            "isph_ctx_set_ordering(ctx, 0) before the assembly");
-    int cap = 64;
-    for (int b = 0; b < nblocks; ++b) cap = std::max(cap, block_ptr[b + 1] - block_ptr[b]);
-    cap = (cap + 63) / 64 * 64;
-    ISPH_REQUIRE(cap <= 1024, "a subdomain of the block stream holds at most 1024 rows (isph_prec_create_schwarz takes larger ones)");
-    return ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, level_of_fill, nblocks, block_ptr, value_bits);
-  }
-  if (block_size <= 0) {
-    // the matrix' own subdomains: the bricks the assembly sorted the particles into (order.hpp)
-    if (!A->order)
-      return fail("block_size 0 selects the library's own subdomains: the matrix must come from an assembly entry point "
-                  "with isph_ctx_set_ordering(ctx, 1)", __FILE__, __LINE__);
-    const std::vector<int> &bp = A->order->block_ptr;
-    int cap = 64;
-    for (size_t b = 0; b + 1 < bp.size(); ++b) cap = std::max(cap, bp[b + 1] - bp[b]);
-    cap = (cap + 63) / 64 * 64;
-    return ilu_create(ctx, A, cap, &M->ilu, /*sgs=*/false, level_of_fill, (int)bp.size() - 1, bp.data(), value_bits);
-  }
-  return ilu_create(ctx, A, block_size, &M->ilu, /*sgs=*/false, level_of_fill, 0, nullptr, value_bits);
-}
-
 int isph_prec_create_blocks_fill(isph_ctx *ctx, const isph_mat *A, int nblocks, const int *block_ptr, int level_of_fill,
                                  isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && Mout && nblocks > 0 && block_ptr, "NULL argument or no subdomains");
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  const int rc = prec_ilu_init(ctx, A, level_of_fill, 0, nblocks, block_ptr, 64, M);
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(A->S.nrow, PREC_BJACOBI_ILU);
+  ISPH_CHECK(prec_ilu_init(ctx, A, level_of_fill, 0, nblocks, block_ptr, 64, M.M));
+  return M.finish(nullptr, Mout);  // a caller's table is refused for a matrix in the library's numbering
 }
 
 void isph_ilu_params_default(isph_ilu_params *p) {
@@ -1344,14 +1111,11 @@ int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params
                "block ILU: value_bits must be 64 (or 0: double values) or 32 (single-precision factor values in the solves)");
   ISPH_REQUIRE(prm->level_of_fill >= 0 && prm->level_of_fill <= 8, "level of fill must be in [0,8]");
   ISPH_REQUIRE(prm->nblocks >= 0 && (prm->nblocks == 0 || prm->block_ptr), "a table of subdomains without its offsets");
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  const int rc = prec_ilu_init(ctx, A, prm->level_of_fill, prm->block_size, prm->nblocks, prm->block_ptr,
-                               prm->value_bits == 32 ? 32 : 64, M);
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  if (prm->nblocks == 0) M->order = A->order;  // as isph_prec_create; a table is refused for a matrix in the library's numbering
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(A->S.nrow, PREC_BJACOBI_ILU);
+  ISPH_CHECK(prec_ilu_init(ctx, A, prm->level_of_fill, prm->block_size, prm->nblocks, prm->block_ptr,
+                           prm->value_bits == 32 ? 32 : 64, M.M));
+  // as isph_prec_create; a caller's table is refused for a matrix in the library's numbering
+  return M.finish(prm->nblocks == 0 ? A->order : nullptr, Mout);
 }
 
 /* ---- Chebyshev polynomial in D^-1 A ------------------------------------ */
@@ -1362,48 +1126,25 @@ void isph_cheb_params_default(isph_cheb_params *p) {
   p->eig_type = 0; p->eig_iters = 10;  // the bound rho ("Anorm"); ML's "eigen-analysis: iterations" for eig_type 1
 }
 
-static int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec *M) {
-  ISPH_REQUIRE(prm->degree >= 1 && prm->degree <= kChebMaxDegree, "Chebyshev: degree must be in [1,16]");
-  ISPH_REQUIRE(prm->ratio > 1.0, "Chebyshev: ratio (\"chebyshev: ratio eigenvalue\") must be > 1");
-  ISPH_REQUIRE(prm->value_bits == 0 || prm->value_bits == 64 || prm->value_bits == 32,
-               "Chebyshev: value_bits must be 64 (or 0: double values) or 32 (single-precision matrix values)");
-  ISPH_REQUIRE(prm->eig_type == 0 || prm->eig_type == 1,
-               "Chebyshev: eig_type must be 0 (the bound rho = ||D^-1 A||_inf) or 1 (the Arnoldi estimate)");
-  ISPH_REQUIRE(prm->eig_iters >= 1 && prm->eig_iters <= kEigMaxIters, "Chebyshev: eig_iters must be in [1,50]");
-  M->type = 6;
-  M->cheb_A = A;
-  ISPH_CHECK(cheb_setup(ctx, A, prm->degree, prm->ratio, prm->lambda_max, prm->lambda_min, /*empty_ok=*/false,
-                        /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &M->cheb,
-                        prm->value_bits == 32 ? 32 : 64, prm->eig_type, prm->eig_iters, /*eig_level=*/0));
-  M->cheb->held = ctx->pattern_hold;
-  return ISPH_SUCCESS;
-}
-
 int isph_prec_create_chebyshev(isph_ctx *ctx, const isph_mat *A, const isph_cheb_params *prm, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && Mout, "NULL argument");
   isph_cheb_params def;
   isph_cheb_params_default(&def);
   if (!prm) prm = &def;
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  const int rc = prec_chebyshev_init(ctx, A, prm, M);
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  M->order = A->order;
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(A->S.nrow, PREC_CHEBYSHEV);
+  ISPH_CHECK(prec_chebyshev_init(ctx, A, prm, M.M));
+  return M.finish(A->order, Mout);
 }
 
 int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double out[3]) {
   ISPH_REQUIRE(ctx && M && out, "NULL argument");
-  ISPH_REQUIRE((M->type == 6 && M->cheb) || (M->type == 3 && M->amg),
-               "isph_prec_eig_estimate: not a Chebyshev or an AMG preconditioner");
-  if (M->type == 6) {
+  ISPH_REQUIRE(prec_cheb(M) || prec_amg(M), "isph_prec_eig_estimate: not a Chebyshev or an AMG preconditioner");
+  if (const Cheb *C = prec_cheb(M)) {
     ISPH_REQUIRE(level == 0, "level out of range");
-    const Cheb *C = M->cheb;
     out[0] = C->eig_type == 1 ? C->lambda : C->rho; out[1] = C->rho; out[2] = (double)C->eig_steps;
     return ISPH_SUCCESS;
   }
-  const isph_amg *G = M->amg;
+  const isph_amg *G = prec_amg(M);
   ISPH_REQUIRE(level >= 0 && level < G->nlev, "level out of range");
   const AmgLevel *L = G->L[(size_t)level];
   if (G->eig_type == 1) {
@@ -1420,185 +1161,30 @@ int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double 
 }
 
 int isph_prec_value_bits(const isph_prec *M) {
-  if (!M) return 0;
-  if (M->type == 6 && M->cheb) return M->cheb->value_bits;
-  if (M->type == 3 && M->amg && M->amg->cheb) return M->amg->cheb_value_bits;
-  if (M->type == 2 && M->ilu && M->ilu->value_bits == 32) return 32;
+  if (const Cheb *C = prec_cheb(M)) return C->value_bits;
+  if (const isph_amg *G = prec_amg(M)) return G->cheb ? G->cheb_value_bits : 0;
+  if (const isph_ilu *F = prec_ilu(M)) return F->value_bits == 32 ? 32 : 0;
   return 0;
 }
 
 int isph_prec_cycle_bits(const isph_prec *M) {
-  return (M && M->type == 3 && M->amg && M->amg->cheb && M->amg->cycle_bits == 32) ? 32 : 64;
-}
-
-// a cycle_bits = 32 AMG is not a linear operator: only flexible GMRES keeps what it was applied to (Z); the other
-// drivers form x += M^-1 (V y), the rounded cycle of a vector it never saw
-static int check_cycle_bits_solver(const isph_prec *M, const isph_solver_params *prm) {
-  if (isph_prec_cycle_bits(M) != 32) return ISPH_SUCCESS;
-  ISPH_REQUIRE(prm->solver_type == 0, "a preconditioner with cycle_bits = 32 needs flexible Block GMRES: solver_type 1 and 2 are not available with it");
-  ISPH_REQUIRE(prm->flexible != 0, "a preconditioner with cycle_bits = 32 needs flexible = 1: the rounded cycle is not a linear operator");
-  return ISPH_SUCCESS;
-}
-
-// "chebyshev<d>" or "chebyshev<d>-f32", d = 1..16; *bits = 64 or 32
-static bool parse_chebyshev_type(const char *type, int *degree, int *bits) {
-  if (strncmp(type, "chebyshev", 9) != 0 || type[9] < '1' || type[9] > '9') return false;
-  const char *tail = type + 10;
-  if (type[9] == '1' && *tail >= '0' && *tail <= '6') ++tail;
-  if (*tail != 0 && strcmp(tail, "-f32") != 0) return false;
-  *degree = atoi(type + 9);
-  *bits = *tail ? 32 : 64;
-  return true;
+  const isph_amg *G = prec_amg(M);
+  return (G && G->cheb && G->cycle_bits == 32) ? 32 : 64;
 }
 
 int isph_prec_create(isph_ctx *ctx, const isph_mat *A, const char *type, int block_size, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && type && Mout, "NULL argument");
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  int rc = ISPH_SUCCESS;
-  int cheb_degree = 0, cheb_bits = 64;
-  if (!strcmp(type, "none")) {
-    M->type = 0;
-  } else if (!strcmp(type, "jacobi")) {
-    M->type = 1;
-    rc = M->invdiag.reserve((size_t)(M->n > 0 ? M->n : 1));
-    if (rc == ISPH_SUCCESS && M->n > 0) {
-      hipLaunchKernelGGL(k_sell_inv_diag, dim3((M->n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, M->n,
-                         A->S.rowlen.p, A->S.slice_off.p, A->S.col.p, A->S.val.p, M->invdiag.p);
-      if (hipGetLastError() != hipSuccess) rc = fail("jacobi setup failed", __FILE__, __LINE__);
-    }
-  } else if (!strncmp(type, "bjacobi-ilu", 11) && type[11] >= '0' && type[11] <= '8' && (type[12] == 0 || !strcmp(type + 12, "-f32"))) {
-    // "bjacobi-ilu<k>": "fact: level-of-fill" = k (precond_ifpack.h:35); "bjacobi-ilu<k>-f32": the same with value_bits = 32
-    rc = prec_ilu_init(ctx, A, /*fill=*/type[11] - '0', block_size, 0, nullptr, type[12] ? 32 : 64, M);
-  } else if (!strncmp(type, "ilu", 3) && type[3] >= '0' && type[3] <= '8' && type[4] == 0) {
-    // "ilu<k>": ILU(k) of the whole local matrix -- what Ifpack factors on one MPI rank (the overlap is a no-op there)
-    M->type = 4;
-    rc = schwarz_create(ctx, A, type[3] - '0', /*block_size=*/0, /*overlap=*/0, /*combine=*/0, &M->schwarz);
-  } else if (!strcmp(type, "sa-amg")) {
-    // PrecondWrapper_ML defaults without a null vector; block_size is the Gauss-Seidel block of the fine level.
-    // isph_prec_create_amg takes the full parameter set and the null vector of a singular system.
-    isph_amg_params prm;
-    isph_amg_params_default(&prm);
-    prm.block = block_size;
-    M->type = 3;
-    rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
-  } else if (!strncmp(type, "sa-amg-ilu", 10) && type[10] >= '0' && type[10] <= '8' && type[11] == 0) {
-    // "sa-amg-ilu<k>": "sa-amg" with ML's IFPACK smoother, block ILU(k) (isph_amg_params::smoother = 4, ilu_fill = k)
-    isph_amg_params prm;
-    isph_amg_params_default(&prm);
-    prm.block = block_size;
-    prm.smoother = 4;
-    prm.ilu_fill = type[10] - '0';
-    M->type = 3;
-    rc = amg_create(ctx, A, &prm, nullptr, &M->amg);
-  } else if (parse_chebyshev_type(type, &cheb_degree, &cheb_bits)) {
-    // "chebyshev<d>", d = 1..16: Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults;
-    // "chebyshev<d>-f32": the same with value_bits = 32
-    isph_cheb_params prm;
-    isph_cheb_params_default(&prm);
-    prm.degree = cheb_degree;
-    prm.value_bits = cheb_bits;
-    rc = prec_chebyshev_init(ctx, A, &prm, M);
-  } else {
-    rc = fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>|sa-amg-ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)", __FILE__, __LINE__);
-  }
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  M->order = A->order;
-  *Mout = M;
-  return ISPH_SUCCESS;
-}
-
-// isph_prec_refactor of "sa-amg" and "chebyshev<d>": the row count is checked here, everything else by the type
-static int prec_refactor_rows(const isph_prec *M, const isph_mat *A) {
-  if (A->S.nrow == M->n) return ISPH_SUCCESS;
-  char msg[160];
-  snprintf(msg, sizeof(msg), "refactor: the matrix has %d rows, the preconditioner was built for %d", A->S.nrow, M->n);
-  return fail(msg, __FILE__, __LINE__);
+  return prec_create_named(ctx, A, type, block_size, Mout);
 }
 
 int isph_prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
   ISPH_REQUIRE(ctx && M && A, "NULL argument");
-  if (M->type == 3 && M->amg) {   // the hierarchy of the new values on the kept aggregates (amg.hpp amg_refactor)
-    ISPH_CHECK(prec_refactor_rows(M, A));
-    ISPH_REQUIRE(M->order == A->order, "refactor: the matrix is not in the row numbering the AMG hierarchy was built in "
-                                       "(the aggregates are sets of its rows): rebuild");
-    ISPH_CHECK(amg_refactor(ctx, M->amg, A));
-    M->order = A->order;
-    return ISPH_SUCCESS;
-  }
-  if (M->type == 6 && M->cheb && M->cheb->held) {  // nothing of the pattern is kept: the set-up of the create call on the new values
-    ISPH_CHECK(prec_refactor_rows(M, A));
-    const Cheb *C0 = M->cheb;
-    Cheb *C1 = nullptr;
-    ISPH_CHECK(cheb_setup(ctx, A, C0->degree, C0->ratio_in, C0->lambda_max_in, C0->lambda_min_in, /*empty_ok=*/false,
-                          /*collective=*/comm_active(ctx) && ctx->nranks > 1, /*prior_failure=*/false, &C1, C0->value_bits,
-                          C0->eig_type_in, C0->eig_iters_in, /*eig_level=*/0));
-    cheb_destroy(M->cheb);
-    C1->held = true;
-    M->cheb = C1;
-    M->cheb_A = A;
-    M->order = A->order;
-    return ISPH_SUCCESS;
-  }
-  if (M->type == 6)
-    return fail("refactor of \"chebyshev<d>\": the polynomial was created while the pattern was not held (isph_ctx_hold_pattern "
-                "was off): rebuild it", __FILE__, __LINE__);
-  if (M->type != 2 || !M->ilu) {
-    static const char *const names[] = {"none", "jacobi", "bjacobi-ilu<k>", "sa-amg", "ilu<k> / additive Schwarz", "overlap ILU(k)",
-                                        "chebyshev<d>"};
-    char msg[200];
-    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to \"bjacobi-ilu<k>\", \"sa-amg\" and \"chebyshev<d>\", not to a "
-                               "preconditioner of type \"%s\": rebuild it", M->type >= 0 && M->type <= 6 ? names[M->type] : "?");
-    return fail(msg, __FILE__, __LINE__);
-  }
-  // the subdomains of the library's own numbering come with the matrix: they must be the ones the factor was laid out for
-  const bool mo = (bool)M->order, ao = (bool)A->order;
-  if (mo != ao || (mo && M->order != A->order && M->order->block_ptr != A->order->block_ptr)) {
-    char msg[200];
-    snprintf(msg, sizeof(msg), "refactor: the subdomain table differs (the preconditioner has %d subdomains %s the library's "
-                               "numbering, the matrix %d)", M->ilu->nblocks, mo ? "in" : "outside",
-             ao ? A->order->nblocks() : 0);
-    return fail(msg, __FILE__, __LINE__);
-  }
-  ISPH_CHECK(ilu_refactor(ctx, M->ilu, A->S));
-  M->order = A->order;
-  return ISPH_SUCCESS;
+  return prec_refactor(ctx, M, A);
 }
 
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r, double *z, int on_device) {
   ISPH_REQUIRE(ctx && M && r && z, "NULL argument");
-  if (M->order && M->n > 0) {  // r and z are the caller's; the preconditioner lives in the numbering of its matrix
-    const size_t n = (size_t)M->n;
-    DevTmp<double> rc, ri, zi;
-    const double *drc = r;
-    if (!on_device) {
-      ISPH_CHECK(rc.reserve(n));
-      ISPH_CHECK_HIP(hipMemcpyAsync(rc.p, r, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-      drc = rc.p;
-    }
-    ISPH_CHECK(ri.reserve(n + 64));
-    ISPH_CHECK(zi.reserve(n + 64));
-    hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid((long long)n)), dim3(kBlock), 0, ctx->stream, (long long)n, M->n, 1,
-                       (const int *)M->order->perm.p, drc, ri.p);
-    ISPH_CHECK(prec_apply_dev(ctx, M, ri.p, zi.p));
-    double *dz = on_device ? z : rc.p;
-    hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(M->n)), dim3(kBlock), 0, ctx->stream, M->n,
-                       (const int *)M->order->perm.p, (const double *)zi.p, dz);
-    if (!on_device) ISPH_CHECK_HIP(hipMemcpyAsync(z, dz, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    ISPH_CHECK_HIP(hipGetLastError());
-    return prec_health(ctx, M);
-  }
-  if (on_device) return prec_apply_dev(ctx, M, r, z);
-  const size_t n = (size_t)M->n;
-  ISPH_CHECK(ctx->xdev.reserve(n > 0 ? n : 1));
-  ISPH_CHECK(ctx->bdev.reserve(n > 0 ? n : 1));
-  ISPH_CHECK_HIP(hipMemcpyAsync(ctx->xdev.p, r, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  ISPH_CHECK(prec_apply_dev(ctx, M, ctx->xdev.p, ctx->bdev.p));
-  ISPH_CHECK_HIP(hipMemcpyAsync(z, ctx->bdev.p, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
-  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  ISPH_CHECK_HIP(hipGetLastError());
-  return prec_health(ctx, M);
+  return prec_apply_operands(ctx, M, r, z, on_device);
 }
 
 int isph_prec_multi_path(isph_ctx *ctx, const isph_prec *M, int nvec) {
@@ -1610,63 +1196,19 @@ int isph_prec_apply_multi(isph_ctx *ctx, const isph_prec *M, int nvec, const dou
   ISPH_REQUIRE(ctx && M && r && z, "NULL argument");
   ISPH_REQUIRE(nvec >= 1, "isph_prec_apply_multi: nvec must be at least 1");
   ISPH_REQUIRE(lda >= M->n, "isph_prec_apply_multi: lda must be at least the number of rows");
-  const int n = M->n;
-  if (n == 0) return ISPH_SUCCESS;
-  const size_t K = (size_t)nvec, ldd = ((size_t)n + 64 + 1) & ~(size_t)1, rowbytes = sizeof(double) * (size_t)n;
-  const bool ordered = (bool)M->order;
-  // host operands: one strided copy each way (the padding rows of z are not written); the matrix' own numbering: the
-  // vectors are gathered into it and the results scattered back, as isph_prec_apply does
-  DevTmp<double> rin, ri, zi;
-  const double *dr = r;
-  double *dz = z;
-  size_t ldr = (size_t)lda, ldz = (size_t)lda;
-  if (!on_device) {
-    ISPH_REQUIRE(!is_device_pointer(r) && !is_device_pointer(z), "device pointer passed with on_device = 0");
-    ISPH_CHECK(rin.reserve(ldd * K));
-    ISPH_CHECK_HIP(hipMemcpy2DAsync(rin.p, sizeof(double) * ldd, r, sizeof(double) * (size_t)lda, rowbytes, K, hipMemcpyHostToDevice, ctx->stream));
-    dr = rin.p; ldr = ldd;
-  }
-  if (ordered) {
-    ISPH_CHECK(ri.reserve(ldd * K));
-    for (size_t k = 0; k < K; ++k)
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid((long long)n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1,
-                         (const int *)M->order->perm.p, dr + k * ldr, ri.p + k * ldd);
-    dr = ri.p; ldr = ldd;
-  }
-  if (ordered || !on_device) {
-    ISPH_CHECK(zi.reserve(ldd * K));
-    dz = zi.p; ldz = ldd;
-  }
-  std::vector<const double *> rs(K);
-  std::vector<double *> zs(K);
-  for (size_t k = 0; k < K; ++k) { rs[k] = dr + k * ldr; zs[k] = dz + k * ldz; }
-  ISPH_CHECK(prec_apply_multi_dev(ctx, M, nvec, rs.data(), zs.data()));
-  if (!ordered && on_device) return ISPH_SUCCESS;
-  if (ordered) {   // back to the caller's numbering: into z itself on the device, into the staged r otherwise
-    double *out = on_device ? z : rin.p;
-    const size_t ldo = on_device ? (size_t)lda : ldd;
-    for (size_t k = 0; k < K; ++k)
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, n, (const int *)M->order->perm.p,
-                         (const double *)(zi.p + k * ldd), out + k * ldo);
-    dz = out;
-  }
-  if (!on_device)
-    ISPH_CHECK_HIP(hipMemcpy2DAsync(z, sizeof(double) * (size_t)lda, dz, sizeof(double) * ldd, rowbytes, K, hipMemcpyDeviceToHost, ctx->stream));
-  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  ISPH_CHECK_HIP(hipGetLastError());
-  return prec_health(ctx, M);
+  return prec_apply_multi_operands(ctx, M, nvec, r, z, lda, on_device);
 }
 
 int isph_prec_export_ilu(isph_ctx *ctx, const isph_prec *M, int *rowptr, int *colidx, double *val) {
-  ISPH_REQUIRE(ctx && M && M->type == 2 && M->ilu, "not an ILU preconditioner");
+  ISPH_REQUIRE(ctx && prec_ilu(M), "not an ILU preconditioner");
   return ilu_export(ctx, M->ilu, rowptr, colidx, val);
 }
 
 int isph_prec_info(isph_ctx *ctx, const isph_prec *M, long long info[4]) {
   ISPH_REQUIRE(ctx && M && info, "NULL argument");
   info[0] = info[1] = info[2] = info[3] = 0;
-  if (M->type != 2 || !M->ilu) return ISPH_SUCCESS;
-  const isph_ilu *F = M->ilu;
+  const isph_ilu *F = prec_ilu(M);
+  if (!F) return ISPH_SUCCESS;
   std::vector<int> bi((size_t)4 * F->nblocks);  // per block: chunks of the L / U stream, rows in the L / U stream
   ISPH_CHECK_HIP(hipMemcpyAsync(bi.data(), F->blkinfo.p, sizeof(int) * bi.size(), hipMemcpyDeviceToHost, ctx->stream));
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
@@ -1676,18 +1218,9 @@ int isph_prec_info(isph_ctx *ctx, const isph_prec *M, long long info[4]) {
   return ISPH_SUCCESS;
 }
 
-long long isph_prec_nnz(const isph_prec *M) { return (M && M->type == 2 && M->ilu) ? ilu_nnz(M->ilu) : 0; }
+long long isph_prec_nnz(const isph_prec *M) { return prec_ilu(M) ? ilu_nnz(M->ilu) : 0; }
 
-void isph_prec_destroy(isph_prec *M) {
-  if (!M) return;
-  M->invdiag.release();
-  if (M->ilu) ilu_destroy(M->ilu);
-  if (M->amg) amg_destroy(M->amg);
-  if (M->schwarz) schwarz_destroy(M->schwarz);
-  if (M->ovl) overlap_destroy(M->ovl);
-  if (M->cheb) cheb_destroy(M->cheb);
-  delete M;
-}
+void isph_prec_destroy(isph_prec *M) { prec_destroy(M); }
 
 /* ---- additive Schwarz ILU(k) with the reference's Ifpack semantics ------ */
 
@@ -1698,27 +1231,22 @@ void isph_schwarz_params_default(isph_schwarz_params *p) {
 
 int isph_prec_create_schwarz(isph_ctx *ctx, const isph_mat *A, const isph_schwarz_params *prm, isph_prec **Mout) {
   ISPH_REQUIRE(ctx && A && prm && Mout, "NULL argument");
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  M->type = 4;
-  const int rc = schwarz_create(ctx, A, prm->level_of_fill, prm->block_size, prm->overlap, prm->combine, &M->schwarz,
-                                /*syncfree=*/prm->level_launches == 0);
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  M->order = A->order;
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(A->S.nrow, PREC_SCHWARZ);
+  ISPH_CHECK(schwarz_create(ctx, A, prm->level_of_fill, prm->block_size, prm->overlap, prm->combine, &M->schwarz,
+                            /*syncfree=*/prm->level_launches == 0));
+  return M.finish(A->order, Mout);
 }
 
 int isph_prec_schwarz_info(const isph_prec *M, long long info[7]) {
-  ISPH_REQUIRE(M && M->type == 4 && M->schwarz && info, "not a Schwarz preconditioner");
-  const isph_schwarz *S = M->schwarz;
+  const isph_schwarz *S = prec_schwarz(M);
+  ISPH_REQUIRE(S && info, "not a Schwarz preconditioner");
   info[0] = S->nloc; info[1] = S->nnz; info[2] = S->nsub; info[3] = S->nlev_l; info[4] = S->nlev_u; info[5] = S->maxrow; info[6] = S->subsweep ? 2 : S->syncfree ? 1 : 0;
   return ISPH_SUCCESS;
 }
 
 int isph_prec_schwarz_paths(const isph_prec *M, long long out[12]) {
-  ISPH_REQUIRE(M && M->type == 4 && M->schwarz && out, "not a Schwarz preconditioner");
-  const isph_schwarz *S = M->schwarz;
+  const isph_schwarz *S = prec_schwarz(M);
+  ISPH_REQUIRE(S && out, "not a Schwarz preconditioner");
   out[0] = S->path_devlocal; out[1] = S->path_symbolic1_dev; out[2] = S->long_rows; out[3] = S->factor_waves; out[4] = S->factor_hbits;
   out[5] = S->nrun_l; out[6] = S->nrun_u; out[7] = S->runs_near[0]; out[8] = S->runs_near[1]; out[9] = S->sub_maxrows;
   out[10] = S->n4l; out[11] = S->n4u;
@@ -1726,14 +1254,14 @@ int isph_prec_schwarz_paths(const isph_prec *M, long long out[12]) {
 }
 
 int isph_prec_schwarz_timing(const isph_prec *M, double ms[6]) {
-  ISPH_REQUIRE(M && M->type == 4 && M->schwarz && ms, "not a Schwarz preconditioner");
+  ISPH_REQUIRE(prec_schwarz(M) && ms, "not a Schwarz preconditioner");
   for (int k = 0; k < 6; ++k) ms[k] = M->schwarz->t_ms[k];
   return ISPH_SUCCESS;
 }
 
 int isph_prec_schwarz_export(isph_ctx *ctx, const isph_prec *M, int *rows, int *loc_ptr, long long *rowptr, int *colidx,
                              double *val) {
-  ISPH_REQUIRE(ctx && M && M->type == 4 && M->schwarz && rows && loc_ptr && rowptr && colidx && val, "bad argument");
+  ISPH_REQUIRE(ctx && prec_schwarz(M) && rows && loc_ptr && rowptr && colidx && val, "bad argument");
   return schwarz_export(ctx, M->schwarz, rows, loc_ptr, rowptr, colidx, val);
 }
 
@@ -1748,32 +1276,9 @@ int isph_prec_create_overlap(isph_ctx *ctx, const isph_mat *Aext, int nlocal, in
                "the extended matrix must be square with nlocal + (number of ghost columns) rows");
   for (int p = 0; p < npeers; ++p) ISPH_REQUIRE(peer_rank[p] >= 0 && peer_rank[p] < ctx->nranks, "peer rank out of range");
   for (int k = 0; k < nsend; ++k) ISPH_REQUIRE(send_idx[k] >= 0 && send_idx[k] < nlocal, "send index out of range");
-  isph_prec *M = new isph_prec();
-  M->n = nlocal;
-  M->type = 5;
-  isph_overlap *O = new isph_overlap();
-  M->ovl = O;
-  O->n = nlocal; O->next = nlocal + nrecv; O->combine = combine;
-  isph_halo &H = O->H;
-  H.npeers = npeers;
-  H.peer.assign(peer_rank, peer_rank + npeers);
-  H.send_ptr.assign(1, 0); H.recv_ptr.assign(1, 0);
-  if (npeers > 0) { H.send_ptr.assign(send_ptr, send_ptr + npeers + 1); H.recv_ptr.assign(recv_ptr, recv_ptr + npeers + 1); }
-  H.nsend = nsend; H.nrecv = nrecv;
-  int rc = H.send_idx.reserve((size_t)(nsend > 0 ? nsend : 1));
-  if (rc == ISPH_SUCCESS && nsend > 0 &&
-      hipMemcpyAsync(H.send_idx.p, send_idx, sizeof(int) * (size_t)nsend, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
-    rc = fail("copy of the send list failed", __FILE__, __LINE__);
-  if (rc == ISPH_SUCCESS) rc = O->rext.reserve((size_t)(O->next > 0 ? O->next : 1));
-  if (rc == ISPH_SUCCESS) rc = O->zext.reserve((size_t)(O->next > 0 ? O->next : 1));
-  if (rc == ISPH_SUCCESS) rc = O->sbuf.reserve((size_t)(nsend > 0 ? nsend : 1));
-  if (rc == ISPH_SUCCESS) rc = O->rbuf.reserve((size_t)(nsend > 0 ? nsend : 1));
-  // one subdomain = the whole extended matrix, no further layers inside it
-  if (rc == ISPH_SUCCESS) rc = schwarz_create(ctx, Aext, level_of_fill, /*block_size=*/0, /*overlap=*/0, /*combine=*/1, &O->inner);
-  if (rc == ISPH_SUCCESS && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = fail("overlap set-up failed", __FILE__, __LINE__);
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(nlocal, PREC_OVERLAP);
+  ISPH_CHECK(overlap_create(ctx, Aext, nlocal, level_of_fill, combine, npeers, peer_rank, send_ptr, send_idx, recv_ptr, &M->ovl));
+  return M.finish(nullptr, Mout);  // the extended matrix is the caller's, in the caller's numbering
 }
 
 /* ---- SA-AMG ----------------------------------------------------------- */
@@ -1795,44 +1300,15 @@ int isph_prec_create_amg(isph_ctx *ctx, const isph_mat *A, const isph_amg_params
   isph_amg_params def;
   isph_amg_params_default(&def);
   if (!prm) prm = &def;
-  isph_prec *M = new isph_prec();
-  M->n = A->S.nrow;
-  M->type = 3;
-  DevTmp<double> tn, tp;
-  const double *dn = nullptr;
-  int rc = nullvec ? stage_in(ctx, nullvec, (size_t)M->n, on_device, tn, &dn) : ISPH_SUCCESS;
-  if (rc == ISPH_SUCCESS && dn && A->order && M->n > 0) {  // the caller's null vector in the matrix' numbering
-    rc = tp.reserve((size_t)M->n);
-    if (rc == ISPH_SUCCESS) {
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(M->n)), dim3(kBlock), 0, ctx->stream, (long long)M->n, M->n, 1,
-                         (const int *)A->order->perm.p, dn, tp.p);
-      dn = tp.p;
-    }
-  }
-  if (rc == ISPH_SUCCESS) rc = amg_create(ctx, A, prm, dn, &M->amg);
-  M->order = A->order;
-  tn.release(); tp.release();
-  if (comm_active(ctx) && ctx->nranks > 1) {
-    // Every level exchanges halos inside the cycle, and how often depends on the depth of the hierarchy and on the coarse
-    // solver.  amg_create agrees on both between the ranks while it builds (amg.hpp); this is the last word on the outcome:
-    // ranks that disagree would wait for each other forever -- fail on every rank together instead.
-    double h[3] = {rc == ISPH_SUCCESS ? 1.0 : 0.0, (rc == ISPH_SUCCESS && M->amg->nlev > 1) ? 1.0 : 0.0,
-                   (rc == ISPH_SUCCESS && M->amg->coarse_smooth) ? 1.0 : 0.0};
-    const double nr = (double)ctx->nranks;
-    if (comm_host_allreduce(ctx, h, 3, /*sum*/ 0) != ISPH_SUCCESS) rc = fail("AMG: set-up consensus between the ranks failed", __FILE__, __LINE__);
-    else if (h[0] != nr) rc = rc != ISPH_SUCCESS ? rc : comm_failed_elsewhere("AMG");
-    else if ((h[1] != 0.0 && h[1] != nr) || (h[1] == 0.0 && h[2] != 0.0 && h[2] != nr))
-      rc = fail("AMG: the ranks built hierarchies of different depth; their fine-level halo exchanges would not match", __FILE__, __LINE__);
-  }
-  if (rc != ISPH_SUCCESS) { isph_prec_destroy(M); return rc; }
-  *Mout = M;
-  return ISPH_SUCCESS;
+  PrecNew M(A->S.nrow, PREC_AMG);
+  ISPH_CHECK(prec_amg_init(ctx, A, prm, nullvec, on_device, M.M));
+  return M.finish(A->order, Mout);
 }
 
-int isph_prec_amg_levels(const isph_prec *M) { return (M && M->type == 3 && M->amg) ? M->amg->nlev : 0; }
+int isph_prec_amg_levels(const isph_prec *M) { return prec_amg(M) ? M->amg->nlev : 0; }
 
 int isph_prec_amg_info(isph_ctx *ctx, const isph_prec *M, int level, long long info[3]) {
-  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && info, "not an AMG preconditioner");
+  ISPH_REQUIRE(ctx && prec_amg(M) && info, "not an AMG preconditioner");
   ISPH_REQUIRE(level >= 0 && level < M->amg->nlev, "level out of range");
   const AmgLevel *L = M->amg->L[(size_t)level];
   info[0] = L->A.n; info[1] = L->A.nnz; info[2] = level < M->amg->nlev - 1 ? L->P.nnz : 0;
@@ -1840,7 +1316,7 @@ int isph_prec_amg_info(isph_ctx *ctx, const isph_prec *M, int level, long long i
 }
 
 int isph_prec_amg_export(isph_ctx *ctx, const isph_prec *M, int level, int what, int *rowptr, int *colidx, double *val) {
-  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && rowptr && colidx && val, "not an AMG preconditioner");
+  ISPH_REQUIRE(ctx && prec_amg(M) && rowptr && colidx && val, "not an AMG preconditioner");
   ISPH_REQUIRE(level >= 0 && level < M->amg->nlev && (what == 0 || (what == 1 && level < M->amg->nlev - 1)), "level out of range");
   const DCsr &Ck = what == 0 ? M->amg->L[(size_t)level]->A : M->amg->L[(size_t)level]->P;
   ISPH_REQUIRE(Ck.nnz < 2147483647LL, "level too large for the 32-bit test export");
@@ -1875,7 +1351,7 @@ int isph_prec_amg_export(isph_ctx *ctx, const isph_prec *M, int level, int what,
 }
 
 int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *agg) {
-  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && agg, "not an AMG preconditioner");
+  ISPH_REQUIRE(ctx && prec_amg(M) && agg, "not an AMG preconditioner");
   ISPH_REQUIRE(level >= 0 && level < M->amg->nlev - 1, "level out of range");
   const AmgLevel *L = M->amg->L[(size_t)level];
   ISPH_CHECK_HIP(hipMemcpyAsync(agg, L->agg.p, sizeof(int) * (size_t)L->A.n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1883,10 +1359,10 @@ int isph_prec_amg_aggregates(isph_ctx *ctx, const isph_prec *M, int level, int *
   return ISPH_SUCCESS;
 }
 
-long long isph_prec_amg_refreshes(const isph_prec *M) { return (M && M->type == 3 && M->amg) ? M->amg->refreshes : 0; }
+long long isph_prec_amg_refreshes(const isph_prec *M) { return prec_amg(M) ? M->amg->refreshes : 0; }
 
 int isph_prec_amg_set_nullvec(isph_ctx *ctx, isph_prec *M, const double *nullvec, int on_device) {
-  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && nullvec, "not an AMG preconditioner, or the null vector is NULL");
+  ISPH_REQUIRE(ctx && prec_amg(M) && nullvec, "not an AMG preconditioner, or the null vector is NULL");
   ISPH_REQUIRE(M->amg->singular, "isph_prec_amg_set_nullvec: the hierarchy was created without a null vector (its coarsest "
                                  "level has a direct solve): rebuild it with one");
   AmgLevel *L0 = M->amg->L[0];
@@ -1896,8 +1372,7 @@ int isph_prec_amg_set_nullvec(isph_ctx *ctx, isph_prec *M, const double *nullvec
   const double *dn = nullptr;
   ISPH_CHECK(stage_in(ctx, nullvec, (size_t)n, on_device, tn, &dn));
   if (M->order)   // the caller's null vector in the numbering of the hierarchy
-    hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1,
-                       (const int *)M->order->perm.p, dn, L0->nv.p);
+    order_gather(ctx, *M->order, n, 1, dn, 0, L0->nv.p, 0);
   else
     ISPH_CHECK_HIP(hipMemcpyAsync(L0->nv.p, dn, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
@@ -1906,7 +1381,7 @@ int isph_prec_amg_set_nullvec(isph_ctx *ctx, isph_prec *M, const double *nullvec
 }
 
 int isph_prec_amg_path(isph_ctx *ctx, const isph_prec *M, int level, long long out[8]) {
-  ISPH_REQUIRE(ctx && M && M->type == 3 && M->amg && out, "not an AMG preconditioner");
+  ISPH_REQUIRE(ctx && prec_amg(M) && out, "not an AMG preconditioner");
   ISPH_REQUIRE(level >= 0 && level < M->amg->nlev, "level out of range");
   const AmgLevel *L = M->amg->L[(size_t)level];
   for (int k = 0; k < 8; ++k) out[k] = L->path[k];
@@ -2003,11 +1478,9 @@ static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, doub
   if (ord && n > 0) {
     ISPH_CHECK(ctx->bint.reserve(tot + 64));
     ISPH_CHECK(ctx->xint.reserve(tot + 64));
-    for (int c = 0; c < nvec; ++c) {
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                         (const double *)cb + (size_t)c * lda, ctx->bint.p + (size_t)c * lda);
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                         (const double *)cx + (size_t)c * lda, ctx->xint.p + (size_t)c * lda);
+    for (int c = 0; c < nvec; ++c) {  // b and x of a column side by side, as the solve reads them
+      order_gather(ctx, *ord, n, 1, (const double *)cb + (size_t)c * lda, 0, ctx->bint.p + (size_t)c * lda, 0);
+      order_gather(ctx, *ord, n, 1, (const double *)cx + (size_t)c * lda, 0, ctx->xint.p + (size_t)c * lda, 0);
     }
     db = ctx->bint.p;
     dx = ctx->xint.p;
@@ -2027,8 +1500,7 @@ static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, doub
       }
       if (ord && n > 0) {  // the caller's mask follows its rows
         ISPH_CHECK(ctx->imask2.reserve((size_t)n));
-        hipLaunchKernelGGL((k_perm_gather<int>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                           (const int *)ctx->imask.p, ctx->imask2.p);
+        order_gather(ctx, *ord, n, 1, (const int *)ctx->imask.p, 0, ctx->imask2.p, 0);
         hipLaunchKernelGGL(k_mask_to_double, dim3(sg), dim3(kBlock), 0, st, n, ctx->imask2.p, ctx->nvec.p);
       } else {
         hipLaunchKernelGGL(k_mask_to_double, dim3(sg), dim3(kBlock), 0, st, n, ctx->imask.p, ctx->nvec.p);
@@ -2063,9 +1535,7 @@ static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, doub
       ISPH_CHECK(rr.C.reserve(cap > 0 ? cap : 1));
       if (R->kk > 0 && n > 0) {
         if (ord) {
-          for (int c = 0; c < R->kk; ++c)
-            hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                               (const double *)R->U.p + (size_t)c * rld, rr.U.p + (size_t)c * rld);
+          order_gather(ctx, *ord, n, R->kk, (const double *)R->U.p, (size_t)rld, rr.U.p, (size_t)rld);
         } else {
           ISPH_CHECK_HIP(hipMemcpyAsync(rr.U.p, R->U.p, sizeof(double) * (size_t)rld * (size_t)R->kk, hipMemcpyDeviceToDevice, st));
         }
@@ -2129,9 +1599,7 @@ static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, doub
     if (rr.kk > 0 && n > 0) {
       ISPH_CHECK(R->U.reserve((size_t)rld * (size_t)rr.kk));
       if (ord) {
-        for (int c = 0; c < rr.kk; ++c)
-          hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, n, (const int *)ord->perm.p,
-                             (const double *)rr.U.p + (size_t)c * rld, R->U.p + (size_t)c * rld);
+        order_scatter(ctx, *ord, n, rr.kk, (const double *)rr.U.p, (size_t)rld, R->U.p, (size_t)rld);
       } else {
         ISPH_CHECK_HIP(hipMemcpyAsync(R->U.p, rr.U.p, sizeof(double) * (size_t)rld * (size_t)rr.kk, hipMemcpyDeviceToDevice, st));
       }
@@ -2139,10 +1607,8 @@ static int solve_body(isph_ctx *ctx, const isph_mat *A, const isph_prec *M, doub
   }
   if (ord && n > 0) {  // back into the caller's numbering (b holds its projection when the system is singular)
     for (int c = 0; c < nvec; ++c) {
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, n, (const int *)ord->perm.p,
-                         (const double *)dx + (size_t)c * lda, cx + (size_t)c * lda);
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, n, (const int *)ord->perm.p,
-                         (const double *)db + (size_t)c * lda, cb + (size_t)c * lda);
+      order_scatter(ctx, *ord, n, 1, (const double *)dx + (size_t)c * lda, 0, cx + (size_t)c * lda, 0);
+      order_scatter(ctx, *ord, n, 1, (const double *)db + (size_t)c * lda, 0, cb + (size_t)c * lda, 0);
     }
     db = cb;
     dx = cx;
@@ -2409,10 +1875,8 @@ int isph_solve_block(isph_ctx *ctx, int dim, const isph_mat *const *blocks, cons
         ISPH_CHECK_HIP(hipMemcpyAsync(stg.p + nt + (size_t)k * n, sx, sizeof(double) * (size_t)n, in, st));
         sb = stg.p + (size_t)k * n; sx = stg.p + nt + (size_t)k * n;
       }
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                         sb, ctx->bdev.p + (size_t)k * n);
-      hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, (long long)n, n, 1, (const int *)ord->perm.p,
-                         sx, ctx->xdev.p + (size_t)k * n);
+      order_gather(ctx, *ord, n, 1, sb, 0, ctx->bdev.p + (size_t)k * n, 0);
+      order_gather(ctx, *ord, n, 1, sx, 0, ctx->xdev.p + (size_t)k * n, 0);
       continue;
     }
     ISPH_CHECK_HIP(hipMemcpyAsync(ctx->bdev.p + (size_t)k * n, b + (size_t)k * lda, sizeof(double) * (size_t)n, in, st));
@@ -2441,8 +1905,7 @@ int isph_solve_block(isph_ctx *ctx, int dim, const isph_mat *const *blocks, cons
   for (int k = 0; k < dim; ++k) {
     if (ord && n > 0) {
       double *dst = on_device ? x + (size_t)k * lda : stg.p + (size_t)k * n;
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, st, n, (const int *)ord->perm.p,
-                         (const double *)ctx->xdev.p + (size_t)k * n, dst);
+      order_scatter(ctx, *ord, n, 1, (const double *)ctx->xdev.p + (size_t)k * n, 0, dst, 0);
       if (!on_device) ISPH_CHECK_HIP(hipMemcpyAsync(x + (size_t)k * lda, dst, sizeof(double) * (size_t)n, out, st));
       continue;
     }

@@ -203,8 +203,7 @@ inline int pb_in(isph_ctx *ctx, const isph_mat *J, const double *src, int on_dev
     d = R->stage.p;
   }
   if (J->order)
-    hipLaunchKernelGGL((k_perm_gather<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, (long long)n, n, 1,
-                       (const int *)J->order->perm.p, d, dst);
+    order_gather(ctx, *J->order, n, 1, d, 0, dst, 0);
   else
     ISPH_CHECK_HIP(hipMemcpyAsync(dst, d, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
   return ISPH_SUCCESS;
@@ -218,8 +217,7 @@ inline int pb_out(isph_ctx *ctx, const isph_mat *J, const double *src, double *o
     double *d = out;
     if (!on_device) { ISPH_CHECK(R->stage.reserve((size_t)n)); d = R->stage.p; }
     if (J->order)
-      hipLaunchKernelGGL((k_perm_scatter<double>), dim3(perm_grid(n)), dim3(kBlock), 0, ctx->stream, n, (const int *)J->order->perm.p,
-                         src, d);
+      order_scatter(ctx, *J->order, n, 1, src, 0, d, 0);
     else
       ISPH_CHECK_HIP(hipMemcpyAsync(d, src, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
     if (!on_device) ISPH_CHECK_HIP(hipMemcpyAsync(out, d, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
@@ -387,7 +385,7 @@ int isph_solve_poisson_boltzmann(isph_ctx *ctx, isph_mat *J, const isph_pb_param
     if (rc == ISPH_SUCCESS && (!M || age >= prm.prec_max_age)) {  // "Preconditioner Reuse Policy" = Reuse
       // prec_refresh: the preconditioner of the first step was created while the pattern was held; its values are redone
       // where the type can be refactored (an SA-AMG across ranks or on a matrix with a halo is not held: rebuilt)
-      if (M && prm.prec_refresh && (M->type == 2 || (M->type == 3 && M->amg && M->amg->held))) {
+      if (M && prm.prec_refresh && (prec_ilu(M) || (prec_amg(M) && M->amg->held))) {
         rc = isph_prec_refactor(ctx, M, J);
         ++info->prec_refreshes;
       } else {

@@ -16,8 +16,9 @@
 
 namespace isph {
 
-int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, double *z);  // isph_capi.hip
-int prec_apply_multi_dev(isph_ctx *ctx, const isph_prec *M, int K, const double *const *rs, double *const *zs);  // isph_capi.hip
+// prec.hpp, which includes this file through the kinds' headers
+inline int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, double *z);
+inline int prec_apply_multi_dev(isph_ctx *ctx, const isph_prec *M, int K, const double *const *rs, double *const *zs);
 
 inline int allreduce_inplace(isph_ctx *ctx, double *d, int count) {
   return comm_allreduce(ctx, d, count, /*sum*/ 0, ctx->stream);
