@@ -2126,3 +2126,10 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 
 // ghost atoms and the full neighbour list of one rank (isph_nlist_build, isph_nlist_info, isph_nlist_get, isph_nlist_destroy)
 #include "neighbours.hpp"
+
+// ghost rows, zero-mean pressure and the observables of a time step (isph_ghost_fill, isph_zero_mean_pressure, isph_status,
+// isph_tgv_error)
+#include "step_ops.hpp"
+
+// the device-resident time step of incompressible Navier-Stokes (isph_ins_*)
+#include "ins_step.hpp"

@@ -37,6 +37,10 @@ EXPORTS = [
     "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
     "isph_recycle_create", "isph_recycle_destroy", "isph_recycle_reset", "isph_recycle_info", "isph_recycle_export", "isph_recycle_import",
     "isph_solve_recycle", "isph_dense_tall_gemm", "isph_dense_block_gram",
+    "isph_ghost_fill", "isph_zero_mean_pressure", "isph_status", "isph_tgv_error",
+    "isph_ins_params_default", "isph_ins_create", "isph_ins_destroy", "isph_ins_set_state", "isph_ins_set_list", "isph_ins_rebuild",
+    "isph_ins_sizes", "isph_ins_get", "isph_ins_pre", "isph_ins_view", "isph_ins_force", "isph_ins_add_force", "isph_ins_solve",
+    "isph_ins_advance", "isph_ins_shift", "isph_ins_diagnostics", "isph_ins_run",
 ]
 
 
@@ -323,6 +327,32 @@ def lib():
                                            C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_int, C.c_int]
         L.isph_dense_block_gram.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_void_p,
                                             C.c_longlong, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int]
+        L.isph_ghost_fill.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_zero_mean_pressure.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int]
+        L.isph_status.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                  C.c_int]
+        L.isph_tgv_error.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_double, C.c_double, C.c_void_p, C.c_int]
+        L.isph_ins_params_default.argtypes = [C.c_void_p]
+        L.isph_ins_params_default.restype = None
+        L.isph_ins_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.isph_ins_destroy.argtypes = [C.c_void_p]
+        L.isph_ins_destroy.restype = None
+        L.isph_ins_set_state.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+        L.isph_ins_set_list.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int]
+        for fn in (L.isph_ins_rebuild, L.isph_ins_pre, L.isph_ins_advance):
+            fn.argtypes = [C.c_void_p]
+        L.isph_ins_sizes.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_ins_get.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_ins_view.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_ins_force.argtypes = [C.c_void_p]
+        L.isph_ins_force.restype = C.c_void_p
+        L.isph_ins_add_force.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_ins_solve.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_ins_shift.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_ins_diagnostics.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+        L.isph_ins_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1856,6 +1886,273 @@ class NeighbourList:
     def close(self):
         if self.h:
             lib().isph_nlist_destroy(self.ctx.h, self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- the glue of a time step: ghost rows, zero-mean pressure, observables -------------------------------------------
+
+KIND_FLUID, KIND_SOLID, KIND_BUFFER_DIRICHLET, KIND_BUFFER_NEUMANN = 99, 12, 32, 64
+
+
+def ghost_fill(ctx, nlocal, owner, a):
+    """isph_ghost_fill: rows i >= nlocal of a [nall] or [nall, ncomp] receive row owner[i], in place (numpy or device
+    tensor, owner on the same side).  nall is len(owner)."""
+    owner = _i32(owner)
+    nlocal = int(nlocal)
+    nall = int(owner.numel()) if _is_torch(owner) else int(owner.size)
+    if not _is_torch(a) and not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
+        raise ValueError("a: a C-contiguous float64 array is updated in place")
+    _f64(a)
+    dev = _on_device(owner, a)
+    if not 0 <= nlocal <= nall:
+        raise OperandError("nlocal = %d outside [0, nall = %d]" % (nlocal, nall))
+    if a.ndim not in (1, 2) or (nall > 0 and int(a.shape[0]) != nall):
+        raise OperandError("a: %s given, [nall = %d] or [nall][ncomp] needed" % (tuple(a.shape), nall))
+    ncomp = 1 if a.ndim == 1 else int(a.shape[1])
+    _need(a, nall * ncomp, "a [nall][ncomp]")
+    _check(lib().isph_ghost_fill(ctx.h if ctx is not None else None, nlocal, nall, _ptr(owner), ncomp, _ptr(a), dev))
+    return a
+
+
+def zero_mean_pressure(ctx, nlocal, type, kinds, f, update=True, want_mean=True):
+    """isph_zero_mean_pressure: in place on f [nall] (numpy or device tensor, like type); kinds = the kind of type 1, 2,
+    ... as in particles_view (None: all Fluid).  Returns the mean (None when want_mean is False: nothing is read back)."""
+    typ = _i32(type)
+    nall = int(typ.numel()) if _is_torch(typ) else int(typ.size)
+    nlocal = int(nlocal)
+    if kinds is None:
+        ntypes = 1 if nall == 0 else (int(typ.max().item()) if _is_torch(typ) else int(np.max(typ)))
+        kinds = [KIND_FLUID] * ntypes
+    ntypes = len(kinds)
+    kind = np.ascontiguousarray([0] + list(kinds), dtype=np.int32)
+    if not _is_torch(f) and not (isinstance(f, np.ndarray) and f.dtype == np.float64 and f.flags.c_contiguous):
+        raise ValueError("f: a C-contiguous float64 array is updated in place")
+    _f64(f)
+    dev = _on_device(typ, f)
+    if not 0 <= nlocal <= nall:
+        raise OperandError("nlocal = %d outside [0, nall = %d]" % (nlocal, nall))
+    _need(f, nall, "f [nall]")
+    mean = C.c_double(0.0)
+    _check(lib().isph_zero_mean_pressure(ctx.h if ctx is not None else None, nlocal, nall, _ptr(typ), _ptr(kind), ntypes,
+                                         _ptr(f), int(bool(update)), C.byref(mean) if want_mean else None, dev))
+    return mean.value if want_mean else None
+
+
+STATUS_FIELDS = ("count", "sum_vx", "sum_vy", "sum_vz", "volume", "mass", "kinetic_energy", "vmax")
+
+
+def status(ctx, nlocal, x, type, vfrac, v, rho, type_mask=-1, centre=(0.0, 0.0, 0.0), radius=0.0):
+    """isph_status == compute isph/status over the owned rows: numpy array of the eight numbers STATUS_FIELDS names.
+    x, v [>= nlocal, 3]; type, vfrac, rho [>= nlocal]; all numpy or all device tensors."""
+    n = int(nlocal)
+    x, v, vfrac, rho, typ = _f64(x), _f64(v), _f64(vfrac), _f64(rho), _i32(type)
+    dev = _on_device(x, v, vfrac, rho, typ)
+    _need(x, 3 * n, "x [nlocal][3]"); _need(v, 3 * n, "v [nlocal][3]"); _need(vfrac, n, "vfrac [nlocal]")
+    _need(rho, n, "rho [nlocal]"); _need(typ, n, "type [nlocal]")
+    pv = _Particles()
+    pv.dim, pv.nlocal, pv.nall = 3, n, n
+    pv.x, pv.type, pv.vfrac = _ptr(x), _ptr(typ), _ptr(vfrac)
+    c = (C.c_double * 3)(*[float(t) for t in centre])
+    out = (C.c_double * 8)()
+    mask = int(type_mask) & 0xFFFFFFFF
+    mask = mask - (1 << 32) if mask >= (1 << 31) else mask
+    _check(lib().isph_status(ctx.h if ctx is not None else None, C.byref(pv), mask, _ptr(v), _ptr(rho), c, float(radius), out,
+                             dev))
+    return np.array(out[:], dtype=np.float64)
+
+
+def tgv_error(ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim=2):
+    """isph_tgv_error == the error of fix isph/tgv: (p_err, p_norm, u_err, u_norm).  x, vnp1 [>= nlocal, 3]; p, rho, nu
+    [>= nlocal]; all numpy or all device tensors."""
+    n = int(nlocal)
+    x, vnp1, p, rho, nu = _f64(x), _f64(vnp1), _f64(p), _f64(rho), _f64(nu)
+    dev = _on_device(x, vnp1, p, rho, nu)
+    _need(x, 3 * n, "x [nlocal][3]"); _need(vnp1, 3 * n, "vnp1 [nlocal][3]"); _need(p, n, "p [nlocal]")
+    _need(rho, n, "rho [nlocal]"); _need(nu, n, "nu [nlocal]")
+    out = (C.c_double * 4)()
+    _check(lib().isph_tgv_error(ctx.h if ctx is not None else None, n, int(dim), _ptr(x), _ptr(vnp1), _ptr(p), _ptr(rho),
+                                _ptr(nu), float(t), float(umax), out, dev))
+    return tuple(out[:])
+
+
+# ---- the time step of incompressible Navier-Stokes, resident on the device ------------------------------------------
+
+class _InsParams(C.Structure):
+    _fields_ = [("dim", C.c_int), ("kernel", C.c_int), ("antisym", C.c_int), ("theta", C.c_double), ("dt", C.c_double),
+                ("incremental_pressure", C.c_int), ("singular_mode", C.c_int), ("g", C.c_double * 3), ("ntypes", C.c_int),
+                ("kind", C.c_void_p), ("h", C.c_void_p), ("cutsq", C.c_void_p),
+                ("prec_helmholtz", C.c_char_p), ("helmholtz_block_size", C.c_int),
+                ("prec_poisson", C.c_char_p), ("poisson_block_size", C.c_int), ("solver", SolverParams),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("periodic", C.c_int * 3), ("cut", C.c_double),
+                ("shift", C.c_double), ("shiftcut", C.c_double), ("nonfluidweight", C.c_double),
+                ("block_helmholtz", C.c_int), ("morris_holmes", C.c_int), ("normals_bd_coord", C.c_int),
+                ("normals_use_part", C.c_int), ("recycle", C.c_void_p), ("tgv_umax", C.c_double),
+                ("status_type_mask", C.c_int), ("status_centre", C.c_double * 3), ("status_radius", C.c_double)]
+
+
+class InsInfo(C.Structure):
+    """isph_ins_info: the SolveInfo of the Helmholtz and of the Poisson solve of one step"""
+    _fields_ = [("helmholtz", SolveInfo), ("poisson", SolveInfo)]
+
+
+class InsParams:
+    """isph_ins_params.  h and cut are the scalars of the generators (one smoothing length, one pair cut; the tables of
+    the ABI are filled with them), kinds the kind of type 1, 2, ... (None: one Fluid type); box = (lo, hi, periodic) and
+    list_cut for InsStep.rebuild.  Every other keyword is a field of the struct (theta, dt, antisym, singular_mode,
+    incremental_pressure, g, prec_helmholtz, helmholtz_block_size, prec_poisson, poisson_block_size, solver, shift,
+    shiftcut, nonfluidweight, tgv_umax, status_type_mask, status_centre, status_radius, and the refused block_helmholtz,
+    morris_holmes, normals_bd_coord, normals_use_part, recycle)."""
+
+    def __init__(self, dim, dt, h, cut, kinds=None, kernel="wendland", box=None, list_cut=None, **kw):
+        s = self.c = _InsParams()
+        lib().isph_ins_params_default(C.byref(s))
+        kinds = [KIND_FLUID] if kinds is None else list(kinds)
+        nt = len(kinds)
+        self._kind = np.ascontiguousarray([0] + kinds, dtype=np.int32)
+        self._h = np.full((nt + 1, nt + 1), float(h))
+        self._cutsq = np.full((nt + 1, nt + 1), float(cut) ** 2)
+        s.dim, s.dt, s.kernel, s.ntypes = int(dim), float(dt), KERNELS[kernel], nt
+        s.kind, s.h, s.cutsq = self._kind.ctypes.data, self._h.ctypes.data, self._cutsq.ctypes.data
+        if box is not None:
+            lo, hi, per = box
+            for a in range(3):
+                s.lo[a], s.hi[a], s.periodic[a] = float(lo[a]), float(hi[a]), int(per[a])
+            s.cut = float(cut if list_cut is None else list_cut)
+        for k, v in kw.items():
+            if k in ("prec_helmholtz", "prec_poisson"):
+                setattr(s, k, v.encode())
+            elif k in ("g", "status_centre"):
+                for a in range(3):
+                    getattr(s, k)[a] = float(v[a])
+            elif k == "recycle":
+                s.recycle = v.h if hasattr(v, "h") else v
+            elif k not in dict(_InsParams._fields_):
+                raise TypeError("InsParams: unknown field %r" % k)
+            else:
+                setattr(s, k, v)
+
+
+DIAG_FIELDS = ("p_err", "p_norm", "u_err", "u_norm") + STATUS_FIELDS + ("iters_helmholtz", "iters_poisson",
+                                                                        "converged_helmholtz", "converged_poisson")
+_INS_FIELDS = {"x": (3, np.float64), "v": (3, np.float64), "vstar": (3, np.float64), "f": (3, np.float64),
+               "normal": (3, np.float64), "p": (1, np.float64), "dp": (1, np.float64), "rho": (1, np.float64),
+               "nu": (1, np.float64), "vfrac": (1, np.float64), "pnd": (1, np.float64), "Gc": (None, np.float64),
+               "Lc": (None, np.float64), "type": (1, np.int32), "owner": (1, np.int32)}
+
+
+class InsStep:
+    """isph_ins: one rank's Navier-Stokes state on the device; the methods are the phases of the reference
+    (include/isph_hip.h).  Operands are numpy arrays or device tensors."""
+
+    def __init__(self, ctx, params):
+        L = lib()
+        self.ctx, self.params, self.dim = ctx, params, int(params.c.dim)
+        self.h = C.c_void_p()
+        _check(L.isph_ins_create(ctx.h, C.byref(params.c), C.byref(self.h)))
+
+    def set_state(self, x, v, p, type, rho, nu):
+        x, v, p, rho, nu, typ = _f64(x), _f64(v), _f64(p), _f64(rho), _f64(nu), _i32(type)
+        dev = _on_device(x, v, p, rho, nu, typ)
+        n = int(typ.numel()) if _is_torch(typ) else int(typ.size)
+        _need(x, 3 * n, "x [nlocal][3]"); _need(v, 3 * n, "v [nlocal][3]"); _need(p, n, "p [nlocal]")
+        _need(rho, n, "rho [nlocal]"); _need(nu, n, "nu [nlocal]")
+        _check(lib().isph_ins_set_state(self.h, n, _ptr(x), _ptr(v), _ptr(p), _ptr(typ), _ptr(rho), _ptr(nu), dev))
+
+    def set_list(self, x_all, owner, neigh_ptr, neigh_idx):
+        """the caller's ghosts (x_all [nall, 3]), owners [nall] and full list (int32 or int64 offsets [nlocal + 1])"""
+        x_all, owner, nidx = _f64(x_all), _i32(owner), _i32(neigh_idx)
+        wide = str(neigh_ptr.dtype) in ("int64", "torch.int64")
+        nptr = (neigh_ptr if _is_torch(neigh_ptr) else np.ascontiguousarray(neigh_ptr)) if wide else _i32(neigh_ptr)
+        dev = _on_device(x_all, owner, nptr, nidx)
+        nall = int(owner.numel()) if _is_torch(owner) else int(owner.size)
+        nl = self.sizes()["nlocal"]
+        _need(x_all, 3 * nall, "x_all [nall][3]"); _need(nptr, nl + 1, "neigh_ptr [nlocal+1]")
+        last = int(nptr[nl].item()) if _is_torch(nptr) else int(nptr[nl])
+        _need(nidx, last, "neigh_idx [neigh_ptr[nlocal]]")
+        _check(lib().isph_ins_set_list(self.h, nall, _ptr(x_all), _ptr(owner), None if wide else _ptr(nptr),
+                                       _ptr(nptr) if wide else None, _ptr(nidx), dev))
+
+    def rebuild(self):
+        _check(lib().isph_ins_rebuild(self.h))
+
+    def sizes(self):
+        a = (C.c_longlong * 6)()
+        _check(lib().isph_ins_sizes(self.h, a))
+        return dict(nlocal=int(a[0]), nall=int(a[1]), entries=int(a[2]), step=int(a[3]), pre_done=bool(a[4]),
+                    solid_present=bool(a[5]))
+
+    def get(self, name, ghosts=False, device=False):
+        """a copy of a field: numpy array, or a device tensor with device=True"""
+        if name not in _INS_FIELDS:
+            raise ValueError("unknown field %r" % name)
+        per, dt = _INS_FIELDS[name]
+        d = self.dim
+        per = {"Gc": d * d, "Lc": d * (d + 1) // 2}.get(name, per)
+        sz = self.sizes()
+        rows = sz["nall"] if ghosts else sz["nlocal"]
+        shape = (rows,) if per == 1 else (rows, per)
+        if device:
+            import torch
+            out = torch.zeros(shape, dtype=torch.float64 if dt is np.float64 else torch.int32, device="cuda")
+        else:
+            out = np.zeros(shape, dtype=dt)
+        _check(lib().isph_ins_get(self.h, name.encode(), int(ghosts), _ptr(out), int(device)))
+        return out
+
+    def pre(self):
+        _check(lib().isph_ins_pre(self.h))
+
+    def view(self):
+        """the isph_particles of the state (device pointers) for the force entry points of the C ABI"""
+        pv = _Particles()
+        _check(lib().isph_ins_view(self.h, C.byref(pv)))
+        return pv
+
+    def force_ptr(self):
+        """device address of the force [nall][3] the Helmholtz right-hand side reads (0 before pre)"""
+        return int(lib().isph_ins_force(self.h) or 0)
+
+    def add_force(self, f):
+        """isph_ins_add_force: f [nlocal, 3] or [nall, 3] (numpy or device tensor) is added to the force of the step"""
+        f = _f64(f)
+        sz = self.sizes()
+        if f.ndim != 2 or int(f.shape[1]) != 3 or int(f.shape[0]) not in (sz["nlocal"], sz["nall"]):
+            raise OperandError("f: [nlocal][3] or [nall][3] needed, %s given" % (tuple(f.shape),))
+        _check(lib().isph_ins_add_force(self.h, int(f.shape[0]), _ptr(f), _on_device(f)))
+
+    def solve(self):
+        info = InsInfo()
+        _check(lib().isph_ins_solve(self.h, C.byref(info)))
+        return info
+
+    def advance(self):
+        _check(lib().isph_ins_advance(self.h))
+
+    def shift(self):
+        vmax = C.c_double(0.0)
+        _check(lib().isph_ins_shift(self.h, C.byref(vmax)))
+        return vmax.value
+
+    def diagnostics(self, t):
+        out = (C.c_double * 12)()
+        _check(lib().isph_ins_diagnostics(self.h, float(t), out))
+        return np.array(out[:], dtype=np.float64)
+
+    def run(self, nsteps, diag=True):
+        """isph_ins_run; returns the [nsteps, 16] diagnostics (columns DIAG_FIELDS) or None"""
+        out = np.zeros((int(nsteps), 16)) if diag else None
+        _check(lib().isph_ins_run(self.h, int(nsteps), _ptr(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().isph_ins_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

@@ -1210,6 +1210,163 @@ int isph_nlist_get(isph_ctx *ctx, const isph_nlist *nl, double *x_all, int *owne
 
 int isph_nlist_destroy(isph_ctx *ctx, isph_nlist *nl);
 
+/* ---- the glue of a time step: ghost rows, zero-mean pressure, observables ----------------------------------------- */
+
+/* What a time step needs between the neighbour sweeps, and the numbers the reference's scripts record, for ONE rank: every
+ * entry point of this section refuses a context with a communicator (isph_ctx_create_dist / _hostcomm) by name.  All
+ * pointers [h|d] per on_device unless marked host; work buffers come from the library's pool; everything runs on the
+ * context's stream.  The sums are two-stage reductions over a partition that depends on the row count alone, summed in a
+ * fixed order, without floating-point atomics (the discipline of the solvers' multi-dot): the bits of a result do not
+ * change from run to run.
+ *
+ * isph_ghost_fill: forward_comm_pair for the periodic images of one rank (what PairISPH::pack_forward_comm /
+ * unpack_forward_comm do through Comm when every ghost is an image of an owned atom, pair_isph.cpp:1924-2125):
+ * row i >= nlocal of a [nall][ncomp] receives row owner[i], in place.  Any ncomp >= 1.  nall == nlocal launches nothing
+ * (owner and a may then be NULL).  An owner[i] outside [0, nlocal) anywhere fails the call -- checked on the device, one
+ * flag is read back; the rows of valid owners may have been written by then. */
+int isph_ghost_fill(isph_ctx *ctx, int nlocal, int nall, const int *owner /*[nall]*/, int ncomp,
+                    double *a /*[nall][ncomp], in place*/, int on_device);
+
+/* PairISPH::computeZeroMeanPressure (ref: pair_isph.cpp:422-464).  Owned rows whose kind is exactly Solid (12) are set
+ * to 0, whatever they held, and left out; mean = sum / count over the other owned rows; with update != 0 the mean is
+ * subtracted from all nall entries whose kind is not Solid (ghost Solid rows are left as they are).  kind: [ntypes + 1],
+ * host always, as in isph_particles.  The mean stays on the device between the kernels and is read back only when
+ * mean_out (host) is not NULL.
+ * Departure: a count of 0 gives mean 0 and subtracts nothing (the reference divides by zero there). */
+int isph_zero_mean_pressure(isph_ctx *ctx, int nlocal, int nall, const int *type /*[nall]*/, const int *kind /*[h]*/,
+                            int ntypes, double *f /*[nall], in place*/, int update, double *mean_out /*host, may be NULL*/,
+                            int on_device);
+
+/* ComputeISPH_Status::compute_vector (ref: compute_isph_status.cpp:141-175) over the owned rows with
+ * type_mask & (1 << (type - 1)), in one sweep: out = { count, sum vx, sum vy, sum vz, sum V, sum rho V,
+ * sum 1/2 rho V |v|^2, max |v| } with V = P->vfrac (required); the maximum is taken over the rows within `radius` of
+ * `centre`, and only when radius > 0 (0 otherwise).  Of P only nlocal, x, type and vfrac are read.  Every term is formed
+ * with the roundings of the reference's loop (no fused multiply-add); out is a host array. */
+int isph_status(isph_ctx *ctx, const isph_particles *P, int type_mask, const double *v /*[nlocal][3]*/,
+                const double *rho /*[nlocal]*/, const double centre[3] /*host*/, double radius, double out[8] /*host*/,
+                int on_device);
+
+/* FixISPH_TGV::compute_error (ref: fix_isph_tgv.cpp:76-116) for the 2-D Taylor-Green vortex at time t with amplitude
+ * umax: out = { pressure l2 error, pressure norm, velocity l2 error, velocity norm }, each sqrt(sum / nlocal).  The
+ * mean of p over all owned rows is removed from the pressure error as the reference removes it (the exact field has
+ * mean 0); the exact velocity has no z component.  x, vnp1: [nlocal][3]; p, rho, nu: [nlocal]; out is a host array.
+ * The ALE start-up branch of the reference (:93-97, which overwrites the state) is not provided. */
+int isph_tgv_error(isph_ctx *ctx, int nlocal, int dim, const double *x, const double *vnp1, const double *p,
+                   const double *rho, const double *nu, double t, double umax, double out[4] /*host*/, int on_device);
+
+/* ---- the time step of incompressible Navier-Stokes, resident on the device ------------------------------------------ */
+
+/* An isph_ins owns ONE rank's state on the device -- x, v, vstar, the force f and the wall normals [nall][3]; p, dp, rho,
+ * nu, vfrac, pnd, type [nall]; Gc, Lc [nlocal][.]; the owner map and the full neighbour list -- and chains the entry
+ * points above into the phases of the reference:
+ *
+ *   PairISPH::compute (pair_isph.cpp:1241-1380)          isph_ins_pre  (computePre, body-force reset)
+ *                                                        [the caller's forces through isph_ins_view / isph_ins_force]
+ *                                                        isph_ins_solve (computeIncompressibleNavierStokes, :910-1034)
+ *   FixISPH::final_integrate -> advanceTime              isph_ins_advance (pair_isph_corrected.cpp:1172-1199)
+ *   FixISPH_Shift::final_integrate                       isph_ins_shift   (fix_isph_shift.cpp:146-163)
+ *   LAMMPS between two compute() calls                   isph_ins_set_list (the caller's) or isph_ins_rebuild
+ *
+ * Every neighbour sweep, assembly and solve is the call a user of this header would make with device operands; the glue
+ * is isph_ghost_fill, isph_zero_mean_pressure and two transposes.  During a step only what those calls read back is
+ * read back: the two counts of a list build, the solve infos, the shift's vmax; the owner map is validated once when a
+ * list is taken; the zero-mean value stays on the device.
+ *
+ * Out of scope, refused by name: a context with a communicator (more than one rank); block Helmholtz
+ * (isph_assemble_block_helmholtz / isph_solve_block); the MorrisHolmes boundary; bd_coord and use_part wall normals; a
+ * recycle handle; a context in hold-pattern mode (isph_ctx_hold_pattern).  Solid particles need antisym = 0 (the wall
+ * normals read Gc).
+ * Departures: isph_zero_mean_pressure's (count 0); G and L are not formed for antisym = 1, which never reads them (the
+ * reference's computePre forms them always); the shift's fixed types are those of kind Solid.
+ * Call isph_ins_params_default FIRST and then change fields: the struct grows at its tail.  The tables and the strings
+ * are copied by isph_ins_create. */
+typedef struct isph_ins isph_ins;
+typedef struct {
+  int dim;                   /* 2 | 3 (default 3)                                                                    */
+  int kernel;                /* 0 Wendland, 1 Quintic, 2 Cubic                                                       */
+  int antisym;               /* 1 = the momentum-preserving family (default), 0 = the corrected one                  */
+  double theta;              /* ns.theta (default 0.5); |theta| < 1e-24: the Helmholtz right-hand side is the result  */
+  double dt;                 /* time step; required                                                                  */
+  int incremental_pressure;  /* ns.is_incremental_pressure_used (default 1)                                          */
+  int singular_mode;         /* 0 NotSingular, 1 NullSpace (default), 2 PinZero, 3 DoubleDiag                        */
+  double g[3];               /* gravity                                                                              */
+  int ntypes;                /* host tables as in isph_particles: kind [ntypes+1], h and cutsq [(ntypes+1)^2]        */
+  const int *kind;
+  const double *h, *cutsq;
+  const char *prec_helmholtz;   /* a type string of isph_prec_create (default "bjacobi-ilu0") ...                     */
+  int helmholtz_block_size;     /* ... and its block_size (default 512)                                               */
+  const char *prec_poisson;     /* the same for the Poisson solve; "sa-amg" on a NullSpace system gets the normalised  */
+  int poisson_block_size;       /* null mask as its null vector (isph_prec_create_amg)                                 */
+  isph_solver_params solver;    /* both solves                                                                        */
+  double lo[3], hi[3];          /* the box of isph_ins_rebuild (isph_nlist_build) ...                                 */
+  int periodic[3];
+  double cut;                   /* ... and its list radius; 0 (default): isph_ins_rebuild is not available            */
+  double shift, shiftcut, nonfluidweight;  /* fix isph/shift; shift = 0 (default): isph_ins_run does not shift        */
+  int block_helmholtz, morris_holmes, normals_bd_coord, normals_use_part;  /* out of scope: non-zero is refused        */
+  const void *recycle;                                                     /* out of scope: non-NULL is refused        */
+  double tgv_umax;              /* the diagnostics of isph_ins_run: umax of isph_tgv_error (default 0.1) ...          */
+  int status_type_mask;         /* ... and type_mask (default -1: every type), centre, radius of isph_status          */
+  double status_centre[3], status_radius;
+} isph_ins_params;
+void isph_ins_params_default(isph_ins_params *p);
+typedef struct {
+  isph_solve_info helmholtz, poisson;   /* helmholtz.converged = 1 and 0 iterations when theta = 0 (no solve) */
+} isph_ins_info;
+
+int isph_ins_create(isph_ctx *ctx, const isph_ins_params *prm, isph_ins **S);
+void isph_ins_destroy(isph_ins *S);
+/* x, v [nlocal][3]; p, rho, nu, type [nlocal] of the owned particles, [h|d].  Drops the list.  The null mask of the
+ * Poisson solve, !(kind & Solid), is made here (a host array, because isph_solve takes it from the host): with device
+ * operands `type` is copied back once. */
+int isph_ins_set_state(isph_ins *S, int nlocal, const double *x, const double *v, const double *p, const int *type,
+                       const double *rho, const double *nu, int on_device);
+/* The caller's ghosts and full list, what LAMMPS hands to PairISPH::compute: x_all [nall][3] (rows >= nlocal are read),
+ * owner [nall] (periodic images of owned atoms only), neigh_ptr [nlocal+1] or neigh_ptr64 (one may be NULL), neigh_idx;
+ * all copied.  v, p, rho, nu and type of the ghosts are gathered through the owner map. */
+int isph_ins_set_list(isph_ins *S, int nall, const double *x_all, const int *owner, const int *neigh_ptr,
+                      const long long *neigh_ptr64, const int *neigh_idx, int on_device);
+/* Ghosts and list from the owned positions with isph_nlist_build (wrap on); the positions never leave the device. */
+int isph_ins_rebuild(isph_ins *S);
+/* info: [0] nlocal [1] nall [2] list entries (-1: no list) [3] steps isph_ins_run has completed [4] 1 between
+ * isph_ins_pre and the next move [5] 1 when a Solid particle is present */
+int isph_ins_sizes(const isph_ins *S, long long info[6]);
+/* Copies a field out, [h|d]: "x" "v" "vstar" "f" "normal" ([.][3]), "p" "dp" "rho" "nu" "vfrac" "pnd" ([.]), "Gc"
+ * ([nlocal][dim*dim]) "Lc" ([nlocal][dimL]), "type" "owner" (int); nlocal rows, or nall with with_ghosts. */
+int isph_ins_get(isph_ins *S, const char *name, int with_ghosts, void *out, int on_device);
+/* computePre (pair_isph_corrected.cpp:302-313): holds the neighbour layout for the step (isph_ctx_hold_neighbours),
+ * volumes and their ghosts, G and L unless antisym, wall normals and pnd (isph_compute_normals) when a Solid kind is
+ * present, f = 0.  Fails without a list.  The hold is the driver's from here on: taking a new list, isph_ins_set_state and
+ * isph_ins_destroy release it, so a caller does not hold the layout of the same context for lists of its own meanwhile. */
+int isph_ins_pre(isph_ins *S);
+/* After isph_ins_pre: the particle view of the state (device pointers, valid until the next list) and the force
+ * [nall][3] the Helmholtz right-hand side reads -- the caller adds surface tension, electrostatic force or random stress
+ * with the entry points above, where the reference adds to atom->f. */
+int isph_ins_view(const isph_ins *S, isph_particles *P);
+double *isph_ins_force(isph_ins *S);
+/* f [rows][3] [h|d], rows = nlocal or nall, is added to that force: for callers that hold a force of their own. */
+int isph_ins_add_force(isph_ins *S, int rows, const double *f, int on_device);
+/* computeIncompressibleNavierStokes (pair_isph.cpp:910-1034): Helmholtz assembly with x0 = v and the dim-column solve
+ * (theta = 0: the right-hand side is copied); vstar with its ghosts (one kernel); Poisson assembly in singular_mode, wall
+ * Neumann rows from the normals; the solve from zero with the null mask when NullSpace; ghosts of dp; zero-mean pressure
+ * when incremental; isph_correct_velocity_pressure; ghosts of the corrected vstar.  Preconditioners are built and
+ * destroyed around each solve, as the reference does.  Non-convergence is reported in info, not an error.  Fails before
+ * isph_ins_pre. */
+int isph_ins_solve(isph_ins *S, isph_ins_info *info /*may be NULL*/);
+/* advanceTime: isph_advance_begin, the ghosts of its dp, isph_advance_end over owned particles AND ghosts (as
+ * functor_advance_time_end.h:36-72 does), so a ghost moves with its owner. */
+int isph_ins_advance(isph_ins *S);
+/* FixISPH_Shift::final_integrate: computePre on the moved particles with the list of the step (volumes; G and L unless
+ * antisym), then isph_shift_particles; vmax_out (host, may be NULL) = the max fluid speed it used. */
+int isph_ins_shift(isph_ins *S, double *vmax_out);
+/* out[0..3] = isph_tgv_error of (x, vstar, p) at time t, out[4..11] = isph_status of (x, vstar, rho, vfrac): the numbers
+ * fix isph/tgv and compute isph/status print between compute() and advanceTime.  After isph_ins_solve. */
+int isph_ins_diagnostics(isph_ins *S, double t, double out[12] /*host*/);
+/* nsteps times: isph_ins_rebuild (when the particles have moved since the list was taken, or there is none), pre, solve,
+ * diagnostics, advance, shift when shift > 0.  diag: host [nsteps][16] or NULL; a row is isph_ins_diagnostics at
+ * t = step dt (steps count from 1 over the life of the state), then the Helmholtz and Poisson iteration counts and their
+ * converged flags. */
+int isph_ins_run(isph_ins *S, int nsteps, double *diag);
+
 #ifdef __cplusplus
 }
 #endif
