@@ -236,6 +236,22 @@ def build_cpp_amg_ilu_test(force=False):
     return CPP_AMG_ILU_TEST
 
 
+CPP_GMRES_POLY_TEST = os.path.join(ROOT, "tests", "cpp", "test_gmres_poly_wrappers")
+
+
+def build_cpp_gmres_poly_test(force=False):
+    """C++ driver of PrecondWrapper_Ifpack's "Precond Type" = "GMRES Polynomial" (host/*.h), linked like build_cpp_test; used by
+    tests/test_gpu_gmres_poly_wrappers.py."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_gmres_poly_wrappers.cpp")
+    host = os.path.join(PKG, "host")
+    deps = [src] + [os.path.join(host, f) for f in os.listdir(host)] + [os.path.join(INC, "isph_hip.h")]
+    if force or _stale(CPP_GMRES_POLY_TEST, deps):
+        build_hip()
+        _run(["g++", "-O2", "-std=c++17", "-I", INC, "-I", host, "-o", CPP_GMRES_POLY_TEST, src,
+              "-L", PKG, "-lisph_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    return CPP_GMRES_POLY_TEST
+
+
 RANK_THREADS = os.path.join(ROOT, "tests", "cpp", "librank_threads.so")
 
 
@@ -292,4 +308,4 @@ def build_all(force=False):
     return (build_host(force), build_hip(force), build_cpp_test(force), build_cpp_mpi(force), build_rank_threads(force),
             build_cpp_chebyshev_test(force), build_cpp_chebyshev_f32_test(force), build_cpp_ilu_f32_test(force), build_cpp_basis_f32_test(force),
             build_cpp_pattern_hold_test(force), build_cpp_eig_estimate_test(force), build_cpp_amg_cycle_f32_test(force),
-            build_cpp_amg_ilu_test(force))
+            build_cpp_amg_ilu_test(force), build_cpp_gmres_poly_test(force))

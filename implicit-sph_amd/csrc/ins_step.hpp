@@ -5,6 +5,7 @@
 // below.  Included by isph_capi.hip.
 #pragma once
 #include <cmath>
+#include <cstdlib>
 #include <string>
 #include <vector>
 
@@ -194,7 +195,8 @@ inline void ins_view(const isph_ins *S, bool with_pre, isph_particles *P) {
 
 inline int ins_make_prec(isph_ins *S, const isph_mat *A, const std::string &type, int block, bool nullspace, isph_prec **M) {
   isph_ctx *ctx = S->ctx;
-  if (type == "sa-amg" && nullspace) {
+  const bool poly = isph_prec_type_kind(type.c_str()) == 7;   // "gmres-poly<d>"
+  if ((type == "sa-amg" || poly) && nullspace) {
     isph_amg_params ap;
     isph_amg_params_default(&ap);
     const int n = S->nlocal;
@@ -203,6 +205,12 @@ inline int ins_make_prec(isph_ins *S, const isph_mat *A, const std::string &type
     if (n > 0)
       hipLaunchKernelGGL(k_ins_null_vector, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, n, S->prm.ntypes,
                          (const int *)S->type.p, (const int *)S->dkind.p, val, S->nullvec.p);
+    if (poly) {   // the polynomial of the string's degree, its set-up projected with the driver's null vector
+      isph_poly_params pp;
+      isph_poly_params_default(&pp);
+      pp.degree = atoi(type.c_str() + 10);
+      return isph_prec_create_gmres_poly(ctx, A, &pp, S->nullvec.p, 1, M);
+    }
     return isph_prec_create_amg(ctx, A, &ap, S->nullvec.p, 1, M);
   }
   return isph_prec_create(ctx, A, type.c_str(), block, M);

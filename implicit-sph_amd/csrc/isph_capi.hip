@@ -1160,6 +1160,39 @@ int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double 
   return ISPH_SUCCESS;
 }
 
+/* ---- GMRES polynomial in D^-1 A ---------------------------------------- */
+
+void isph_poly_params_default(isph_poly_params *p) { p->degree = 4; }
+
+int isph_prec_create_gmres_poly(isph_ctx *ctx, const isph_mat *A, const isph_poly_params *prm, const double *nullvec, int on_device,
+                                isph_prec **Mout) {
+  ISPH_REQUIRE(ctx && A && Mout, "NULL argument");
+  isph_poly_params def;
+  isph_poly_params_default(&def);
+  if (!prm) prm = &def;
+  PrecNew M(A->S.nrow, PREC_GMRES_POLY);
+  ISPH_CHECK(prec_gmres_poly_init(ctx, A, prm, nullvec, on_device, M.M));
+  return M.finish(A->order, Mout);
+}
+
+int isph_prec_poly_info(const isph_prec *M, double *roots_re_im, double *hess, int *degree) {
+  const Poly *P = prec_poly(M);
+  ISPH_REQUIRE(P, "isph_prec_poly_info: not a GMRES polynomial preconditioner");
+  if (roots_re_im)
+    for (int k = 0; k < kPolyMaxDegree; ++k) {
+      roots_re_im[2 * k] = k < P->degree ? P->re[k] : 0.0;
+      roots_re_im[2 * k + 1] = k < P->degree ? P->im[k] : 0.0;
+    }
+  if (hess) std::copy_n(P->hess, kPolyHessLd * kPolyMaxDegree, hess);
+  if (degree) *degree = P->degree;
+  return ISPH_SUCCESS;
+}
+
+int isph_prec_type_kind(const char *type) {
+  PrecSpec s;
+  return type && parse_prec_type(type, &s) ? (int)s.kind : -1;
+}
+
 int isph_prec_value_bits(const isph_prec *M) {
   if (const Cheb *C = prec_cheb(M)) return C->value_bits;
   if (const isph_amg *G = prec_amg(M)) return G->cheb ? G->cheb_value_bits : 0;

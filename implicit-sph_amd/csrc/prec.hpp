@@ -2,7 +2,7 @@
 // is created, the type strings of isph_prec_create, the application to one or several device vectors, the operand routes
 // of the C entry points (host or device vectors, the caller's row numbering or the matrix' own) and the per-kind
 // refactor.  isph_capi.hip checks the arguments of an entry point and calls into here; the kinds themselves live in
-// ilu.hpp, amg.hpp, schwarz.hpp and chebyshev.hpp, the overlap kind below.
+// ilu.hpp, amg.hpp, schwarz.hpp, chebyshev.hpp and gmres_poly.hpp, the overlap kind below.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -11,6 +11,7 @@
 #include "chebyshev.hpp"
 #include "comm.hpp"
 #include "core.hpp"
+#include "gmres_poly.hpp"
 #include "ilu.hpp"
 #include "schwarz.hpp"
 #include "solver.hpp"
@@ -27,6 +28,7 @@ enum PrecKind : int {
   PREC_SCHWARZ = 4,      // additive Schwarz ILU(k) (schwarz.hpp)
   PREC_OVERLAP = 5,      // ILU(k) of the rank's rows + one layer of the neighbours' rows (isph_prec_create_overlap)
   PREC_CHEBYSHEV = 6,    // Chebyshev polynomial in D^-1 A (chebyshev.hpp; applies the matrix it was built from: cheb_A must outlive it)
+  PREC_GMRES_POLY = 7,   // GMRES polynomial in D^-1 A (gmres_poly.hpp; applies the matrix it was built from, like the Chebyshev kind)
   PREC_KINDS
 };
 
@@ -45,7 +47,8 @@ struct isph_prec {
   isph_schwarz *schwarz = nullptr;
   isph_overlap *ovl = nullptr;
   isph::Cheb *cheb = nullptr;
-  const isph_mat *cheb_A = nullptr;
+  const isph_mat *cheb_A = nullptr;  // ... and the matrix a GMRES polynomial applies
+  isph::Poly *poly = nullptr;
   isph::RowOrderPtr order;  // the numbering of the matrix it was built from (isph_prec_apply takes the caller's)
   // ISPH_PREC_MULTI_SINGLE=1, read when the object is created: several vectors are applied one after the other whatever
   // one-sweep form the type has (prec_apply_multi_dev) -- the cross-check and the timing baseline of those forms
@@ -76,6 +79,7 @@ inline isph_schwarz *prec_schwarz(const isph_prec *M, bool with_overlap = false)
   return M && with_overlap && M->type == PREC_OVERLAP && M->ovl ? M->ovl->inner : nullptr;
 }
 inline Cheb *prec_cheb(const isph_prec *M) { return M && M->type == PREC_CHEBYSHEV ? M->cheb : nullptr; }
+inline Poly *prec_poly(const isph_prec *M) { return M && M->type == PREC_GMRES_POLY ? M->poly : nullptr; }
 
 // ---- operands at the C ABI ----------------------------------------------------------------------------------------------
 // upload helper: returns device pointer (either the caller's or a staged copy)
@@ -180,6 +184,7 @@ inline void prec_destroy(isph_prec *M) {
   if (M->schwarz) schwarz_destroy(M->schwarz);
   if (M->ovl) overlap_destroy(M->ovl);
   if (M->cheb) cheb_destroy(M->cheb);
+  if (M->poly) poly_destroy(M->poly);
   delete M;
 }
 
@@ -260,6 +265,24 @@ inline int prec_chebyshev_init(isph_ctx *ctx, const isph_mat *A, const isph_cheb
   return ISPH_SUCCESS;
 }
 
+// the GMRES polynomial with the caller's null vector (host or device, the caller's numbering; may be NULL)
+inline int prec_gmres_poly_init(isph_ctx *ctx, const isph_mat *A, const isph_poly_params *prm, const double *nullvec, int on_device,
+                                isph_prec *M) {
+  ISPH_REQUIRE(prm->degree >= 1 && prm->degree <= kPolyMaxDegree, "GMRES polynomial: degree must be in [1,25]");
+  M->cheb_A = A;
+  DevTmp<double> tn, tp;
+  const double *dn = nullptr;
+  if (nullvec) ISPH_CHECK(stage_in(ctx, nullvec, (size_t)M->n, on_device, tn, &dn));
+  if (dn && A->order && M->n > 0) {  // the caller's null vector in the matrix' numbering
+    ISPH_CHECK(tp.reserve((size_t)M->n));
+    order_gather(ctx, *A->order, M->n, 1, dn, 0, tp.p, 0);
+    dn = tp.p;
+  }
+  ISPH_CHECK(poly_create(ctx, A, prm->degree, dn, /*collective=*/comm_active(ctx) && ctx->nranks > 1, &M->poly));
+  M->poly->held = ctx->pattern_hold;
+  return ISPH_SUCCESS;
+}
+
 // the hierarchy with the caller's null vector (host or device, the caller's numbering; may be NULL)
 inline int prec_amg_init(isph_ctx *ctx, const isph_mat *A, const isph_amg_params *prm, const double *nullvec, int on_device,
                          isph_prec *M) {
@@ -293,7 +316,7 @@ inline int prec_amg_init(isph_ctx *ctx, const isph_mat *A, const isph_amg_params
 // ---- the type strings of isph_prec_create -------------------------------------------------------------------------------
 struct PrecSpec {
   PrecKind kind = PREC_NONE;
-  int k = 0;            // "fact: level-of-fill" of the ILU kinds and of the AMG's ILU smoother; the Chebyshev degree
+  int k = 0;            // "fact: level-of-fill" of the ILU kinds and of the AMG's ILU smoother; the degree of a polynomial
   int value_bits = 64;  // 32: the "-f32" forms
   int smoother = 0;     // isph_amg_params::smoother of the AMG forms
 };
@@ -308,7 +331,8 @@ inline bool parse_prec_number(const char *&s, int lo, int hi, int *out) {
   return true;
 }
 
-// none | jacobi | bjacobi-ilu<k>[-f32] | ilu<k> | sa-amg | sa-amg-ilu<k>, k = 0..8 | chebyshev<d>[-f32], d = 1..16
+// none | jacobi | bjacobi-ilu<k>[-f32] | ilu<k> | sa-amg | sa-amg-ilu<k>, k = 0..8 | chebyshev<d>[-f32], d = 1..16 |
+// gmres-poly<d>, d = 1..25
 inline bool parse_prec_type(const char *type, PrecSpec *spec) {
   static const struct { const char *stem; PrecKind kind; int lo, hi; bool f32; int smoother; } forms[] = {  // lo > hi: no number
       {"none", PREC_NONE, 1, 0, false, 0},
@@ -322,7 +346,9 @@ inline bool parse_prec_type(const char *type, PrecSpec *spec) {
       {"sa-amg", PREC_AMG, 1, 0, false, 0},
       {"sa-amg-ilu", PREC_AMG, 0, 8, false, 4},
       // Ifpack's "Precond Type" = "Chebyshev" with "chebyshev: degree" = d and its other defaults; "-f32": value_bits = 32
-      {"chebyshev", PREC_CHEBYSHEV, 1, kChebMaxDegree, true, 0}};
+      {"chebyshev", PREC_CHEBYSHEV, 1, kChebMaxDegree, true, 0},
+      // Belos' GMRES polynomial of degree d in D^-1 A, without a null vector (isph_prec_create_gmres_poly takes one)
+      {"gmres-poly", PREC_GMRES_POLY, 1, kPolyMaxDegree, false, 0}};
   for (const auto &f : forms) {
     const size_t len = strlen(f.stem);
     if (strncmp(type, f.stem, len) != 0) continue;
@@ -343,7 +369,7 @@ inline bool parse_prec_type(const char *type, PrecSpec *spec) {
 inline int prec_create_named(isph_ctx *ctx, const isph_mat *A, const char *type, int block_size, isph_prec **Mout) {
   PrecSpec s;
   if (!parse_prec_type(type, &s))
-    return fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>|sa-amg-ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)", __FILE__, __LINE__);
+    return fail("unknown preconditioner type (none|jacobi|bjacobi-ilu<k>|ilu<k>|sa-amg-ilu<k>, k = 0..8|sa-amg|chebyshev<d>|chebyshev<d>-f32, d = 1..16|bjacobi-ilu<k>-f32)|gmres-poly<d>, d = 1..25", __FILE__, __LINE__);
   PrecNew M(A->S.nrow, s.kind);
   switch (s.kind) {
     case PREC_JACOBI: ISPH_CHECK(prec_jacobi_init(ctx, A, M.M)); break;
@@ -363,6 +389,13 @@ inline int prec_create_named(isph_ctx *ctx, const isph_mat *A, const char *type,
       prm.degree = s.k;
       prm.value_bits = s.value_bits;
       ISPH_CHECK(prec_chebyshev_init(ctx, A, &prm, M.M));
+      break;
+    }
+    case PREC_GMRES_POLY: {
+      isph_poly_params prm;
+      isph_poly_params_default(&prm);
+      prm.degree = s.k;
+      ISPH_CHECK(prec_gmres_poly_init(ctx, A, &prm, nullptr, 0, M.M));
       break;
     }
     default: break;  // PREC_NONE: the identity
@@ -414,6 +447,7 @@ inline int prec_apply_dev(isph_ctx *ctx, const isph_prec *M, const double *r, do
     case PREC_SCHWARZ: return schwarz_apply(ctx, M->schwarz, r, z);
     case PREC_OVERLAP: return overlap_apply(ctx, M->ovl, r, z);
     case PREC_CHEBYSHEV: return cheb_apply(ctx, M->cheb_A, M->cheb, r, z, /*zero_guess=*/true);
+    case PREC_GMRES_POLY: return poly_apply(ctx, M->cheb_A, M->poly, r, z);
     default: return ilu_apply(ctx, M->ilu, r, z);
   }
 }
@@ -569,6 +603,30 @@ inline int prec_refactor_chebyshev(isph_ctx *ctx, isph_prec *M, const isph_mat *
   return ISPH_SUCCESS;
 }
 
+// ... and of "gmres-poly<d>": the Arnoldi steps, the roots and the steps again, with the null vector of the create call
+inline int prec_refactor_gmres_poly(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
+  if (!M->poly || !M->poly->held)
+    return fail("refactor of \"gmres-poly<d>\": the polynomial was created while the pattern was not held (isph_ctx_hold_pattern "
+                "was off): rebuild it", __FILE__, __LINE__);
+  ISPH_CHECK(prec_refactor_rows(M, A));
+  Poly *P0 = M->poly;
+  ISPH_REQUIRE(!P0->has_null || M->order == A->order, "refactor: the matrix is not in the row numbering the null vector of the "
+                                                      "GMRES polynomial was kept in: rebuild");
+  Poly *P1 = new Poly();
+  P1->degree_in = P0->degree_in; P1->unfused = P0->unfused; P1->has_null = P0->has_null; P1->held = true;
+  std::swap(P1->nullv, P0->nullv);
+  const int rc = poly_build(ctx, A, P1, /*collective=*/comm_active(ctx) && ctx->nranks > 1);
+  if (rc != ISPH_SUCCESS) {   // the old polynomial stays whole
+    std::swap(P1->nullv, P0->nullv);
+    poly_destroy(P1);
+    return rc;
+  }
+  poly_destroy(P0);
+  M->poly = P1;
+  M->cheb_A = A;
+  return ISPH_SUCCESS;
+}
+
 // the numeric factorisation again.  The subdomains of the library's own numbering come with the matrix: they must be the
 // ones the factor was laid out for
 inline int prec_refactor_ilu(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
@@ -586,12 +644,13 @@ inline int prec_refactor_ilu(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
 inline int prec_refactor(isph_ctx *ctx, isph_prec *M, const isph_mat *A) {
   if (prec_amg(M)) ISPH_CHECK(prec_refactor_amg(ctx, M, A));
   else if (M->type == PREC_CHEBYSHEV) ISPH_CHECK(prec_refactor_chebyshev(ctx, M, A));
+  else if (M->type == PREC_GMRES_POLY) ISPH_CHECK(prec_refactor_gmres_poly(ctx, M, A));
   else if (prec_ilu(M)) ISPH_CHECK(prec_refactor_ilu(ctx, M, A));
   else {
     static const char *const names[PREC_KINDS] = {"none", "jacobi", "bjacobi-ilu<k>", "sa-amg", "ilu<k> / additive Schwarz",
-                                                  "overlap ILU(k)", "chebyshev<d>"};
+                                                  "overlap ILU(k)", "chebyshev<d>", "gmres-poly<d>"};
     char msg[200];
-    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to \"bjacobi-ilu<k>\", \"sa-amg\" and \"chebyshev<d>\", not to a "
+    snprintf(msg, sizeof(msg), "isph_prec_refactor applies to \"bjacobi-ilu<k>\", \"sa-amg\", \"chebyshev<d>\" and \"gmres-poly<d>\", not to a "
                                "preconditioner of type \"%s\": rebuild it", M->type >= 0 && M->type < PREC_KINDS ? names[M->type] : "?");
     return fail(msg, __FILE__, __LINE__);
   }

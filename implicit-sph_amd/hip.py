@@ -32,6 +32,7 @@ EXPORTS = [
     "isph_smooth_field", "isph_ek_params_default", "isph_electrostatic_force", "isph_random_stress_tensor", "isph_random_stress_force",
     "isph_force_from_random_stress", "isph_cheb_params_default", "isph_prec_create_chebyshev", "isph_prec_value_bits", "isph_prec_cycle_bits",
     "isph_prec_eig_estimate",
+    "isph_poly_params_default", "isph_prec_create_gmres_poly", "isph_prec_poly_info", "isph_prec_type_kind",
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
     "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
@@ -249,6 +250,12 @@ def lib():
         L.isph_prec_create_chebyshev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.isph_prec_value_bits.argtypes = [C.c_void_p]
         L.isph_prec_eig_estimate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_poly_params_default.argtypes = [C.c_void_p]
+        L.isph_poly_params_default.restype = None
+        L.isph_prec_create_gmres_poly.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_prec_poly_info.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.isph_prec_type_kind.argtypes = [C.c_char_p]
+        L.isph_prec_type_kind.restype = C.c_int
         L.isph_ilu_params_default.argtypes = [C.c_void_p]
         L.isph_ilu_params_default.restype = None
         L.isph_prec_create_ilu.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -787,7 +794,7 @@ class Precond:
         the library's row numbering)"""
         self.ctx, self.n = ctx, A.info()["nrow"]
         self.h = C.c_void_p()
-        self.A = A if kind.startswith("chebyshev") else None   # the polynomial applies the matrix: keep it alive
+        self.A = A if kind.startswith(("chebyshev", "gmres-poly")) else None   # a polynomial applies the matrix: keep it alive
         if block_ptr is not None:
             f32 = kind.endswith("-f32")   # "bjacobi-ilu<k>-f32": the table form with value_bits = 32
             fill = kind[11:-4] if f32 else kind[11:]
@@ -885,6 +892,24 @@ class Precond:
         a = (C.c_double * 3)()
         _check(lib().isph_prec_eig_estimate(self.ctx.h, self.h, int(level), a))
         return dict(lambda_used=float(a[0]), rho=float(a[1]), steps=int(a[2]))
+
+    def _poly_info(self):
+        roots = np.zeros(2 * POLY_MAX_DEGREE)
+        hess = np.zeros((POLY_MAX_DEGREE + 1) * POLY_MAX_DEGREE)
+        deg = C.c_int()
+        _check(lib().isph_prec_poly_info(self.h, _ptr(roots), _ptr(hess), C.byref(deg)))
+        return roots, hess, deg.value
+
+    def roots(self):
+        """isph_prec_poly_info: the roots of a GMRES polynomial ("gmres-poly<d>", PrecondGmresPoly) in application order, a
+        complex array of the degree reached; any other kind fails by name"""
+        roots, _, d = self._poly_info()
+        return roots[0:2 * d:2] + 1j * roots[1:2 * d:2]
+
+    def hessenberg(self):
+        """isph_prec_poly_info: the Arnoldi matrix H, (degree + 1) x degree, of a GMRES polynomial"""
+        _, hess, d = self._poly_info()
+        return hess.reshape(POLY_MAX_DEGREE, POLY_MAX_DEGREE + 1).T[:d + 1, :d].copy()
 
     def info(self):
         a = (C.c_longlong * 4)()
@@ -1019,6 +1044,41 @@ class PrecondChebyshev(Precond):
         prm = ChebParams(degree=int(degree), ratio=float(ratio), lambda_max=float(lambda_max), lambda_min=float(lambda_min),
                          value_bits=int(value_bits), eig_type=int(eig_type), eig_iters=int(eig_iters))
         _check(lib().isph_prec_create_chebyshev(ctx.h, A.h, C.byref(prm), C.byref(self.h)))
+
+
+POLY_MAX_DEGREE = 25
+
+
+class PolyParams(C.Structure):
+    """Mirror of isph_poly_params: degree 1..25 of the GMRES polynomial (default 4)."""
+    _fields_ = [("degree", C.c_int)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().isph_poly_params_default(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+def prec_type_kind(kind):
+    """isph_prec_type_kind: the kind a type string of Precond names (7 = "gmres-poly<d>"), -1 for one it refuses; no
+    context and no device needed"""
+    return int(lib().isph_prec_type_kind(str(kind).encode()))
+
+
+class PrecondGmresPoly(Precond):
+    """isph_prec_create_gmres_poly: Belos' GMRES polynomial of `degree` roots in D^-1 A as a fixed linear preconditioner.
+    nullvec (host array or device tensor, the caller's row numbering): the null vector of a singular system; the set-up is
+    projected with it.  The matrix is applied, not copied: it is kept alive here.  Precond(ctx, A, "gmres-poly<d>") is the
+    same without a null vector."""
+
+    def __init__(self, ctx, A, degree=4, nullvec=None):
+        self.ctx, self.h, self.n, self.A = ctx, C.c_void_p(), A.info()["nrow"], A
+        prm = PolyParams(degree=int(degree))
+        nv = None if nullvec is None else _f64(nullvec)
+        _need(nv, self.n, "nullvec [n]")
+        _check(lib().isph_prec_create_gmres_poly(ctx.h, A.h, C.byref(prm), _ptr(nv), int(nv is not None and _is_torch(nv)),
+                                                 C.byref(self.h)))
 
 
 def solve_block(ctx, blocks, b, x, prec=None, params=None, lda=None):

@@ -31,6 +31,9 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       // device-side extension (not a reference key), "Precond Type" = "ILU" only: "isph: ilu value bits" = 32 makes the
       // triangular solves of the block stream read the strict-L / strict-U values rounded to float
       // (isph_ilu_params::value_bits).  Not set here: absent means 64.
+      // device-side extension (not a reference type): "Precond Type" = "GMRES Polynomial" is Belos' GMRES polynomial in
+      // D^-1 A as a fixed preconditioner (isph_prec_create_gmres_poly) with "isph: polynomial degree" roots (1..25,
+      // absent means 4); the null vector of a singular system is passed on (setNullVector).
     } else if (_param.get() != param) {
       _param = Teuchos::rcp(param, false);
     }
@@ -54,6 +57,11 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
   // particles, whatever the atom order (on the 100^3 TGV system in create_atoms order 71 iterations instead of 164).
   // INTEGRATION.md shows the call.  NULL pointers clear them.
   void setCoordinates(const int dim, double *x, double *y, double *z) { storeCoordinates(dim, x, y, z); }
+
+  // "Precond Type" = "GMRES Polynomial" projects its set-up with the null vector of a singular system (borrowed until
+  // the solve, as PrecondWrapper_ML borrows it); the other types have no use for it
+  virtual void setNullVector(double *n) { _null = n; }
+  virtual bool usesNullVector() const { return _param.get() != NULL && _param->get("Precond Type", "ILU") == "GMRES Polynomial"; }
 
  protected:
   // the throughput path (block-Jacobi ILU(0), overlap 0 inside the rank) can be built during the matrix ingress
@@ -166,8 +174,24 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       _refreshable = rc == ISPH_SUCCESS;
       return rc;
     }
+    if (type == "GMRES Polynomial") {
+      // Belos' GMRES polynomial in D^-1 A: no subdomains, no overlap, no interval
+      isph_poly_params pp;
+      isph_poly_params_default(&pp);
+      pp.degree = _param->get("isph: polynomial degree", pp.degree);
+      if (_comm.MyPID() == 0 && !_warned) {
+        std::printf(">> PrecondWrapper_Ifpack(HIP): GMRES polynomial of degree %d in D^-1 A%s; \"Overlap Level\" and \"isph: block "
+                    "rows\" mean nothing for this type and are ignored\n", pp.degree, _null != nullptr ? " with the null vector" : "");
+        _warned = true;
+      }
+      // (a kept polynomial is not refreshed: its null vector is borrowed per solve -- the set-up runs again)
+      destroyDevice();
+      _kept_sig = deviceSignature();
+      return isph_prec_create_gmres_poly(ctx, A, &pp, _null, /*on_device=*/0, &_M);
+    }
     if (type != "ILU") {
-      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): Precond Type '%s' is not available; available: \"ILU\", \"Chebyshev\"\n",
+      std::fprintf(stderr, ">> PrecondWrapper_Ifpack(HIP): Precond Type '%s' is not available; available: \"ILU\", \"Chebyshev\", "
+                           "\"GMRES Polynomial\"\n",
                    type.c_str());
       return ISPH_FAILURE;
     }
@@ -294,8 +318,13 @@ class PrecondWrapper_Ifpack : public PrecondWrapper {
       sig += cb;
       sig += _param->get("isph: chebyshev eigen-analysis", "Anorm");
     }
+    if (sig.compare(0, 16, "GMRES Polynomial") == 0) {
+      std::snprintf(buf, sizeof(buf), "|%d|%d|", _param->get("isph: polynomial degree", 4), _null != nullptr ? 1 : 0);
+      sig += buf;
+    }
     return sig;
   }
+  double *_null = nullptr;  // setNullVector
   bool _warned = false, _warned_table = false;
   std::vector<int> _bptr;  // setSubdomains
 };

@@ -237,6 +237,8 @@ int isph_spmv_time(isph_ctx *ctx, const isph_mat *A, const double *x_dev, double
  *   "chebyshev<d>"  d = 1..16: Chebyshev polynomial of degree d in D^-1 A, Ifpack's "Precond Type" = "Chebyshev"
  *                   (isph_prec_create_chebyshev takes the ratio and the eigenvalues)
  *   "chebyshev<d>-f32"  the same with value_bits = 32: the polynomial of A rounded to single precision
+ *   "gmres-poly<d>" d = 1..25: Belos' GMRES polynomial of degree d in D^-1 A as a fixed preconditioner, without a null
+ *                   vector (isph_prec_create_gmres_poly takes one; there is no "-f32" form)
  * Rebuilt every solve in the reference (solver_lin_belos.h:153,190). */
 /* block_size 0 ("bjacobi-ilu<k>" only): the matrix' own subdomains, i.e. the bricks the assembly sorted the particles
  * into (isph_ctx_set_ordering); fails for a matrix in the caller's numbering. */
@@ -306,6 +308,11 @@ int isph_prec_create_ilu(isph_ctx *ctx, const isph_mat *A, const isph_ilu_params
  * is bit for bit that of a fresh create on A.  M applies A from then on (the caller keeps it alive).  REFUSED: another row
  * count; a polynomial created with the mode off (as before this type could be refactored: the mode is the caller's
  * statement that its preconditioners are meant to follow the matrix), M then untouched and usable.
+ *
+ * "gmres-poly<d>" (isph_prec_create_gmres_poly or isph_prec_create) CREATED WHILE isph_ctx_hold_pattern WAS ON: the same rule.
+ * The diagonal, the Arnoldi steps, the roots and the steps of the application are made again with the degree and the
+ * (normalised) null vector of the create call: bit for bit a fresh create on A.  REFUSED: another row count, a polynomial
+ * created with the mode off, a null vector kept in another row numbering than A's; M then untouched and usable.
  *
  * "sa-amg" (isph_prec_create_amg or isph_prec_create; every smoother, cheb_value_bits, cycle_bits, eig_type, threshold,
  * with or without a null vector), on one rank, for a hierarchy CREATED WHILE isph_ctx_hold_pattern WAS ON -- ML's
@@ -447,6 +454,47 @@ int isph_prec_cycle_bits(const isph_prec *M);
  * {rho, rho, 0}.  Collective for a hierarchy across ranks.  Any other preconditioner, or a level out of range, is an
  * error. */
 int isph_prec_eig_estimate(isph_ctx *ctx, const isph_prec *M, int level, double out[3]);
+
+/* Belos' GMRES polynomial (GmresPolySolMgr's polynomial, restated from the algorithm and unpinned against Belos,
+ * DESIGN.md 10) in D^-1 A as a fixed linear preconditioner: z = p(B) D^-1 r, B = D^-1 A, p the degree - 1 polynomial with
+ * 1 - B p(B) = prod_k (1 - B / theta_k) whose roots theta_1 .. theta_degree are the harmonic Ritz values of `degree`
+ * Arnoldi steps from v_0 = u / |u|.  No interval and no ratio, and a complex spectrum is handled.
+ *   u: the deterministic start vector of the eigenvalue estimate (isph_cheb_params above: Philox, keyed by the global row
+ *      in the caller's numbering), so the polynomial depends neither on the library's row numbering nor on the rank count
+ *      up to summation rounding.  nullvec != NULL (a singular system; any length, normalised inside): u and every set-up
+ *      product w are projected, w <- w - (w.n) n.
+ *   Arnoldi: classical Gram-Schmidt twice per step with the solvers' deterministic multi-dot, H of size (degree + 1) x
+ *      degree; H^ = H_d + h_{d+1,d}^2 f e_d^T with H_d^T f = e_d; the roots are the eigenvalues of H^ (host, the complex
+ *      Hessenberg-QR the Recycling GMRES uses).  A breakdown h_{j+1,j} <= 1e-14 |h_00| at step j < degree gives degree j.
+ *   Order: modified Leja -- the root of largest modulus first, then always the one farthest (by the product of distances)
+ *      from those chosen, a conjugate directly behind its partner.  |Im theta| <= 1e-8 |theta| counts as a real root.
+ *   Application, product form: r <- D^-1 r, z = 0; a real root: z += r / theta, r <- r - (B r) / theta; a pair a +- ib:
+ *      t = 2a r - B r, z += t / (a^2 + b^2), r <- r - (B t) / (a^2 + b^2); the product behind the last root is not made:
+ *      degree - 1 sweeps of the matrix, each one kernel with the update in its epilogue (ISPH_POLY_UNFUSED=1 at create
+ *      time: a product and a vector kernel instead, same bits; the cross-check).  No projection in the application:
+ *      B 1 = 0 keeps a null component bounded and the solver removes it.
+ * degree: 1..25 (Belos' maximum); anything else is refused.  A root with |theta| <= 1e-10 max |theta| fails the create
+ * call with "near-zero root: a singular matrix needs the null vector", a zero diagonal entry fails it too.  A fixed linear
+ * operator: every solver type may use it.  Collective on several ranks.  A must outlive the preconditioner: it is applied,
+ * not copied.  Several vectors (isph_prec_apply_multi, isph_solve with nvec > 1) are applied one after the other.
+ * isph_prec_refactor takes a polynomial created under isph_ctx_hold_pattern: the whole set-up again with the null vector
+ * of the create call, bit for bit a fresh create.  isph_prec_create(type = "gmres-poly<d>") is degree d without a null
+ * vector.  Measured at 100^3: DESIGN.md 9.4.
+ * Call isph_poly_params_default FIRST and then change fields: the struct grows at its tail. */
+typedef struct {
+  int degree; /* 1..25, default 4 */
+} isph_poly_params;
+void isph_poly_params_default(isph_poly_params *p);
+int isph_prec_create_gmres_poly(isph_ctx *ctx, const isph_mat *A, const isph_poly_params *prm,
+                                const double *nullvec /*[nrow] caller's numbering, h|d, or NULL*/, int on_device, isph_prec **M);
+/* The polynomial of M: roots_re_im[2 k], roots_re_im[2 k + 1] = the real and the imaginary part of root k in application
+ * order (room for 2 x 25), hess = H column-major with leading dimension 26 (room for 26 x 25; rows 0 .. degree of columns
+ * 0 .. degree - 1 are set, the rest is 0), *degree = the degree reached.  Any argument but M may be NULL.  Another kind of
+ * preconditioner is an error. */
+int isph_prec_poly_info(const isph_prec *M, double *roots_re_im, double *hess, int *degree);
+/* The kind a type string of isph_prec_create names (0 "none", 1 "jacobi", 2 "bjacobi-ilu<k>", 3 "sa-amg", 4 "ilu<k>",
+ * 6 "chebyshev<d>", 7 "gmres-poly<d>"), or -1 for a string it refuses.  Host only: no context, no device. */
+int isph_prec_type_kind(const char *type);
 
 /* z = M^-1 r (Belos::EpetraPrecOp::Apply -> Ifpack ApplyInverse). */
 int isph_prec_apply(isph_ctx *ctx, const isph_prec *M, const double *r /*[h|d]*/,
