@@ -2160,6 +2160,11 @@ int isph_shift_particles(isph_ctx *ctx, const isph_particles *P, int antisym, co
 // ghost atoms and the full neighbour list of one rank (isph_nlist_build, isph_nlist_info, isph_nlist_get, isph_nlist_destroy)
 #include "neighbours.hpp"
 
+// migration, off-rank ghosts, list, column map and halo plan on a brick of ranks, forward comm through that plan
+// (isph_migrate, isph_migrated_*, isph_nlist_build_dist, isph_nlist_dist_info, isph_nlist_dist_get, isph_nlist_forward,
+// isph_nlist_forward_int)
+#include "nlist_dist.hpp"
+
 // ghost rows, zero-mean pressure and the observables of a time step (isph_ghost_fill, isph_zero_mean_pressure, isph_status,
 // isph_tgv_error)
 #include "step_ops.hpp"

@@ -23,6 +23,7 @@
 //     out coalesced; longer rows (a dense clump) are written unsorted and sorted in place by their wave with a bitonic
 //     network in global memory.  Candidates always come from global memory (L2): no staging that a dense cell could
 //     overflow.
+// Stages 3 - 5 are nl_list_rows, which the multi-rank build (nlist_dist.hpp) runs over its own owned + ghost particles.
 #pragma once
 #include <rocprim/rocprim.hpp>
 
@@ -40,7 +41,14 @@ struct isph_nlist {
   isph::DevBuf<long long> ptr64;   // [nlocal + 1]
   isph::DevBuf<int> ptr32;         // [nlocal + 1] when fits32
   isph::DevBuf<int> idx;           // [nnz]
-  void release() { x.release(); owner.release(); ptr64.release(); ptr32.release(); idx.release(); }
+  // a list built across ranks (nlist_dist.hpp): owner rank and matrix column of every particle, the halo plan
+  int dist = 0, ncol = 0, noffrank = 0;
+  isph::DevBuf<int> orank, colmap;  // [nall]
+  isph_halo halo;                   // peers, send / receive ranges, send_idx: the plan of isph_nlist_forward
+  void release() {
+    x.release(); owner.release(); ptr64.release(); ptr32.release(); idx.release();
+    orank.release(); colmap.release(); halo.send_idx.release();
+  }
 };
 
 namespace isph {
@@ -319,55 +327,10 @@ inline int nl_check_box(int dim, int nlocal, const double lo[3], const double hi
   return ISPH_SUCCESS;
 }
 
-inline int nlist_build(isph_ctx *ctx, int dim, int nlocal, const double *x, const double lo[3], const double hi[3],
-                       const int periodic[3], double cut, int wrap, int on_device, isph_nlist &L) {
+// Stages 3 - 5: the rows of the n owned particles over the nall particles of L.x (owned first), into L.ptr64 / ptr32 / idx.
+inline int nl_list_rows(isph_ctx *ctx, int dim, int n, int nall, double cut, isph_nlist &L) {
   hipStream_t st = ctx->stream;
-  NlBox b;
-  memset(&b, 0, sizeof(b));
-  b.dim = dim; b.wrap = wrap != 0; b.cut = cut;
-  for (int a = 0; a < 3; ++a) {
-    b.lo[a] = lo[a]; b.hi[a] = hi[a]; b.period[a] = hi[a] - lo[a];
-    b.periodic[a] = a < dim && periodic[a] != 0;
-  }
-  const int n = nlocal;
-  L.dim = dim; L.nlocal = n;
-  ISPH_CHECK(L.ptr64.reserve((size_t)n + 1));
-  if (n == 0) {
-    ISPH_CHECK_HIP(hipMemsetAsync(L.ptr64.p, 0, sizeof(long long), st));
-    ISPH_CHECK(L.ptr32.reserve(1));
-    ISPH_CHECK_HIP(hipMemsetAsync(L.ptr32.p, 0, sizeof(int), st));
-    ISPH_CHECK_HIP(hipStreamSynchronize(st));
-    L.fits32 = 1;
-    return ISPH_SUCCESS;
-  }
-  const dim3 blk(kBlock), grid_n((n + kBlock - 1) / kBlock);
-  // 1. wrap, images per owner, their offsets
-  DevTmp<double> xin, xw;
-  const double *dx = x;
-  if (!on_device) {
-    ISPH_REQUIRE(!is_device_pointer(x), "on_device = 0 but x is device memory");
-    ISPH_CHECK(xin.reserve((size_t)n * 3));
-    ISPH_CHECK_HIP(hipMemcpyAsync(xin.p, x, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
-    dx = xin.p;
-  }
-  DevTmp<int> gcnt, goff;
-  ISPH_CHECK(xw.reserve((size_t)n * 3));
-  ISPH_CHECK(gcnt.reserve((size_t)n + 1));
-  ISPH_CHECK(goff.reserve((size_t)n + 1));
-  ISPH_CHECK_HIP(hipMemsetAsync(gcnt.p + n, 0, sizeof(int), st));
-  hipLaunchKernelGGL(k_nl_wrap_count, grid_n, blk, 0, st, n, b, dx, xw.p, gcnt.p);
-  ISPH_CHECK(nl_exclusive_scan<int>(st, gcnt.p, goff.p, (size_t)n + 1));
-  int nghost = 0;
-  ISPH_CHECK_HIP(hipMemcpyAsync(&nghost, goff.p + n, sizeof(int), hipMemcpyDeviceToHost, st));
-  ISPH_CHECK_HIP(hipStreamSynchronize(st));
-  ISPH_REQUIRE(nghost >= 0 && (long long)n + nghost < INT_MAX, "too many particles");
-  const int nall = n + nghost;
-  L.nghost = nghost;
-  // 2. owned + images
-  ISPH_CHECK(L.x.reserve((size_t)nall * 3));
-  ISPH_CHECK(L.owner.reserve((size_t)nall));
-  hipLaunchKernelGGL(k_nl_images, grid_n, blk, 0, st, n, b, (const double *)xw.p, (const int *)goff.p, L.x.p, L.owner.p);
-  xin.release(); xw.release(); gcnt.release(); goff.release();
+  const dim3 blk(kBlock);
   // 3. the cell grid, on the device
   const dim3 grid_all((nall + kBlock - 1) / kBlock);
   const int gb = std::min(256, (nall + kBlock - 1) / kBlock);
@@ -434,6 +397,58 @@ inline int nlist_build(isph_ctx *ctx, int dim, int nlocal, const double *x, cons
   ISPH_CHECK_HIP(hipStreamSynchronize(st));
   ISPH_CHECK_HIP(hipGetLastError());
   return ISPH_SUCCESS;
+}
+
+inline int nlist_build(isph_ctx *ctx, int dim, int nlocal, const double *x, const double lo[3], const double hi[3],
+                       const int periodic[3], double cut, int wrap, int on_device, isph_nlist &L) {
+  hipStream_t st = ctx->stream;
+  NlBox b;
+  memset(&b, 0, sizeof(b));
+  b.dim = dim; b.wrap = wrap != 0; b.cut = cut;
+  for (int a = 0; a < 3; ++a) {
+    b.lo[a] = lo[a]; b.hi[a] = hi[a]; b.period[a] = hi[a] - lo[a];
+    b.periodic[a] = a < dim && periodic[a] != 0;
+  }
+  const int n = nlocal;
+  L.dim = dim; L.nlocal = n;
+  ISPH_CHECK(L.ptr64.reserve((size_t)n + 1));
+  if (n == 0) {
+    ISPH_CHECK_HIP(hipMemsetAsync(L.ptr64.p, 0, sizeof(long long), st));
+    ISPH_CHECK(L.ptr32.reserve(1));
+    ISPH_CHECK_HIP(hipMemsetAsync(L.ptr32.p, 0, sizeof(int), st));
+    ISPH_CHECK_HIP(hipStreamSynchronize(st));
+    L.fits32 = 1;
+    return ISPH_SUCCESS;
+  }
+  const dim3 blk(kBlock), grid_n((n + kBlock - 1) / kBlock);
+  // 1. wrap, images per owner, their offsets
+  DevTmp<double> xin, xw;
+  const double *dx = x;
+  if (!on_device) {
+    ISPH_REQUIRE(!is_device_pointer(x), "on_device = 0 but x is device memory");
+    ISPH_CHECK(xin.reserve((size_t)n * 3));
+    ISPH_CHECK_HIP(hipMemcpyAsync(xin.p, x, sizeof(double) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+    dx = xin.p;
+  }
+  DevTmp<int> gcnt, goff;
+  ISPH_CHECK(xw.reserve((size_t)n * 3));
+  ISPH_CHECK(gcnt.reserve((size_t)n + 1));
+  ISPH_CHECK(goff.reserve((size_t)n + 1));
+  ISPH_CHECK_HIP(hipMemsetAsync(gcnt.p + n, 0, sizeof(int), st));
+  hipLaunchKernelGGL(k_nl_wrap_count, grid_n, blk, 0, st, n, b, dx, xw.p, gcnt.p);
+  ISPH_CHECK(nl_exclusive_scan<int>(st, gcnt.p, goff.p, (size_t)n + 1));
+  int nghost = 0;
+  ISPH_CHECK_HIP(hipMemcpyAsync(&nghost, goff.p + n, sizeof(int), hipMemcpyDeviceToHost, st));
+  ISPH_CHECK_HIP(hipStreamSynchronize(st));
+  ISPH_REQUIRE(nghost >= 0 && (long long)n + nghost < INT_MAX, "too many particles");
+  const int nall = n + nghost;
+  L.nghost = nghost;
+  // 2. owned + images
+  ISPH_CHECK(L.x.reserve((size_t)nall * 3));
+  ISPH_CHECK(L.owner.reserve((size_t)nall));
+  hipLaunchKernelGGL(k_nl_images, grid_n, blk, 0, st, n, b, (const double *)xw.p, (const int *)goff.p, L.x.p, L.owner.p);
+  xin.release(); xw.release(); gcnt.release(); goff.release();
+  return nl_list_rows(ctx, dim, n, nall, cut, L);
 }
 
 template <class T>

@@ -10,6 +10,9 @@ atoms (owner rank, owner local index) derive
 Index lists are exchanged once at plan time with torch.distributed object
 collectives (works on gloo and nccl); the per-SpMV exchange itself runs inside
 libisph_hip on RCCL (csrc/solver.hpp halo_exchange).
+
+hip.NeighbourListDist (isph_nlist_build_dist, csrc/nlist_dist.hpp) builds the ghosts, the list and the same HaloPlan
+(.plan()) on the device without an all-gather: the sender chose what it sent.
 """
 import sys
 from dataclasses import dataclass, field

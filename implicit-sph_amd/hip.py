@@ -35,6 +35,8 @@ EXPORTS = [
     "isph_poly_params_default", "isph_prec_create_gmres_poly", "isph_prec_poly_info", "isph_prec_type_kind",
     "isph_ilu_params_default", "isph_prec_create_ilu",
     "isph_nlist_build", "isph_nlist_info", "isph_nlist_get", "isph_nlist_destroy",
+    "isph_nlist_build_dist", "isph_nlist_dist_info", "isph_nlist_dist_get", "isph_nlist_forward", "isph_nlist_forward_int",
+    "isph_migrate", "isph_migrated_info", "isph_migrated_get", "isph_migrated_destroy",
     "isph_ctx_hold_pattern", "isph_mat_update_values", "isph_mat_pattern_info", "isph_prec_refactor",
     "isph_recycle_create", "isph_recycle_destroy", "isph_recycle_reset", "isph_recycle_info", "isph_recycle_export", "isph_recycle_import",
     "isph_solve_recycle", "isph_dense_tall_gemm", "isph_dense_block_gram",
@@ -317,6 +319,17 @@ def lib():
         L.isph_nlist_info.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_nlist_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_nlist_destroy.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_nlist_build_dist.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_int, C.c_int,
+                                            C.POINTER(C.c_void_p)]
+        L.isph_nlist_dist_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_nlist_dist_get.argtypes = [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6 + [C.c_int]
+        L.isph_nlist_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_nlist_forward_int.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_migrate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.POINTER(C.c_void_p)]
+        L.isph_migrated_info.argtypes = [C.c_void_p, C.c_void_p]
+        L.isph_migrated_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.isph_migrated_destroy.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_ctx_hold_pattern.argtypes = [C.c_void_p, C.c_int]
         L.isph_mat_update_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         L.isph_mat_pattern_info.argtypes = [C.c_void_p, C.c_void_p]
@@ -1953,6 +1966,175 @@ class NeighbourList:
             self.close()
         except Exception:
             pass
+
+
+class _CDecomp(C.Structure):
+    _fields_ = [("dim", C.c_int), ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("periodic", C.c_int * 3),
+                ("pgrid", C.c_int * 3), ("faces", C.c_void_p * 3)]
+
+
+class Decomp:
+    """isph_decomp: a brick of pgrid[0] x pgrid[1] x pgrid[2] ranks over the box lo .. hi (`dim` entries each, or three);
+    rank = cx + pgrid[0] * (cy + pgrid[1] * cz).  faces: None (uniform cuts) or per axis None / the pgrid[a] + 1 cut planes
+    from lo to hi.  Grid cell c owns x when faces[c] <= x < faces[c + 1]."""
+
+    def __init__(self, dim, lo, hi, periodic, pgrid, faces=None):
+        if dim not in (2, 3):
+            raise ValueError("dim must be 2 or 3")
+        self.dim = int(dim)
+        self.lo = [float(v) for v in (list(lo) + [0.0] * 3)[:3]]
+        self.hi = [float(v) for v in (list(hi) + [0.0] * 3)[:3]]
+        self.periodic = [int(bool(v)) for v in (list(periodic) + [0] * 3)[:3]]
+        self.pgrid = [int(v) for v in (list(pgrid) + [1] * 3)[:3]]
+        for a in range(self.dim, 3):
+            self.lo[a], self.hi[a], self.periodic[a], self.pgrid[a] = 0.0, 0.0, 0, 1
+        self.faces = [None, None, None]
+        for a in range(self.dim):
+            if faces is not None and faces[a] is not None:
+                f = np.ascontiguousarray(faces[a], dtype=np.float64)
+                if f.shape != (self.pgrid[a] + 1,):
+                    raise ValueError("faces[%d]: pgrid[%d] + 1 = %d planes needed" % (a, a, self.pgrid[a] + 1))
+                self.faces[a] = f
+
+    @property
+    def nranks(self):
+        return self.pgrid[0] * self.pgrid[1] * self.pgrid[2]
+
+    def c_struct(self):
+        """the isph_decomp; it points into self.faces: keep self alive for the duration of the call"""
+        d = _CDecomp()
+        d.dim = self.dim
+        for a in range(3):
+            d.lo[a], d.hi[a], d.periodic[a], d.pgrid[a] = self.lo[a], self.hi[a], self.periodic[a], self.pgrid[a]
+            d.faces[a] = None if self.faces[a] is None else self.faces[a].ctypes.data
+        return d
+
+
+class NeighbourListDist(NeighbourList):
+    """isph_nlist_build_dist: ghost atoms from the neighbouring ranks and from periodic images, the full list, the column
+    map and the halo plan of this rank's owned particles x [nlocal, 3] (numpy or torch device tensor; nlocal = 0 takes
+    part), built on the device.  COLLECTIVE: every rank of the context constructs one, with the same decomp, cut and prune.
+    get() adds owner_rank and colmap; plan() is the dist.HaloPlan Matrix.set_halo / HaloForward take; forward() is
+    forward_comm_pair of a per-atom array through that plan."""
+
+    def __init__(self, ctx, x, decomp, cut, prune=True):
+        self.h = C.c_void_p()
+        self.ctx, self.decomp = ctx, decomp
+        if len(x.shape) != 2 or int(x.shape[1]) != 3:
+            raise ValueError("x must be [nlocal, 3], got %s" % (tuple(x.shape),))
+        x = _f64(x)
+        if _is_torch(x) and not x.is_contiguous():
+            x = x.contiguous()
+        self.dev = _on_device(x)
+        self._like = x
+        self.dim, self.nlocal = decomp.dim, int(x.shape[0])
+        cd = decomp.c_struct()
+        _check(lib().isph_nlist_build_dist(ctx.h, C.byref(cd), self.nlocal, _ptr(x) if self.nlocal else None, float(cut),
+                                           int(bool(prune)), self.dev, C.byref(self.h)))
+
+    @property
+    def info(self):
+        """dict(nlocal, nghost, entries, fits32, ncol, npeers, nsend, noffrank)"""
+        a = (C.c_longlong * 8)()
+        _check(lib().isph_nlist_dist_info(self.h, a))
+        return dict(nlocal=int(a[0]), nghost=int(a[1]), entries=int(a[2]), fits32=int(a[3]), ncol=int(a[4]), npeers=int(a[5]),
+                    nsend=int(a[6]), noffrank=int(a[7]))
+
+    def get(self, ptr64=False):
+        """NeighbourList.get() + owner_rank [nall], colmap [nall] (on the side of x)"""
+        g = NeighbourList.get(self, ptr64)
+        i = self.info
+        nall = i["nlocal"] + i["nghost"]
+        orank, colmap = self._empty((nall,), "int32"), self._empty((nall,), "int32")
+        _check(lib().isph_nlist_dist_get(self.ctx.h, self.h, _ptr(orank), _ptr(colmap), None, None, None, None, self.dev))
+        g.update(owner_rank=orank, colmap=colmap)
+        return g
+
+    def plan(self):
+        """dist.HaloPlan of the list (numpy arrays on the host)"""
+        from . import dist
+        i = self.info
+        n, nall, npeers = i["nlocal"], i["nlocal"] + i["nghost"], i["npeers"]
+        orank, colmap, own = (np.zeros(nall, dtype=np.int32) for _ in range(3))
+        peers, sp, rp = np.zeros(npeers, dtype=np.int32), np.zeros(npeers + 1, dtype=np.int32), np.zeros(npeers + 1, dtype=np.int32)
+        sidx = np.zeros(i["nsend"], dtype=np.int32)
+        _check(lib().isph_nlist_dist_get(self.ctx.h, self.h, _ptr(orank), _ptr(colmap), _ptr(peers), _ptr(sp), _ptr(sidx), _ptr(rp), 0))
+        _check(lib().isph_nlist_get(self.ctx.h, self.h, None, _ptr(own), None, None, None, 0))
+        p = dist.HaloPlan(int(self.ctx.rank), int(self.ctx.nranks), n, i["ncol"], colmap, peers, sp, sidx, rp)
+        p.ghost_col_of = colmap[n:].copy()
+        ridx = np.zeros(i["ncol"] - n, dtype=np.int32)
+        off = colmap >= n
+        ridx[colmap[off] - n] = own[off]
+        p.recv_idx = ridx
+        return p
+
+    def forward(self, a, ncomp=None):
+        """isph_nlist_forward / _forward_int, in place: rows >= nlocal of a [nall] or [nall, ncomp] (float64 or int32, C
+        contiguous, numpy or device tensor) receive their owner's row.  Collective.  Returns a."""
+        i = self.info
+        nall = i["nlocal"] + i["nghost"]
+        if a.ndim not in (1, 2) or int(a.shape[0]) != nall:
+            raise OperandError("a: %s given, [nall = %d] or [nall][ncomp] needed" % (tuple(a.shape), nall))
+        nc = 1 if a.ndim == 1 else int(a.shape[1])
+        if ncomp is not None and int(ncomp) != nc:
+            raise OperandError("a has %d components, ncomp = %d" % (nc, int(ncomp)))
+        if nc < 1:
+            raise OperandError("a needs at least one component")
+        kind = str(a.dtype).replace("torch.", "")
+        if kind not in ("float64", "int32"):
+            raise ValueError("a: float64 or int32 needed, got %s" % a.dtype)
+        if (_is_torch(a) and not a.is_contiguous()) or (not _is_torch(a) and not a.flags.c_contiguous):
+            raise ValueError("a: a C-contiguous array is updated in place")
+        fn = lib().isph_nlist_forward if kind == "float64" else lib().isph_nlist_forward_int
+        _check(fn(self.ctx.h, self.h, nc, _ptr(a) if nall else None, _on_device(a)))
+        return a
+
+
+def migrate(ctx, decomp, x, fd=None, fi=None):
+    """isph_migrate (Comm::exchange): x [nlocal, 3] is wrapped and every particle goes to the rank whose sub-box holds it,
+    with its row of fd [nlocal, nd] (float64) and fi [nlocal, ni] (int32).  COLLECTIVE.  Returns (x, fd, fi, info) on the
+    side of x: the stayers in their old order, then the arrivals by (source rank, source index); info = dict(nlocal, sent,
+    received).  fd / fi None: returned as [nlocal', 0]."""
+    x = _f64(x)
+    n = int(x.shape[0])
+    if len(x.shape) != 2 or int(x.shape[1]) != 3:
+        raise ValueError("x must be [nlocal, 3], got %s" % (tuple(x.shape),))
+    dev = _on_device(x)
+    nd = 0 if fd is None else int(fd.shape[1])
+    ni = 0 if fi is None else int(fi.shape[1])
+    if fd is not None:
+        fd = _f64(fd)
+        if fd.ndim != 2 or int(fd.shape[0]) != n:
+            raise OperandError("fd: [nlocal = %d][nd] needed" % n)
+        _same_side(dev, fd)
+    if fi is not None:
+        fi = _i32(fi)
+        if fi.ndim != 2 or int(fi.shape[0]) != n:
+            raise OperandError("fi: [nlocal = %d][ni] needed" % n)
+        _same_side(dev, fi)
+    for a in (x, fd, fi):
+        if a is not None and _is_torch(a) and not a.is_contiguous():
+            raise ValueError("contiguous tensors needed")
+    h = C.c_void_p()
+    cd = decomp.c_struct()
+    _check(lib().isph_migrate(ctx.h, C.byref(cd), n, _ptr(x) if n else None, nd, _ptr(fd) if n and nd else None, ni,
+                              _ptr(fi) if n and ni else None, dev, C.byref(h)))
+    try:
+        a = (C.c_longlong * 3)()
+        _check(lib().isph_migrated_info(h, a))
+        m = int(a[0])
+
+        def empty(shape, kind):
+            if dev:
+                import torch
+                return torch.empty(shape, dtype=getattr(torch, kind), device=x.device)
+            return np.empty(shape, dtype=getattr(np, kind))
+        xo, fdo, fio = empty((m, 3), "float64"), empty((m, nd), "float64"), empty((m, ni), "int32")
+        _check(lib().isph_migrated_get(ctx.h, h, _ptr(xo) if m else None, _ptr(fdo) if m and nd else None,
+                                       _ptr(fio) if m and ni else None, dev))
+    finally:
+        lib().isph_migrated_destroy(ctx.h, h)
+    return xo, fdo, fio, dict(nlocal=m, sent=int(a[1]), received=int(a[2]))
 
 
 # ---- the glue of a time step: ghost rows, zero-mean pressure, observables -------------------------------------------

@@ -204,6 +204,49 @@ def make_cloud_device(ctx, x_owned, box, h, cut, dim=3, like=None):
     return out
 
 
+def make_cloud_dist_device(ctx, x_owned, decomp, h, cut, like=None, tags=None, prune=True):
+    """make_cloud_device on a brick of ranks (hip.NeighbourListDist / isph_nlist_build_dist): this rank's owned positions
+    x_owned [nlocal, 3] (torch device tensor; a numpy array is uploaded first; they must lie in the rank's sub-box of
+    `decomp`, a hip.Decomp -- hip.migrate puts them there) -> the dict of make_cloud_device with owner_rank filled in, the
+    ghosts being the particles of the neighbouring ranks and the periodic images within the cut, plus
+      colmap  [nall] matrix column of every particle (device),   plan  the dist.HaloPlan (host arrays),
+      nlist   the hip.NeighbourListDist itself: nlist.forward(a) is the forward comm of a per-atom array; close it when done.
+    COLLECTIVE: every rank of ctx calls it.  like: a dict with this rank's owned rho, nu, type (numpy or device; the first
+    nlocal rows count), forwarded to the ghosts; tags [nlocal] int32: global tags, forwarded too (default: 1 + the index
+    on the owner, which is not unique across ranks).  hip.assemble_poisson takes the dict with colmap and plan.ncol,
+    Matrix.set_halo and hip.HaloForward take the plan's lists."""
+    import torch
+    from . import hip
+    if not hip._is_torch(x_owned):
+        x_owned = torch.from_numpy(np.ascontiguousarray(x_owned, dtype=np.float64).reshape(-1, 3)).to(torch.device("cuda", 0))
+    nl = hip.NeighbourListDist(ctx, x_owned, decomp, cut, prune=prune)
+    g = nl.get()
+    info = nl.info
+    n, nall = info["nlocal"], info["nlocal"] + info["nghost"]
+    dev = x_owned.device
+    own = g["owner_index"]
+
+    def forwarded(src, dtype):
+        a = torch.zeros(nall, dtype=dtype, device=dev)
+        if not hip._is_torch(src):
+            src = torch.from_numpy(np.ascontiguousarray(src))
+        a[:n] = src[:n].to(device=dev, dtype=dtype)
+        return nl.forward(a)
+
+    spec = like["spec"] if like is not None and "spec" in like else None
+    out = dict(spec=spec, dim=decomp.dim, nlocal=n, nall=nall, x=g["x"], v=torch.zeros((nall, 3), dtype=torch.float64, device=dev),
+               tag=(own + 1) if tags is None else forwarded(tags, torch.int32),
+               type=torch.ones(nall, dtype=torch.int32, device=dev), owner_rank=g["owner_rank"], owner_index=own,
+               neigh_ptr=g["neigh_ptr"], neigh_idx=g["neigh_idx"], h=float(h), cut=float(cut), colmap=g["colmap"], plan=nl.plan(),
+               nlist=nl)
+    if like is not None:
+        for k in ("rho", "nu"):
+            out[k] = forwarded(like[k], torch.float64)
+        out["type"] = forwarded(like["type"], torch.int32)
+        out["dt"] = like.get("dt")
+    return out
+
+
 def single_rank_colmap(parts):
     """Matrix column of every particle on one rank: ghosts are periodic images,
     their column is the owner's local id (Epetra LID of the shared tag)."""

@@ -1234,7 +1234,7 @@ int isph_force_from_random_stress(isph_ctx *ctx, const isph_particles *P, const 
  *   list    j != i with ((d0 d0) + d1 d1) + d2 d2 < cut cut, every product and sum rounded (no fused multiply-add);
  *           every row in ascending particle index; offsets in the CSR form of isph_particles
  *
- * A non-periodic axis gets no wrap and no images.  Off-rank ghosts (LAMMPS' Comm) are the caller's.  Every device buffer
+ * A non-periodic axis gets no wrap and no images.  Off-rank ghosts (LAMMPS' Comm): isph_nlist_build_dist below.  Every device buffer
  * comes from the library's pool; only the two counts (ghosts, list entries) are read back during the build. */
 typedef struct isph_nlist isph_nlist;
 
@@ -1257,6 +1257,83 @@ int isph_nlist_get(isph_ctx *ctx, const isph_nlist *nl, double *x_all, int *owne
                    long long *neigh_ptr64, int *neigh_ptr, int *neigh_idx, int on_device);
 
 int isph_nlist_destroy(isph_ctx *ctx, isph_nlist *nl);
+
+/* ---- the same step on a brick of ranks: migration, off-rank ghosts, list, column map, halo plan --------------------- */
+
+/* What LAMMPS' Comm (exchange, borders, forward_comm) and Neighbor::build do between two compute() calls on several
+ * ranks, and what Epetra's FillComplete derives from the result (column map + Import), on the device.  Everything between
+ * ranks goes through the context's communicator (RCCL or the host-staged callbacks): point-to-point exchanges with the
+ * at most 26 grid neighbours and max all-reduces of a failure flag.  Integers travel as doubles.  Every call of this
+ * section is COLLECTIVE: every rank of the context makes it, with the same decomposition, cut and prune; a rank that
+ * fails a check of its own carries the failure to the next consensus, where all ranks fail together (the others with
+ * "... failed on another rank").  One rank without a communicator is allowed.
+ *
+ * The decomposition: a grid of pgrid[0] x pgrid[1] x pgrid[2] sub-boxes cut by planes; grid cell c of axis a owns x
+ * (after the wrap of isph_nlist_build on periodic axes) when faces[a][c] <= x < faces[a][c + 1] -- a particle on a face
+ * belongs to the upper cell.  Beyond a non-periodic outer face the outer cell owns. */
+typedef struct {
+  int dim;                 /* 2 | 3 */
+  double lo[3], hi[3];     /* the global box */
+  int periodic[3];
+  int pgrid[3];            /* ranks per axis; rank = cx + pgrid[0] * (cy + pgrid[1] * cz) */
+  const double *faces[3];  /* faces[a][0 .. pgrid[a]]: cut planes, faces[a][0] = lo, last = hi; NULL: uniform,
+                              lo + c * ((hi - lo) / pgrid[a]), the last one hi itself (host always) */
+} isph_decomp;
+
+/* Ghosts, list, column map and halo plan of this rank's nlocal owned particles x [nlocal][3] [h|d] (nlocal = 0 takes
+ * part).  Refused by name: pgrid[0] * pgrid[1] * pgrid[2] != the context's rank count; a sub-box narrower than cut on an
+ * axis with more than one rank; a periodic axis with one rank shorter than 2 cut; owned particles outside the rank's
+ * sub-box after the wrap (the message carries their number).
+ *
+ *   border  on axis a a particle is needed on the low side when x_a - flo_a < cut and on the high side when
+ *           x_a >= fhi_a - cut (flo / fhi: the owner's faces); every non-zero combination over the axes; nothing crosses a
+ *           non-periodic outer face; the receiver is the rank at that grid offset, wrapped on periodic axes; the image
+ *           shift s_a in {-1, 0, +1} is non-zero exactly when the offset crosses the periodic boundary (to the low side
+ *           from grid coordinate 0: +1); position x_a + s_a P_a, rounded once, z = 0 in 2-D.  An axis with one rank gives
+ *           the self-images of isph_nlist_build.
+ *   ghosts  follow the owned particles, sorted by owner rank, owner index, shift (sz outermost, sx innermost), ascending;
+ *           this rank's own images stand at its own rank's place.  With two ranks on a periodic axis a particle may arrive
+ *           twice with different shifts: two ghosts, one column.  On one rank everything equals isph_nlist_build bit for bit.
+ *   list    as isph_nlist_build, over owned + ghost particles.
+ *   prune   != 0: the ghosts no owned row lists are dropped (Epetra's column map holds inserted columns only), neigh_idx
+ *           is renumbered, and the senders learn which of their particles survived.
+ *   colmap  owned i -> i; a self-image -> its owner's index; an off-rank ghost -> nlocal + the rank of its (owner rank,
+ *           owner index) among the distinct such pairs, ascending.
+ *   plan    peers: the ascending ranks with traffic in either direction; send_idx per peer: the ascending distinct owned
+ *           indices that peer holds; recv_ptr: the ghost columns per peer (isph_mat_set_halo / isph_halo_create take them).
+ *
+ * Read back during a build: the record counts per neighbour rank (each way), the ghost, column and send counts per
+ * neighbour rank, the number of list entries, the consensus flags.  Device buffers come from the library's pool.
+ * isph_nlist_info / isph_nlist_get / isph_nlist_destroy work on the result; owner_index is the index on the owner's rank. */
+int isph_nlist_build_dist(isph_ctx *ctx, const isph_decomp *dc, int nlocal, const double *x, double cut, int prune,
+                          int on_device, isph_nlist **out);
+
+/* info: [0] nlocal  [1] nghost  [2] list entries  [3] fits32  [4] ncol (owned + ghost columns)  [5] npeers
+ *       [6] send entries  [7] off-rank ghosts */
+int isph_nlist_dist_info(const isph_nlist *nl, long long info[8]);
+
+/* copies out; any pointer may be NULL; [h|d] per on_device.  owner_rank / colmap [nall], peers [npeers],
+ * send_ptr / recv_ptr [npeers + 1], send_idx [send entries]. */
+int isph_nlist_dist_get(isph_ctx *ctx, const isph_nlist *nl, int *owner_rank, int *colmap, int *peers, int *send_ptr,
+                        int *send_idx, int *recv_ptr, int on_device);
+
+/* forward_comm_pair of a per-atom array a [nall][ncomp] [h|d], in place: rows >= nlocal receive their owner's row, from
+ * this rank (self-images) or through one exchange of the distinct ghost columns over the list's plan.  Collective. */
+int isph_nlist_forward(isph_ctx *ctx, const isph_nlist *nl, int ncomp, double *a, int on_device);
+int isph_nlist_forward_int(isph_ctx *ctx, const isph_nlist *nl, int ncomp, int *a, int on_device);
+
+/* Comm::exchange: the positions x [nlocal][3] are wrapped; a particle whose wrapped position lies in another sub-box goes
+ * to that rank with its nd doubles fd [nlocal][nd] and ni ints fi [nlocal][ni] (either may be 0 / NULL).  The target must
+ * be one of the 26 (8 in 2-D) grid neighbours, else ALL ranks fail with "moved farther than one sub-box".  New owned
+ * order: the stayers in their old order, then the arrivals sorted by (source rank, source index).  Collective. */
+typedef struct isph_migrated isph_migrated;
+int isph_migrate(isph_ctx *ctx, const isph_decomp *dc, int nlocal, const double *x, int nd, const double *fd, int ni,
+                 const int *fi, int on_device, isph_migrated **out);
+/* info: [0] the new nlocal  [1] particles sent  [2] particles received */
+int isph_migrated_info(const isph_migrated *mg, long long info[3]);
+/* x [nlocal'][3], fd [nlocal'][nd], fi [nlocal'][ni]; any pointer may be NULL; [h|d] per on_device */
+int isph_migrated_get(isph_ctx *ctx, const isph_migrated *mg, double *x, double *fd, int *fi, int on_device);
+int isph_migrated_destroy(isph_ctx *ctx, isph_migrated *mg);
 
 /* ---- the glue of a time step: ghost rows, zero-mean pressure, observables ----------------------------------------- */
 
