@@ -48,7 +48,17 @@ struct AsmTables {  // small per-type tables, device resident
   // 1: every row's neighbours are ordered by matrix column (k_neigh_sort), so the row kernels can emit column-sorted
   // rows directly (the diagonal takes its slot on the way) and the SELL row sort is skipped
   int sorted;
+  // non-NULL (sorted lists above the row threshold of the quadratic merge): the row kernels set *dup when a row receives a
+  // column twice -- two periodic images of one particle inside the cut, or the row particle's own image -- and the
+  // assembly then merges the adjacent duplicates (merge_adjacent_row); NULL: the assembly merges every row anyway
+  int *dup;
 };
+
+// sorted lists: a column that enters a row twice enters it twice in a row (or equals the row's own column)
+__device__ __forceinline__ void note_column(const AsmTables &T, int cj, int ci_own, int &prev) {
+  if (T.dup && (cj == prev || cj == ci_own)) *T.dup = 1;
+  prev = cj;
+}
 
 __device__ __forceinline__ int neigh_at(const AsmTables &T, int i, int k) {
   return T.nt[T.noff[i >> 6] + (long long)k * 64 + (i & 63)];
@@ -563,6 +573,7 @@ __global__ void k_asm_count(AsmTables T, int nlocal, const double *__restrict__ 
   const int i = xcd_block() * blockDim.x + threadIdx.x;
   if (i >= nlocal) return;
   const int it = type[i], nt1 = T.ntypes + 1;
+  if (T.dup && i == 0) *T.dup = 0;  // the flag of the row kernel that follows on the stream (sell_merge_prepare)
   int cnt = 1;
   for (int jj = 0, nn_i = T.nlen[i]; jj < nn_i; ++jj) {
     const int j = neigh_at(T, i, jj);
@@ -644,6 +655,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_poisson(AsmTables T, PoissonArgs
   const double mi = a.invrho[i];
   const int jb = 0, je = T.nlen[i];
   int cnt = 0, pdiag = -1;  // pdiag: slot of the diagonal (sorted lists: where the row's own column belongs)
+  int cprev = -1;
   const int ci_own = a.colmap[i];
   double diag_final;
   double bi = 0.0;
@@ -681,6 +693,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_poisson(AsmTables T, PoissonArgs
           }
         }
         const int cj = a.colmap[j];
+        note_column(T, cj, ci_own, cprev);
         if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
         const long long p = sell_pos(off, lane, cnt++);
         scol[p] = cj;
@@ -798,6 +811,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_poisson(AsmTables T, PoissonArgs
       v -= tmp;
       diag2 += tmp;
       const int cj = q3.y;
+      note_column(T, cj, ci_own, cprev);
       if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
       const long long p = sell_pos(off, lane, cnt++);
       scol[p] = cj;
@@ -921,7 +935,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
   const double mi = MODE ? a.r2[i].x : a.nu[i] * a.rho[i];
   const double vscale = MODE >= 2 ? 1.0 : -a.theta;                         // what multiplies the Laplacian in A
   const int jb = 0, je = T.nlen[i];
-  int cnt = 0, pdiag = -1;
+  int cnt = 0, pdiag = -1, cprev = -1;
   const int ci_own = a.colmap[i];
   double diag_final;
   double wv[3] = {0, 0, 0}, gp[3] = {0, 0, 0};
@@ -932,6 +946,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
       double rij[3];
       if (pair_rsq(dim, a.x, i, j, rij) < T.cutsq[it * nt1 + a.type[j]]) {
         const int cj = a.colmap[j];
+        note_column(T, cj, ci_own, cprev);
         if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
         const long long p = sell_pos(off, lane, cnt++);
         if (sval) { scol[p] = cj; sval[p] = 0.0; }
@@ -1054,6 +1069,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
         for (int k = 0; k < nf; ++k) wv[k] += aval * vj3[k];
       }
       const int cj = q3.y;
+      note_column(T, cj, ci_own, cprev);
       if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
       const long long p = sell_pos(off, lane, cnt++);
       if (sval) { scol[p] = cj; sval[p] = aval * vscale; }
@@ -1092,9 +1108,13 @@ __global__ __launch_bounds__(kBlock) void k_asm_helmholtz(AsmTables T, Helmholtz
 }
 
 // merge duplicate columns inside a row (periodic images sharing a tag in a
-// box narrower than 2*cut; what FillComplete + SumIntoGlobalValues do):
-// later duplicates are added into the first occurrence and turned into
-// explicit zeros on the row's own column.  Only run for small problems.
+// box with ONE periodic direction narrower than 2*cut; what FillComplete +
+// SumIntoGlobalValues do): later duplicates are added into the first
+// occurrence and turned into explicit zeros on the row's own column (`row`:
+// owned particles map to their own index in the caller's column map, and the
+// library's numbering keeps that, order.hpp k_perm_colmap).  Quadratic in the
+// row length and indifferent to the order of the row: run for small problems
+// and for rows that did not come out column-sorted.
 __global__ void k_sell_merge_duplicates(int nrow, const int *__restrict__ rowlen, const long long *__restrict__ slice_off,
                                         int *__restrict__ scol, double *__restrict__ sval, int *__restrict__ newlen) {
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1125,11 +1145,66 @@ __global__ void k_sell_merge_duplicates(int nrow, const int *__restrict__ rowlen
   newlen[row] = out;
 }
 
+// The same for rows in column order (lists ordered by k_neigh_sort, n above the row threshold of the quadratic merge): a
+// duplicate is an adjacent equal column, one pass over the row, values added in list order like above.  *flag == 0 -- no
+// row kernel saw a column twice, every box at least two cuts wide -- and each thread returns after one load: such an
+// assembly pays an empty launch.
+__device__ inline int merge_adjacent_row(int row, int *__restrict__ rowlen, const long long *__restrict__ slice_off,
+                                         const int *__restrict__ colmap, int *__restrict__ scol, double *__restrict__ sval) {
+  const long long off = slice_off[row >> 6];
+  const int lane = row & 63, len = rowlen[row];
+  int out = 0, last = -1;
+  double acc = 0.0;
+  for (int k = 0; k < len; ++k) {
+    const long long pk = sell_pos(off, lane, k);
+    const int c = scol[pk];
+    const double v = sval[pk];
+    if (out > 0 && c == last) {
+      acc += v;
+      sval[sell_pos(off, lane, out - 1)] = acc;
+    } else {
+      const long long po = sell_pos(off, lane, out++);
+      scol[po] = c;
+      sval[po] = v;
+      last = c;
+      acc = v;
+    }
+  }
+  const int own = colmap[row];
+  for (int k = out; k < len; ++k) {
+    const long long p = sell_pos(off, lane, k);
+    scol[p] = own;
+    sval[p] = 0.0;
+  }
+  rowlen[row] = out;
+  return out;
+}
+__global__ void k_sell_merge_adjacent(int nrow, const int *__restrict__ flag, int *__restrict__ rowlen,
+                                      const long long *__restrict__ slice_off, const int *__restrict__ colmap,
+                                      int *__restrict__ scol, double *__restrict__ sval) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= nrow || *flag == 0) return;
+  merge_adjacent_row(row, rowlen, slice_off, colmap, scol, sval);
+}
+
 // nnz = sum of the row lengths, reduced on the device (the 4 MB copy of a million row lengths and the host loop over
 // them cost 0.4 ms per assembly)
 __global__ __launch_bounds__(kBlock) void k_sum_rowlen(int n, const int *__restrict__ len, unsigned long long *__restrict__ out) {
   unsigned long long s = 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) s += (unsigned long long)len[i];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
+}
+// k_sum_rowlen with the one-pass merge in front of it: the Poisson assembly ends with the sum anyway, so a sorted assembly
+// without duplicate columns (*flag == 0) launches nothing for the merge
+__global__ __launch_bounds__(kBlock) void k_merge_adjacent_sum_rowlen(int n, const int *__restrict__ flag, int *__restrict__ len,
+                                                                      const long long *__restrict__ slice_off,
+                                                                      const int *__restrict__ colmap, int *__restrict__ scol,
+                                                                      double *__restrict__ sval, unsigned long long *__restrict__ out) {
+  const bool merge = *flag != 0;
+  unsigned long long s = 0;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    s += (unsigned long long)(merge ? merge_adjacent_row(i, len, slice_off, colmap, scol, sval) : len[i]);
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if ((threadIdx.x & 63) == 0 && s) atomicAdd(out, s);
 }
@@ -1171,6 +1246,32 @@ struct NeighPtr {
   const int *p32 = nullptr;
   const long long *p64 = nullptr;
 };
+
+// Duplicate columns of a row are merged for every n.  Before k_asm_count, which zeroes it, and the row kernel, which
+// raises it: the device flag of the sorted layout above the threshold (T.dup).  After them: the one-pass merge under that flag, or the quadratic merge of every row.  T.dup is
+// also what decides the row sort behind the merge: set, the rows stay in column order (sell_set_wmax); NULL, the
+// quadratic merge or an unsorted list left them in any order (sell_sort_rows).
+constexpr int kMergeAllRowsMax = 32768;
+inline int sell_merge_prepare(int n, AsmTables &T, DevTmp<int> &flag) {
+  T.dup = nullptr;
+  if (!(T.sorted && n > kMergeAllRowsMax)) return ISPH_SUCCESS;
+  ISPH_CHECK(flag.reserve(1));
+  T.dup = flag.p;
+  return ISPH_SUCCESS;
+}
+inline int sell_merge_rows(isph_ctx *ctx, const AsmTables &T, const int *colmap, Sell &M, DevTmp<int> &newlen) {
+  const int n = M.nrow, grid = (n + kBlock - 1) / kBlock;
+  if (T.dup) {
+    hipLaunchKernelGGL(k_sell_merge_adjacent, dim3(grid), dim3(kBlock), 0, ctx->stream, n, (const int *)T.dup, M.rowlen.p,
+                       (const long long *)M.slice_off.p, colmap, M.col.p, M.val.p);
+    return ISPH_SUCCESS;
+  }
+  ISPH_CHECK(newlen.reserve((size_t)n));
+  hipLaunchKernelGGL(k_sell_merge_duplicates, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p, M.col.p,
+                     M.val.p, newlen.p);
+  ISPH_CHECK_HIP(hipMemcpyAsync(M.rowlen.p, newlen.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
+  return ISPH_SUCCESS;
+}
 
 // builds the lane-interleaved neighbour list and hooks it into T
 template <class OFF>
@@ -1287,7 +1388,7 @@ inline int stage_tables(isph_ctx *ctx, const isph_particles *P, StagedParticles 
   const size_t nt1 = (size_t)P->ntypes + 1;
   ISPH_REQUIRE(P->kind && P->h && P->cutsq, "kind/h/cutsq tables are required (host pointers)");
   T.ntypes = P->ntypes; T.kernel = P->kernel; T.dim = P->dim;
-  T.noff = nullptr; T.nt = nullptr; T.sorted = 0;
+  T.noff = nullptr; T.nt = nullptr; T.sorted = 0; T.dup = nullptr;
   isph_table_cache &C = ctx->tables;
   const bool same = C.ntypes == P->ntypes && C.kernel == P->kernel && C.dim == P->dim && C.kind.size() == nt1 &&
                     memcmp(C.kind.data(), P->kind, sizeof(int) * nt1) == 0 &&
@@ -1374,7 +1475,7 @@ inline int assemble_poisson(isph_ctx *ctx, const isph_particles *P, int antisym,
   memset(&a, 0, sizeof(a));
   isph_mat *A = new isph_mat();
   DevTmp<double> bdev;
-  DevTmp<int> newlen;
+  DevTmp<int> newlen, dupflag;
   int rc = stage_tables(ctx, P, S, T);
   long long nnb = 0;
   if (rc == ISPH_SUCCESS) rc = stage(ctx, P->x, (size_t)P->nall * 3, on_device, S.x, &a.x);
@@ -1440,7 +1541,9 @@ inline int assemble_poisson(isph_ctx *ctx, const isph_particles *P, int antisym,
                          a.vfrac, a.invrho, a.vstar, a.type, a.colmap, pk1.p, pk2.p, pk3.p, (T.dim == 3 && a.antisym) ? 1 : 0);
       a.r1 = pk1.p; a.r2 = pk2.p; a.r3 = pk3.p;
       // (the count reads x and type directly: 24 + 4 bytes per neighbour; from the 32-byte records it ran 13 % slower)
-      hipLaunchKernelGGL(k_asm_count, dim3(xcd_grid(grid)), dim3(kBlock), 0, ctx->stream, T, n, a.x, a.type, a.nptr, a.nidx, M.rowlen.p);
+      rc = sell_merge_prepare(n, T, dupflag);
+      if (rc == ISPH_SUCCESS)
+        hipLaunchKernelGGL(k_asm_count, dim3(xcd_grid(grid)), dim3(kBlock), 0, ctx->stream, T, n, a.x, a.type, a.nptr, a.nidx, M.rowlen.p);
       hipLaunchKernelGGL(k_slicew_from_rowlen, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p);
       rc = sell_finalize_offsets(ctx, M);
     }
@@ -1468,18 +1571,12 @@ inline int assemble_poisson(isph_ctx *ctx, const isph_particles *P, int antisym,
         hipLaunchKernelGGL((k_asm_poisson<3, 0>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, M.col.p, M.val.p, db);
       else
         hipLaunchKernelGGL((k_asm_poisson<0, -1>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, M.col.p, M.val.p, db);
-      if (n <= 32768) {  // tiny boxes may see the same tag twice in a row
-        rc = newlen.reserve((size_t)n);
-        if (rc == ISPH_SUCCESS) {
-          hipLaunchKernelGGL(k_sell_merge_duplicates, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p,
-                             M.col.p, M.val.p, newlen.p);
-          if (hipMemcpyAsync(M.rowlen.p, newlen.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-            rc = fail("copy failed", __FILE__, __LINE__);
-        }
-      }
-      // rows come out column-sorted when the neighbour lists were ordered; merged duplicates break that order
-      // (sorted lists, no merge: the widest slice is known since sell_finalize_offsets)
-      if (rc == ISPH_SUCCESS && !(T.sorted && n > 32768)) rc = sell_sort_rows(ctx, M);  // columns ascending, like Epetra after FillComplete
+      // a box with one periodic direction shorter than two cuts shows a row the same tag twice: merged for every n (sorted
+      // lists above the threshold: under the row kernel's flag, inside the row-length sum below)
+      if (!T.dup) rc = sell_merge_rows(ctx, T, a.colmap, M, newlen);
+      // rows come out column-sorted when the neighbour lists were ordered (the one-pass merge keeps that order, the
+      // quadratic one of the small problems does not; the widest slice is known since sell_finalize_offsets)
+      if (rc == ISPH_SUCCESS && !T.dup) rc = sell_sort_rows(ctx, M);  // columns ascending, like Epetra after FillComplete
       if (rc == ISPH_SUCCESS && !on_device &&
           hipMemcpyAsync(b_out, db, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = fail("copy failed", __FILE__, __LINE__);
@@ -1489,8 +1586,12 @@ inline int assemble_poisson(isph_ctx *ctx, const isph_particles *P, int antisym,
       if (rc == ISPH_SUCCESS) rc = acc.reserve(1);
       if (rc == ISPH_SUCCESS) {
         if (hipMemsetAsync(acc.p, 0, sizeof(unsigned long long), ctx->stream) != hipSuccess) rc = fail("memset failed", __FILE__, __LINE__);
-        hipLaunchKernelGGL(k_sum_rowlen, dim3(std::min(256, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, n,
-                           (const int *)M.rowlen.p, acc.p);
+        if (T.dup)
+          hipLaunchKernelGGL(k_merge_adjacent_sum_rowlen, dim3(std::min(256, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                             n, (const int *)T.dup, M.rowlen.p, (const long long *)M.slice_off.p, a.colmap, M.col.p, M.val.p, acc.p);
+        else
+          hipLaunchKernelGGL(k_sum_rowlen, dim3(std::min(256, (n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, n,
+                             (const int *)M.rowlen.p, acc.p);
         if (hipMemcpyAsync(&hacc, acc.p, sizeof(hacc), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail("copy failed", __FILE__, __LINE__);
       }
       if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipGetLastError() != hipSuccess)
@@ -1529,7 +1630,7 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
   const bool rhs_only = A_out == nullptr;  // theta = 0 callers only need b (the reference then copies b into x)
   isph_mat *A = new isph_mat();
   DevTmp<double> bdev;
-  DevTmp<int> newlen;
+  DevTmp<int> newlen, dupflag;
   int rc = stage_tables(ctx, P, S, T);
   long long nnb = 0;
   if (rc == ISPH_SUCCESS) rc = stage(ctx, P->x, (size_t)P->nall * 3, on_device, S.x, &a.x);
@@ -1583,7 +1684,8 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
   if (rc == ISPH_SUCCESS && !on_device && !no_b) { rc = bdev.reserve((size_t)lda * nrhs); db = bdev.p; }
   if (rc == ISPH_SUCCESS && n > 0) {
     const int grid = (n + kBlock - 1) / kBlock;
-    if (!rhs_only) {
+    if (!rhs_only) rc = sell_merge_prepare(n, T, dupflag);
+    if (rc == ISPH_SUCCESS && !rhs_only) {
       hipLaunchKernelGGL(k_asm_count, dim3(xcd_grid(grid)), dim3(kBlock), 0, ctx->stream, T, n, a.x, a.type, a.nptr, a.nidx, M.rowlen.p);
       hipLaunchKernelGGL(k_slicew_from_rowlen, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p);
       rc = sell_finalize_offsets(ctx, M);
@@ -1624,17 +1726,10 @@ inline int assemble_helmholtz(isph_ctx *ctx, const isph_particles *P, int antisy
         else
           hipLaunchKernelGGL((k_asm_helmholtz<0, -1>), dim3(xcd_grid(gridp)), dim3(kBlock), 0, ctx->stream, T, a, M.slice_off.p, mcol, mval, db);
       }
-      if (!rhs_only && n <= 32768) {
-        rc = newlen.reserve((size_t)n);
-        if (rc == ISPH_SUCCESS) {
-          hipLaunchKernelGGL(k_sell_merge_duplicates, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p,
-                             M.col.p, M.val.p, newlen.p);
-          if (hipMemcpyAsync(M.rowlen.p, newlen.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-            rc = fail("copy failed", __FILE__, __LINE__);
-        }
-      }
-      // rows come out column-sorted when the neighbour lists were ordered; merged duplicates break that order
-      if (rc == ISPH_SUCCESS && !rhs_only) rc = (T.sorted && n > 32768) ? sell_set_wmax(ctx, M) : sell_sort_rows(ctx, M);
+      // a box with one periodic direction shorter than two cuts shows a row the same tag twice: merged for every n
+      if (rc == ISPH_SUCCESS && !rhs_only) rc = sell_merge_rows(ctx, T, a.colmap, M, newlen);
+      // rows come out column-sorted when the neighbour lists were ordered; the quadratic merge breaks that order
+      if (rc == ISPH_SUCCESS && !rhs_only) rc = T.dup ? sell_set_wmax(ctx, M) : sell_sort_rows(ctx, M);
       if (rc == ISPH_SUCCESS && !on_device && !no_b &&
           hipMemcpyAsync(b_out, db, sizeof(double) * (size_t)lda * nrhs, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
         rc = fail("copy failed", __FILE__, __LINE__);

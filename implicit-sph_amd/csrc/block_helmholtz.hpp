@@ -59,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_block_helmholtz(AsmTables T, Blo
   const double mi = a.nu[i];
   const int jb0 = 0, je = T.nlen[i];
   const int ci_own = a.colmap[i];
-  int cnt = 0, pdiag = -1;
+  int cnt = 0, pdiag = -1, cprev = -1;
 
   if (!(ikind & KIND_FLUID)) {  // solid row: zero row, unit diagonal in the diagonal blocks, b = v
     for (int jj = jb0; jj < je; ++jj) {
@@ -67,6 +67,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_block_helmholtz(AsmTables T, Blo
       double rij[3];
       if (pair_rsq(dim, a.x, i, j, rij) < T.cutsq[it * nt1 + a.type[j]]) {
         const int cj = a.colmap[j];
+        note_column(T, cj, ci_own, cprev);
         if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
         const long long p = sell_pos(off, lane, cnt++);
         for (int q = 0; q < d2; ++q)
@@ -224,6 +225,7 @@ __global__ __launch_bounds__(kBlock) void k_asm_block_helmholtz(AsmTables T, Blo
       val[s] = v * alpha;
     }
     const int cj = a.colmap[j];
+    note_column(T, cj, ci_own, cprev);
     if (T.sorted && pdiag < 0 && cj > ci_own) pdiag = cnt++;
     const long long p = sell_pos(off, lane, cnt++);
     for (int ib = 0; ib < dim; ++ib)
@@ -291,7 +293,7 @@ inline int assemble_block_helmholtz(isph_ctx *ctx, const isph_particles *P, int 
   HelmholtzArgs &a = A.h;
   isph_mat *blk[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   DevTmp<double> bdev;
-  DevTmp<int> newlen;
+  DevTmp<int> newlen, dupflag;
   int rc = stage_tables(ctx, P, S, T);
   long long nnb = 0;
   if (rc == ISPH_SUCCESS) rc = stage(ctx, P->x, (size_t)P->nall * 3, on_device, S.x, &a.x);
@@ -342,9 +344,12 @@ inline int assemble_block_helmholtz(isph_ctx *ctx, const isph_particles *P, int 
   if (rc == ISPH_SUCCESS && n > 0) {
     Sell &M = A0->S;
     const int grid = (n + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_asm_count, dim3(xcd_grid(grid)), dim3(kBlock), 0, ctx->stream, T, n, a.x, a.type, a.nptr, a.nidx, M.rowlen.p);
-    hipLaunchKernelGGL(k_slicew_from_rowlen, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p);
-    rc = sell_finalize_offsets(ctx, M);
+    rc = sell_merge_prepare(n, T, dupflag);
+    if (rc == ISPH_SUCCESS) {
+      hipLaunchKernelGGL(k_asm_count, dim3(xcd_grid(grid)), dim3(kBlock), 0, ctx->stream, T, n, a.x, a.type, a.nptr, a.nidx, M.rowlen.p);
+      hipLaunchKernelGGL(k_slicew_from_rowlen, dim3(grid), dim3(kBlock), 0, ctx->stream, n, M.rowlen.p, M.slice_off.p);
+      rc = sell_finalize_offsets(ctx, M);
+    }
     for (int q = 1; q < d2 && rc == ISPH_SUCCESS; ++q) {
       const bool diagblk = (q / dim) == (q % dim);
       if (!normal && !diagblk) continue;
@@ -373,21 +378,14 @@ inline int assemble_block_helmholtz(isph_ctx *ctx, const isph_particles *P, int 
       for (int q = 0; q < d2 && rc == ISPH_SUCCESS; ++q) {
         if (!blk[q]) continue;
         Sell &B = blk[q]->S;
-        if (n <= 32768) {
-          rc = newlen.reserve((size_t)n);
-          if (rc == ISPH_SUCCESS) {
-            hipLaunchKernelGGL(k_sell_merge_duplicates, dim3(grid), dim3(kBlock), 0, ctx->stream, n, B.rowlen.p, B.slice_off.p,
-                               B.col.p, B.val.p, newlen.p);
-            if (hipMemcpyAsync(B.rowlen.p, newlen.p, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-              rc = fail("copy failed", __FILE__, __LINE__);
-          }
-        }
-        if (rc == ISPH_SUCCESS) rc = (T.sorted && n > 32768) ? sell_set_wmax(ctx, B) : sell_sort_rows(ctx, B);
+        // a box with one periodic direction shorter than two cuts shows a row the same tag twice: merged for every n
+        rc = sell_merge_rows(ctx, T, a.colmap, B, newlen);
+        if (rc == ISPH_SUCCESS) rc = T.dup ? sell_set_wmax(ctx, B) : sell_sort_rows(ctx, B);
       }
-      // Above the merge threshold every block keeps the scalar pattern as the row kernel wrote it: the 16-bit window
+      // Above the row-sort threshold every block keeps the scalar pattern of the row kernel and the merge: the 16-bit window
       // columns of the SpMV are built once, for block (0,0), and copied (0.2 ms per block instead of a 1 ms rebuild on
       // each block's first SpMV; a 2 M-particle cavity step has nine of them)
-      if (rc == ISPH_SUCCESS && T.sorted && n > 32768 && sell_cols16(ctx, A0->S)) {
+      if (rc == ISPH_SUCCESS && T.dup && sell_cols16(ctx, A0->S)) {
         const Sell &S0 = A0->S;
         for (int q = 1; q < d2 && rc == ISPH_SUCCESS; ++q) {
           if (!blk[q]) continue;
