@@ -2,7 +2,7 @@
 // particles that left their sub-box (isph_migrate, LAMMPS' Comm::exchange), ghost atoms from the neighbouring ranks and
 // from periodic images, the full neighbour list, the column map and the halo plan (isph_nlist_build_dist, Comm::borders +
 // Neighbor::build + what Epetra's FillComplete derives), and the forward comm of per-atom arrays through that plan
-// (isph_nlist_forward, forward_comm_pair).
+// (isph_nlist_forward, forward_comm_pair; isph_nlist_forward_multi: several arrays in one exchange).
 //
 // Everything between ranks goes through comm.hpp: comm_exchange with a temporary isph_halo over the (at most 26) grid
 // neighbours, comm_consensus for the failure flags.  Integers travel as doubles (exact below 2^53).  No kernel waits on
@@ -693,6 +693,115 @@ inline int nlist_forward(isph_ctx *ctx, const isph_nlist *nl, int ncomp, T *a, i
   return ISPH_SUCCESS;
 }
 
+// several per-atom arrays in ONE exchange (PairISPH::pack_forward_comm sends several fields per message): a record of
+// width = sum of ncomp doubles per listed atom, the arrays' components one behind the other; ints travel as doubles
+constexpr int kFwdMaxArrays = 8;
+
+struct FwdMulti {   // passed to the kernels by value
+  int narr, width;
+  void *a[kFwdMaxArrays];
+  int ncomp[kFwdMaxArrays], is_int[kFwdMaxArrays];
+  int off[kFwdMaxArrays + 1];   // first component of array j in the record
+};
+
+__device__ __forceinline__ int fwd_array_of(const FwdMulti &F, int c) {
+  int j = 0;
+  while (j + 1 < F.narr && c >= F.off[j + 1]) ++j;
+  return j;
+}
+
+// one thread per double of the send buffer: consecutive lanes write consecutive doubles of a record
+__global__ __launch_bounds__(kBlock) void k_dd_fwd_pack_multi(long long nelem, FwdMulti F, const int *__restrict__ send_idx,
+                                                              double *__restrict__ sbuf) {
+  const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= nelem) return;
+  const long long k = e / F.width;
+  const int c = (int)(e - k * F.width), j = fwd_array_of(F, c);
+  const long long src = (long long)send_idx[k] * F.ncomp[j] + (c - F.off[j]);
+  sbuf[e] = F.is_int[j] ? (double)static_cast<const int *>(F.a[j])[src] : static_cast<const double *>(F.a[j])[src];
+}
+
+// one thread per double of a ghost's record: from the owner's row on this rank (a self-image) or from the receive buffer
+__global__ __launch_bounds__(kBlock) void k_dd_fwd_gather_multi(long long nelem, FwdMulti F, int n, int ncol,
+                                                                const int *__restrict__ colmap, const double *__restrict__ rbuf) {
+  const long long e = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= nelem) return;
+  const long long g = e / F.width;
+  const int c = (int)(e - g * F.width), j = fwd_array_of(F, c), nc = F.ncomp[j], cc = c - F.off[j];
+  const int col = colmap[n + g];
+  if (col < 0 || col >= ncol) return;   // never for a map this library made; keeps the reads in bounds
+  const long long dst = ((long long)n + g) * nc + cc;
+  if (F.is_int[j]) {
+    int *a = static_cast<int *>(F.a[j]);
+    a[dst] = col < n ? a[(long long)col * nc + cc] : (int)rbuf[(long long)(col - n) * F.width + c];
+  } else {
+    double *a = static_cast<double *>(F.a[j]);
+    a[dst] = col < n ? a[(long long)col * nc + cc] : rbuf[(long long)(col - n) * F.width + c];
+  }
+}
+
+// agree: the caller's arguments are checked and staged, then a consensus stands before the exchange, so a rank whose
+// arguments are refused fails its peers with it (the stand-alone entry point).  The driver passes its own arrays and has
+// its consensus behind it: no all-reduce of its own
+inline int nlist_forward_multi(isph_ctx *ctx, const isph_nlist *nl, int narrays, const isph_fwd_array *arr, int on_device,
+                               bool agree) {
+  hipStream_t st = ctx->stream;
+  const int n = nl->nlocal, ng = nl->nghost;
+  const size_t nall = (size_t)n + (size_t)ng;
+  const isph_halo &H = nl->halo;
+  FwdMulti F;
+  memset(&F, 0, sizeof(F));
+  DevTmp<double> td[kFwdMaxArrays], sbuf, rbuf;
+  DevTmp<int> ti[kFwdMaxArrays];
+  auto local = [&]() -> int {
+    ISPH_REQUIRE(nl->dist, "isph_nlist_forward_multi: the list was not built by isph_nlist_build_dist");
+    ISPH_REQUIRE(narrays >= 1 && narrays <= kFwdMaxArrays && arr, "isph_nlist_forward_multi: 1 to 8 arrays are taken");
+    F.narr = narrays;
+    for (int j = 0; j < narrays; ++j) {
+      ISPH_REQUIRE(arr[j].ncomp >= 1 && arr[j].ncomp <= 64, "isph_nlist_forward_multi: ncomp must be 1 .. 64");
+      ISPH_REQUIRE(arr[j].a || nall == 0, "NULL argument");
+      F.ncomp[j] = arr[j].ncomp; F.is_int[j] = arr[j].is_int != 0; F.off[j + 1] = F.off[j] + arr[j].ncomp;
+      F.a[j] = arr[j].a;
+      if (!on_device && nall > 0) {
+        ISPH_REQUIRE(!is_device_pointer(arr[j].a), "on_device = 0 but an array is device memory");
+        const size_t own = (size_t)n * (size_t)arr[j].ncomp, all = nall * (size_t)arr[j].ncomp;
+        if (F.is_int[j]) {
+          ISPH_CHECK(ti[j].reserve(all));
+          ISPH_CHECK_HIP(hipMemcpyAsync(ti[j].p, arr[j].a, sizeof(int) * own, hipMemcpyHostToDevice, st));
+          F.a[j] = ti[j].p;
+        } else {
+          ISPH_CHECK(td[j].reserve(all));
+          ISPH_CHECK_HIP(hipMemcpyAsync(td[j].p, arr[j].a, sizeof(double) * own, hipMemcpyHostToDevice, st));
+          F.a[j] = td[j].p;
+        }
+      }
+    }
+    F.width = F.off[narrays];
+    ISPH_CHECK(sbuf.reserve((size_t)(H.nsend > 0 ? H.nsend : 1) * F.width));
+    ISPH_CHECK(rbuf.reserve((size_t)(H.nrecv > 0 ? H.nrecv : 1) * F.width));
+    return ISPH_SUCCESS;
+  };
+  int rc = local();
+  if (agree) (void)comm_consensus(ctx, comm_active(ctx) && ctx->nranks > 1, "isph_nlist_forward_multi", kDdBroken, nullptr, 0, rc);
+  ISPH_CHECK(rc);
+  const long long ns = (long long)H.nsend * F.width, ne = (long long)ng * F.width;
+  if (ns > 0)
+    hipLaunchKernelGGL(k_dd_fwd_pack_multi, dd_grid(ns), dim3(kBlock), 0, st, ns, F, (const int *)H.send_idx.p, sbuf.p);
+  ISPH_CHECK(comm_exchange(ctx, H, sbuf.p, rbuf.p, F.width, false, st));
+  if (ne > 0)
+    hipLaunchKernelGGL(k_dd_fwd_gather_multi, dd_grid(ne), dim3(kBlock), 0, st, ne, F, n, nl->ncol, (const int *)nl->colmap.p,
+                       (const double *)rbuf.p);
+  if (!on_device && ng > 0)
+    for (int j = 0; j < narrays; ++j) {
+      const size_t own = (size_t)n * (size_t)arr[j].ncomp, gh = (size_t)ng * (size_t)arr[j].ncomp;
+      if (F.is_int[j]) ISPH_CHECK_HIP(hipMemcpyAsync((int *)arr[j].a + own, ti[j].p + own, sizeof(int) * gh, hipMemcpyDeviceToHost, st));
+      else ISPH_CHECK_HIP(hipMemcpyAsync((double *)arr[j].a + own, td[j].p + own, sizeof(double) * gh, hipMemcpyDeviceToHost, st));
+    }
+  ISPH_CHECK_HIP(hipStreamSynchronize(st));
+  ISPH_CHECK_HIP(hipGetLastError());
+  return ISPH_SUCCESS;
+}
+
 // ---- migration ----------------------------------------------------------------------------------------------------------
 
 struct MgGeom {
@@ -927,6 +1036,11 @@ int isph_nlist_forward(isph_ctx *ctx, const isph_nlist *nl, int ncomp, double *a
 int isph_nlist_forward_int(isph_ctx *ctx, const isph_nlist *nl, int ncomp, int *a, int on_device) {
   ISPH_REQUIRE(ctx && nl, "NULL argument");
   return isph::nlist_forward<int>(ctx, nl, ncomp, a, on_device);
+}
+
+int isph_nlist_forward_multi(isph_ctx *ctx, const isph_nlist *nl, int narrays, const isph_fwd_array *arr, int on_device) {
+  ISPH_REQUIRE(ctx && nl, "NULL argument");
+  return isph::nlist_forward_multi(ctx, nl, narrays, arr, on_device, /*agree=*/true);
 }
 
 int isph_migrate(isph_ctx *ctx, const isph_decomp *dc, int nlocal, const double *x, int nd, const double *fd, int ni, const int *fi,

@@ -1,6 +1,7 @@
 // step_ops.hpp -- the glue of a time step that is no neighbour sweep: the forward comm of periodic images on one rank,
 // computeZeroMeanPressure, and the two observables the reference's scripts record (compute isph/status, fix isph/tgv).
-// Included by isph_capi.hip; every entry point is usable on its own.
+// Included by isph_capi.hip; every entry point is usable on its own.  The last three have a collective form over the
+// ranks of a communicator (isph_*_dist, at the end of the namespace).
 //
 // Reductions follow the discipline of the solvers' multi-dot (krylov.hpp): a grid that depends on n alone, every block
 // sums a fixed set of rows in a fixed order into its own slot, one block per quantity then sums the slots in a fixed
@@ -10,6 +11,7 @@
 
 #include "amg.hpp"  // wave_max_f64
 #include "assemble.hpp"
+#include "comm.hpp"
 #include "core.hpp"
 #include "operators.hpp"  // InOut
 
@@ -202,13 +204,13 @@ __global__ __launch_bounds__(kBlock) void k_tgv_pressure_sum(int nlocal, const d
   block_partials<1, false>(acc, 0.0, partial);
 }
 
-// psum[0] = sum of p over the owned rows (on the device); the exact pressure has mean 0 (fix_isph_tgv.cpp:77)
-__global__ __launch_bounds__(kBlock) void k_tgv_error(int nlocal, double t, double umax, const double *__restrict__ psum,
-                                                      const double *__restrict__ x, const double *__restrict__ vnp1,
-                                                      const double *__restrict__ p, const double *__restrict__ rho,
-                                                      const double *__restrict__ nu, double *__restrict__ partial) {
+// the four sums of this rank's rows with the pressure mean pavg_diff removed; the exact pressure has mean 0
+// (fix_isph_tgv.cpp:77)
+__device__ __forceinline__ void tgv_error_sums(int nlocal, double t, double umax, double pavg_diff, const double *__restrict__ x,
+                                               const double *__restrict__ vnp1, const double *__restrict__ p,
+                                               const double *__restrict__ rho, const double *__restrict__ nu,
+                                               double *__restrict__ partial) {
   double acc[4] = {0.0, 0.0, 0.0, 0.0};  // errorp, normp, erroru, normu
-  const double pavg_diff = nlocal > 0 ? psum[0] / (double)nlocal : 0.0;
   const long long stride = (long long)gridDim.x * kBlock;
   for (long long i = (long long)blockIdx.x * kBlock + threadIdx.x; i < nlocal; i += stride) {
     const double x0 = x[3 * i], x1 = x[3 * i + 1];
@@ -223,6 +225,14 @@ __global__ __launch_bounds__(kBlock) void k_tgv_error(int nlocal, double t, doub
     acc[3] += u0 * u0 + u1 * u1;
   }
   block_partials<4, false>(acc, 0.0, partial);
+}
+
+// psum[0] = sum of p over the owned rows (on the device)
+__global__ __launch_bounds__(kBlock) void k_tgv_error(int nlocal, double t, double umax, const double *__restrict__ psum,
+                                                      const double *__restrict__ x, const double *__restrict__ vnp1,
+                                                      const double *__restrict__ p, const double *__restrict__ rho,
+                                                      const double *__restrict__ nu, double *__restrict__ partial) {
+  tgv_error_sums(nlocal, t, umax, nlocal > 0 ? psum[0] / (double)nlocal : 0.0, x, vnp1, p, rho, nu, partial);
 }
 
 // device operands; out[4] on the host
@@ -245,17 +255,12 @@ inline int tgv_error_device(isph_ctx *ctx, int nlocal, const double *d_x, const 
   return ISPH_SUCCESS;
 }
 
-// device operands; out[8] on the host
-inline int status_device(isph_ctx *ctx, int nlocal, int type_mask, const double *d_x, const int *d_type, const double *d_vfrac,
-                         const double *d_v, const double *d_rho, const double centre[3], double radius, double out[8]) {
-  DevTmp<double> partial, scal;
-  const int g = step_red_grid(nlocal);
-  ISPH_CHECK(partial.reserve((size_t)8 * g));
-  ISPH_CHECK(scal.reserve(8));
+// the arguments of k_status.  The reference tests sqrt(r^2) <= radius and keeps max sqrt(|v|^2).  The correctly rounded
+// root is monotone, so the first is a threshold on r^2 and the second is the root of the maximum: both roots are taken on
+// the host, exactly.
+inline StatusArgs status_args(int nlocal, int type_mask, const double centre[3], double radius) {
   StatusArgs s;
   s.nlocal = nlocal; s.type_mask = type_mask;
-  // the reference tests sqrt(r^2) <= radius and keeps max sqrt(|v|^2).  The correctly rounded root is monotone, so the
-  // first is a threshold on r^2 and the second is the root of the maximum: both roots are taken on the host, exactly.
   s.with_max = radius > 0.0;
   s.rsq_max = radius * radius;
   if (s.with_max && std::isfinite(s.rsq_max)) {
@@ -264,6 +269,17 @@ inline int status_device(isph_ctx *ctx, int nlocal, int type_mask, const double 
       s.rsq_max = std::nextafter(s.rsq_max, INFINITY);
   }
   for (int k = 0; k < 3; ++k) s.c[k] = centre[k];
+  return s;
+}
+
+// device operands; out[8] on the host
+inline int status_device(isph_ctx *ctx, int nlocal, int type_mask, const double *d_x, const int *d_type, const double *d_vfrac,
+                         const double *d_v, const double *d_rho, const double centre[3], double radius, double out[8]) {
+  DevTmp<double> partial, scal;
+  const int g = step_red_grid(nlocal);
+  ISPH_CHECK(partial.reserve((size_t)8 * g));
+  ISPH_CHECK(scal.reserve(8));
+  const StatusArgs s = status_args(nlocal, type_mask, centre, radius);
   hipLaunchKernelGGL(k_status, dim3(g), dim3(kBlock), 0, ctx->stream, s, d_x, d_type, d_vfrac, d_v, d_rho, partial.p);
   hipLaunchKernelGGL(k_step_reduce, dim3(8), dim3(kBlock), 0, ctx->stream, g, 7, (const double *)partial.p, scal.p);
   ISPH_CHECK_HIP(hipMemcpyAsync(out, scal.p, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -276,6 +292,152 @@ inline int status_device(isph_ctx *ctx, int nlocal, int type_mask, const double 
 inline int step_one_rank(const isph_ctx *ctx, const char *msg) {
   ISPH_REQUIRE(ctx->nranks == 1 && !ctx->comm && !ctx->host_tr.allreduce, msg);
   return ISPH_SUCCESS;
+}
+
+// ---- the same three over the ranks of a communicator -----------------------------------------------------------------
+// Per rank the two-stage reduction above; the second stage writes the rank's sums into ITS slot of an [nranks][nq] vector
+// and zeros into the others, one sum all-reduce adds the vectors (adding zeros is exact, so every slot arrives with the
+// bits its rank computed, whatever order the transport adds in), and k_step_slot_combine adds the slots in rank order.
+// The maximum goes through a max all-reduce.  The bits of a result are the same on every rank, from run to run and from
+// transport to transport.  Without a communicator the one-rank forms above are called: their bits.
+
+inline bool step_dist(const isph_ctx *ctx) { return comm_active(ctx); }
+inline int step_rank(const isph_ctx *ctx) { return comm_active(ctx) ? ctx->rank : 0; }
+inline int step_nranks(const isph_ctx *ctx) { return comm_active(ctx) ? ctx->nranks : 1; }
+
+// second stage on a rank of several: block k sums partial[k * nblk + .] in the fixed order of k_step_reduce and writes
+// slots[r * nq + k] for every rank r -- the sum for r == rank, 0 for the others; quantity kmax is a maximum and goes to
+// maxout[0].  extra (k == kextra): a number the host knows (a row count) takes the place of the sum.
+__global__ __launch_bounds__(kBlock) void k_step_reduce_slots(int nblk, int kmax, int nranks, int rank, int nq, int kextra,
+                                                              double extra, const double *__restrict__ partial,
+                                                              double *__restrict__ slots, double *__restrict__ maxout) {
+  __shared__ double sw[4];
+  __shared__ double total;
+  const int k = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool is_max = k == kmax;
+  double a = 0.0;
+  if (k != kextra) {
+    const double *__restrict__ p = partial + (long long)k * nblk;
+    for (int b = threadIdx.x; b < nblk; b += kBlock) a = is_max ? fmax(a, p[b]) : a + p[b];
+  }
+  a = is_max ? wave_max_f64(a) : wave_sum(a);
+  if (lane == 0) sw[wave] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double t = is_max ? fmax(fmax(sw[0], sw[1]), fmax(sw[2], sw[3])) : (sw[0] + sw[1]) + (sw[2] + sw[3]);
+    total = k == kextra ? extra : t;
+    if (is_max) maxout[0] = t;
+  }
+  __syncthreads();
+  if (is_max) return;
+  for (int r = threadIdx.x; r < nranks; r += kBlock) slots[(long long)r * nq + k] = r == rank ? total : 0.0;
+}
+
+// out[k] = slots[0][k] + slots[1][k] + ... in rank order: one thread per quantity
+__global__ __launch_bounds__(kBlock) void k_step_slot_combine(int nranks, int nq, const double *__restrict__ slots,
+                                                              double *__restrict__ out) {
+  const int k = blockIdx.x * kBlock + threadIdx.x;
+  if (k >= nq) return;
+  double a = 0.0;
+  for (int r = 0; r < nranks; ++r) a += slots[(long long)r * nq + k];
+  out[k] = a;
+}
+
+// partial [nq x g] of this rank -> out[0 .. nq) summed over the ranks (on the device); quantity kmax, when >= 0, is not
+// part of nq: its maximum over the ranks lands in out[nq]
+inline int step_sum_ranks(isph_ctx *ctx, int g, int nq, int kmax, int kextra, double extra, const double *partial, double *out) {
+  const int nr = step_nranks(ctx);
+  DevTmp<double> slots;
+  ISPH_CHECK(slots.reserve((size_t)nr * nq));
+  hipLaunchKernelGGL(k_step_reduce_slots, dim3(nq + (kmax >= 0 ? 1 : 0)), dim3(kBlock), 0, ctx->stream, g, kmax, nr, step_rank(ctx),
+                     nq, kextra, extra, partial, slots.p, out + nq);
+  ISPH_CHECK_HIP(hipGetLastError());
+  ISPH_CHECK(comm_allreduce(ctx, slots.p, nr * nq, /*sum*/ 0, ctx->stream));
+  if (kmax >= 0) ISPH_CHECK(comm_allreduce(ctx, out + nq, 1, /*max*/ 1, ctx->stream));
+  hipLaunchKernelGGL(k_step_slot_combine, dim3((nq + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, nr, nq,
+                     (const double *)slots.p, out);
+  ISPH_CHECK_HIP(hipGetLastError());
+  // the slots go back to the pool when this returns: the combine must have read them (the pool parks a block until the
+  // device has been synchronised, so the launch above is safe)
+  return ISPH_SUCCESS;
+}
+
+// zero_mean_device over all ranks: one sum all-reduce
+inline int zero_mean_dist_device(isph_ctx *ctx, int nlocal, int nall, const int *d_type, const int *d_kind, int ntypes, double *d_f,
+                                 int update, double *mean_out) {
+  if (!step_dist(ctx)) return zero_mean_device(ctx, nlocal, nall, d_type, d_kind, ntypes, d_f, update, mean_out);
+  DevTmp<double> partial, scal;
+  const int g = step_red_grid(nlocal);
+  ISPH_CHECK(partial.reserve((size_t)2 * g));
+  ISPH_CHECK(scal.reserve(2));
+  hipLaunchKernelGGL(k_zero_mean_sum, dim3(g), dim3(kBlock), 0, ctx->stream, nlocal, ntypes, d_type, d_kind, d_f, partial.p);
+  ISPH_CHECK(step_sum_ranks(ctx, g, 2, -1, -1, 0.0, partial.p, scal.p));
+  if (update && nall > 0)
+    hipLaunchKernelGGL(k_zero_mean_subtract, dim3((nall + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, nall, ntypes,
+                       d_type, d_kind, (const double *)scal.p, d_f);
+  ISPH_CHECK_HIP(hipGetLastError());
+  if (mean_out) {
+    double h[2] = {0.0, 0.0};
+    ISPH_CHECK_HIP(hipMemcpyAsync(h, scal.p, 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    *mean_out = h[1] == 0.0 ? 0.0 : h[0] / h[1];
+  }
+  return ISPH_SUCCESS;
+}
+
+// psum = {sum of p, number of rows} over the owned rows of ALL ranks
+__global__ __launch_bounds__(kBlock) void k_tgv_error_dist(int nlocal, double t, double umax, const double *__restrict__ psum,
+                                                           const double *__restrict__ x, const double *__restrict__ vnp1,
+                                                           const double *__restrict__ p, const double *__restrict__ rho,
+                                                           const double *__restrict__ nu, double *__restrict__ partial) {
+  tgv_error_sums(nlocal, t, umax, psum[1] > 0.0 ? psum[0] / psum[1] : 0.0, x, vnp1, p, rho, nu, partial);
+}
+
+// tgv_error_device over all ranks: two sum all-reduces (the pressure mean and the row count, then the four sums)
+inline int tgv_error_dist_device(isph_ctx *ctx, int nlocal, const double *d_x, const double *d_vnp1, const double *d_p,
+                                 const double *d_rho, const double *d_nu, double t, double umax, double out[4]) {
+  if (!step_dist(ctx)) return tgv_error_device(ctx, nlocal, d_x, d_vnp1, d_p, d_rho, d_nu, t, umax, out);
+  DevTmp<double> partial, scal;
+  const int g = step_red_grid(nlocal);
+  ISPH_CHECK(partial.reserve((size_t)4 * g));
+  ISPH_CHECK(scal.reserve(6));
+  hipLaunchKernelGGL(k_tgv_pressure_sum, dim3(g), dim3(kBlock), 0, ctx->stream, nlocal, d_p, partial.p);
+  ISPH_CHECK(step_sum_ranks(ctx, g, 2, -1, /*kextra=*/1, (double)nlocal, partial.p, scal.p + 4));
+  hipLaunchKernelGGL(k_tgv_error_dist, dim3(g), dim3(kBlock), 0, ctx->stream, nlocal, t, umax, (const double *)(scal.p + 4), d_x,
+                     d_vnp1, d_p, d_rho, d_nu, partial.p);
+  ISPH_CHECK(step_sum_ranks(ctx, g, 4, -1, -1, 0.0, partial.p, scal.p));
+  double h[6];
+  ISPH_CHECK_HIP(hipMemcpyAsync(h, scal.p, 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  for (int k = 0; k < 4; ++k) out[k] = h[5] > 0.0 ? std::sqrt(h[k] / h[5]) : 0.0;
+  return ISPH_SUCCESS;
+}
+
+// status_device over all ranks: one sum all-reduce of the seven sums, one max all-reduce
+inline int status_dist_device(isph_ctx *ctx, int nlocal, int type_mask, const double *d_x, const int *d_type, const double *d_vfrac,
+                              const double *d_v, const double *d_rho, const double centre[3], double radius, double out[8]) {
+  if (!step_dist(ctx)) return status_device(ctx, nlocal, type_mask, d_x, d_type, d_vfrac, d_v, d_rho, centre, radius, out);
+  DevTmp<double> partial, scal;
+  const int g = step_red_grid(nlocal);
+  ISPH_CHECK(partial.reserve((size_t)8 * g));
+  ISPH_CHECK(scal.reserve(8));
+  const StatusArgs s = status_args(nlocal, type_mask, centre, radius);
+  hipLaunchKernelGGL(k_status, dim3(g), dim3(kBlock), 0, ctx->stream, s, d_x, d_type, d_vfrac, d_v, d_rho, partial.p);
+  ISPH_CHECK(step_sum_ranks(ctx, g, 7, /*kmax=*/7, -1, 0.0, partial.p, scal.p));
+  ISPH_CHECK_HIP(hipMemcpyAsync(out, scal.p, 8 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  ISPH_CHECK_HIP(hipGetLastError());
+  out[7] = std::sqrt(out[7]);
+  return ISPH_SUCCESS;
+}
+
+// the argument checks of a collective primitive are made by every rank before the first all-reduce: a rank whose
+// arguments are refused fails the others with it
+inline int step_agree(isph_ctx *ctx, const char *who, int rc) {
+  const bool dist = comm_active(ctx) && ctx->nranks > 1;
+  (void)comm_consensus(ctx, dist, who, "the consensus all-reduce failed", nullptr, 0, rc);
+  return rc;
 }
 
 }  // namespace isph
@@ -354,6 +516,72 @@ int isph_tgv_error(isph_ctx *ctx, int nlocal, int dim, const double *x, const do
   ISPH_CHECK(stage(ctx, rho, n, on_device, srho, &drho));
   ISPH_CHECK(stage(ctx, nu, n, on_device, snu, &dnu));
   return tgv_error_device(ctx, nlocal, dx, dv, dp, drho, dnu, t, umax, out);
+}
+
+int isph_zero_mean_pressure_dist(isph_ctx *ctx, int nlocal, int nall, const int *type, const int *kind, int ntypes, double *f,
+                                 int update, double *mean_out, int on_device) {
+  using namespace isph;
+  ISPH_REQUIRE(ctx, "NULL argument");
+  DevTmp<int> stype, skind;
+  const int *dtype = nullptr, *dkind = nullptr;
+  InOut fi;
+  auto local = [&]() -> int {
+    ISPH_REQUIRE(kind && (nall == 0 || (type && f)), "NULL argument");
+    ISPH_REQUIRE(nlocal >= 0 && nall >= nlocal && ntypes >= 0, "isph_zero_mean_pressure_dist: need 0 <= nlocal <= nall, ntypes >= 0");
+    ISPH_CHECK(stage(ctx, type, (size_t)nall, on_device, stype, &dtype));
+    ISPH_CHECK(stage(ctx, kind, (size_t)ntypes + 1, 0, skind, &dkind));
+    if (nall > 0) ISPH_CHECK(fi.open(ctx, f, (size_t)nall, on_device));
+    return ISPH_SUCCESS;
+  };
+  ISPH_CHECK(step_agree(ctx, "isph_zero_mean_pressure_dist", local()));
+  ISPH_CHECK(zero_mean_dist_device(ctx, nlocal, nall, dtype, dkind, ntypes, fi.dev, update, mean_out));
+  if (nall > 0) ISPH_CHECK(fi.close(ctx));
+  ISPH_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return ISPH_SUCCESS;
+}
+
+int isph_status_dist(isph_ctx *ctx, const isph_particles *P, int type_mask, const double *v, const double *rho,
+                     const double centre[3], double radius, double out[8], int on_device) {
+  using namespace isph;
+  ISPH_REQUIRE(ctx && P && centre && out, "NULL argument");
+  DevTmp<double> sx, svf, sv, srho;
+  DevTmp<int> stype;
+  const double *dx = nullptr, *dvf = nullptr, *dv = nullptr, *drho = nullptr;
+  const int *dtype = nullptr;
+  auto local = [&]() -> int {
+    ISPH_REQUIRE(P->nlocal >= 0, "isph_status_dist: nlocal must not be negative");
+    const size_t n = (size_t)P->nlocal;
+    ISPH_REQUIRE(n == 0 || (P->x && P->type && P->vfrac && v && rho), "isph_status_dist: x, type, vfrac, v and rho are needed");
+    ISPH_CHECK(stage(ctx, P->x, 3 * n, on_device, sx, &dx));
+    ISPH_CHECK(stage(ctx, P->type, n, on_device, stype, &dtype));
+    ISPH_CHECK(stage(ctx, P->vfrac, n, on_device, svf, &dvf));
+    ISPH_CHECK(stage(ctx, v, 3 * n, on_device, sv, &dv));
+    ISPH_CHECK(stage(ctx, rho, n, on_device, srho, &drho));
+    return ISPH_SUCCESS;
+  };
+  ISPH_CHECK(step_agree(ctx, "isph_status_dist", local()));
+  return status_dist_device(ctx, P->nlocal, type_mask, dx, dtype, dvf, dv, drho, centre, radius, out);
+}
+
+int isph_tgv_error_dist(isph_ctx *ctx, int nlocal, int dim, const double *x, const double *vnp1, const double *p,
+                        const double *rho, const double *nu, double t, double umax, double out[4], int on_device) {
+  using namespace isph;
+  ISPH_REQUIRE(ctx && out, "NULL argument");
+  DevTmp<double> sx, sv, sp, srho, snu;
+  const double *dx = nullptr, *dv = nullptr, *dp = nullptr, *drho = nullptr, *dnu = nullptr;
+  auto local = [&]() -> int {
+    ISPH_REQUIRE(nlocal >= 0 && (dim == 2 || dim == 3), "isph_tgv_error_dist: need nlocal >= 0 and dim 2 or 3");
+    ISPH_REQUIRE(nlocal == 0 || (x && vnp1 && p && rho && nu), "NULL argument");
+    const size_t n = (size_t)nlocal;
+    ISPH_CHECK(stage(ctx, x, 3 * n, on_device, sx, &dx));
+    ISPH_CHECK(stage(ctx, vnp1, 3 * n, on_device, sv, &dv));
+    ISPH_CHECK(stage(ctx, p, n, on_device, sp, &dp));
+    ISPH_CHECK(stage(ctx, rho, n, on_device, srho, &drho));
+    ISPH_CHECK(stage(ctx, nu, n, on_device, snu, &dnu));
+    return ISPH_SUCCESS;
+  };
+  ISPH_CHECK(step_agree(ctx, "isph_tgv_error_dist", local()));
+  return tgv_error_dist_device(ctx, nlocal, dx, dv, dp, drho, dnu, t, umax, out);
 }
 
 }  // extern "C"

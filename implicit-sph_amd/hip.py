@@ -44,6 +44,8 @@ EXPORTS = [
     "isph_ins_params_default", "isph_ins_create", "isph_ins_destroy", "isph_ins_set_state", "isph_ins_set_list", "isph_ins_rebuild",
     "isph_ins_sizes", "isph_ins_get", "isph_ins_pre", "isph_ins_view", "isph_ins_force", "isph_ins_add_force", "isph_ins_solve",
     "isph_ins_advance", "isph_ins_shift", "isph_ins_diagnostics", "isph_ins_run",
+    "isph_nlist_forward_multi", "isph_zero_mean_pressure_dist", "isph_status_dist", "isph_tgv_error_dist",
+    "isph_ins_create_dist", "isph_ins_set_state_dist", "isph_ins_sizes_dist",
 ]
 
 
@@ -373,6 +375,13 @@ def lib():
         L.isph_ins_shift.argtypes = [C.c_void_p, C.c_void_p]
         L.isph_ins_diagnostics.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
         L.isph_ins_run.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.isph_nlist_forward_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        L.isph_zero_mean_pressure_dist.argtypes = L.isph_zero_mean_pressure.argtypes
+        L.isph_status_dist.argtypes = L.isph_status.argtypes
+        L.isph_tgv_error_dist.argtypes = L.isph_tgv_error.argtypes
+        L.isph_ins_create_dist.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.isph_ins_set_state_dist.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_int]
+        L.isph_ins_sizes_dist.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1973,6 +1982,10 @@ class _CDecomp(C.Structure):
                 ("pgrid", C.c_int * 3), ("faces", C.c_void_p * 3)]
 
 
+class _FwdArray(C.Structure):
+    _fields_ = [("a", C.c_void_p), ("ncomp", C.c_int), ("is_int", C.c_int)]
+
+
 class Decomp:
     """isph_decomp: a brick of pgrid[0] x pgrid[1] x pgrid[2] ranks over the box lo .. hi (`dim` entries each, or three);
     rank = cx + pgrid[0] * (cy + pgrid[1] * cz).  faces: None (uniform cuts) or per axis None / the pgrid[a] + 1 cut planes
@@ -2089,6 +2102,30 @@ class NeighbourListDist(NeighbourList):
         _check(fn(self.ctx.h, self.h, nc, _ptr(a) if nall else None, _on_device(a)))
         return a
 
+    def forward_multi(self, arrays):
+        """isph_nlist_forward_multi: the forward of up to 8 arrays ([nall] or [nall, ncomp], float64 or int32, C contiguous,
+        all numpy or all device tensors) in ONE exchange, in place.  Collective.  Returns the list."""
+        arrays = list(arrays)
+        if not 1 <= len(arrays) <= 8:
+            raise OperandError("forward_multi takes 1 to 8 arrays, %d given" % len(arrays))
+        i = self.info
+        nall = i["nlocal"] + i["nghost"]
+        rec = (_FwdArray * len(arrays))()
+        for j, a in enumerate(arrays):
+            if a.ndim not in (1, 2) or int(a.shape[0]) != nall:
+                raise OperandError("array %d: %s given, [nall = %d] or [nall][ncomp] needed" % (j, tuple(a.shape), nall))
+            kind = str(a.dtype).replace("torch.", "")
+            if kind not in ("float64", "int32"):
+                raise ValueError("array %d: float64 or int32 needed, got %s" % (j, a.dtype))
+            if (_is_torch(a) and not a.is_contiguous()) or (not _is_torch(a) and not a.flags.c_contiguous):
+                raise ValueError("array %d: a C-contiguous array is updated in place" % j)
+            nc = 1 if a.ndim == 1 else int(a.shape[1])
+            if nc < 1:
+                raise OperandError("array %d needs at least one component" % j)
+            rec[j].a, rec[j].ncomp, rec[j].is_int = (_ptr(a) if nall else None), nc, int(kind == "int32")
+        _check(lib().isph_nlist_forward_multi(self.ctx.h, self.h, len(arrays), rec, _on_device(*arrays)))
+        return arrays
+
 
 def migrate(ctx, decomp, x, fd=None, fi=None):
     """isph_migrate (Comm::exchange): x [nlocal, 3] is wrapped and every particle goes to the rank whose sub-box holds it,
@@ -2162,9 +2199,8 @@ def ghost_fill(ctx, nlocal, owner, a):
     return a
 
 
-def zero_mean_pressure(ctx, nlocal, type, kinds, f, update=True, want_mean=True):
-    """isph_zero_mean_pressure: in place on f [nall] (numpy or device tensor, like type); kinds = the kind of type 1, 2,
-    ... as in particles_view (None: all Fluid).  Returns the mean (None when want_mean is False: nothing is read back)."""
+def _zero_mean_call(fn, ctx, nlocal, type, kinds, f, update, want_mean):
+    """the operand checks and the call isph_zero_mean_pressure and its _dist form share"""
     typ = _i32(type)
     nall = int(typ.numel()) if _is_torch(typ) else int(typ.size)
     nlocal = int(nlocal)
@@ -2181,17 +2217,30 @@ def zero_mean_pressure(ctx, nlocal, type, kinds, f, update=True, want_mean=True)
         raise OperandError("nlocal = %d outside [0, nall = %d]" % (nlocal, nall))
     _need(f, nall, "f [nall]")
     mean = C.c_double(0.0)
-    _check(lib().isph_zero_mean_pressure(ctx.h if ctx is not None else None, nlocal, nall, _ptr(typ), _ptr(kind), ntypes,
-                                         _ptr(f), int(bool(update)), C.byref(mean) if want_mean else None, dev))
+    _check(fn(ctx.h if ctx is not None else None, nlocal, nall, _ptr(typ), _ptr(kind), ntypes, _ptr(f), int(bool(update)),
+              C.byref(mean) if want_mean else None, dev))
     return mean.value if want_mean else None
+
+
+def zero_mean_pressure(ctx, nlocal, type, kinds, f, update=True, want_mean=True):
+    """isph_zero_mean_pressure: in place on f [nall] (numpy or device tensor, like type); kinds = the kind of type 1, 2,
+    ... as in particles_view (None: all Fluid).  Returns the mean (None when want_mean is False: nothing is read back)."""
+    return _zero_mean_call(lib().isph_zero_mean_pressure, ctx, nlocal, type, kinds, f, update, want_mean)
+
+
+def zero_mean_pressure_dist(ctx, nlocal, type, kinds, f, update=True, want_mean=True):
+    """isph_zero_mean_pressure_dist: zero_mean_pressure over the owned rows of ALL ranks of ctx.  COLLECTIVE; pass kinds
+    (the table cannot be guessed from one rank's types)."""
+    if kinds is None:
+        raise ValueError("zero_mean_pressure_dist: kinds is needed")
+    return _zero_mean_call(lib().isph_zero_mean_pressure_dist, ctx, nlocal, type, kinds, f, update, want_mean)
 
 
 STATUS_FIELDS = ("count", "sum_vx", "sum_vy", "sum_vz", "volume", "mass", "kinetic_energy", "vmax")
 
 
-def status(ctx, nlocal, x, type, vfrac, v, rho, type_mask=-1, centre=(0.0, 0.0, 0.0), radius=0.0):
-    """isph_status == compute isph/status over the owned rows: numpy array of the eight numbers STATUS_FIELDS names.
-    x, v [>= nlocal, 3]; type, vfrac, rho [>= nlocal]; all numpy or all device tensors."""
+def _status_call(fn, ctx, nlocal, x, type, vfrac, v, rho, type_mask, centre, radius):
+    """the operand checks and the call isph_status and its _dist form share"""
     n = int(nlocal)
     x, v, vfrac, rho, typ = _f64(x), _f64(v), _f64(vfrac), _f64(rho), _i32(type)
     dev = _on_device(x, v, vfrac, rho, typ)
@@ -2204,23 +2253,43 @@ def status(ctx, nlocal, x, type, vfrac, v, rho, type_mask=-1, centre=(0.0, 0.0, 
     out = (C.c_double * 8)()
     mask = int(type_mask) & 0xFFFFFFFF
     mask = mask - (1 << 32) if mask >= (1 << 31) else mask
-    _check(lib().isph_status(ctx.h if ctx is not None else None, C.byref(pv), mask, _ptr(v), _ptr(rho), c, float(radius), out,
-                             dev))
+    _check(fn(ctx.h if ctx is not None else None, C.byref(pv), mask, _ptr(v), _ptr(rho), c, float(radius), out, dev))
     return np.array(out[:], dtype=np.float64)
 
 
-def tgv_error(ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim=2):
-    """isph_tgv_error == the error of fix isph/tgv: (p_err, p_norm, u_err, u_norm).  x, vnp1 [>= nlocal, 3]; p, rho, nu
-    [>= nlocal]; all numpy or all device tensors."""
+def status(ctx, nlocal, x, type, vfrac, v, rho, type_mask=-1, centre=(0.0, 0.0, 0.0), radius=0.0):
+    """isph_status == compute isph/status over the owned rows: numpy array of the eight numbers STATUS_FIELDS names.
+    x, v [>= nlocal, 3]; type, vfrac, rho [>= nlocal]; all numpy or all device tensors."""
+    return _status_call(lib().isph_status, ctx, nlocal, x, type, vfrac, v, rho, type_mask, centre, radius)
+
+
+def status_dist(ctx, nlocal, x, type, vfrac, v, rho, type_mask=-1, centre=(0.0, 0.0, 0.0), radius=0.0):
+    """isph_status_dist: status over the owned rows of ALL ranks of ctx; the same bits on every rank.  COLLECTIVE."""
+    return _status_call(lib().isph_status_dist, ctx, nlocal, x, type, vfrac, v, rho, type_mask, centre, radius)
+
+
+def _tgv_error_call(fn, ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim):
+    """the operand checks and the call isph_tgv_error and its _dist form share"""
     n = int(nlocal)
     x, vnp1, p, rho, nu = _f64(x), _f64(vnp1), _f64(p), _f64(rho), _f64(nu)
     dev = _on_device(x, vnp1, p, rho, nu)
     _need(x, 3 * n, "x [nlocal][3]"); _need(vnp1, 3 * n, "vnp1 [nlocal][3]"); _need(p, n, "p [nlocal]")
     _need(rho, n, "rho [nlocal]"); _need(nu, n, "nu [nlocal]")
     out = (C.c_double * 4)()
-    _check(lib().isph_tgv_error(ctx.h if ctx is not None else None, n, int(dim), _ptr(x), _ptr(vnp1), _ptr(p), _ptr(rho),
-                                _ptr(nu), float(t), float(umax), out, dev))
+    _check(fn(ctx.h if ctx is not None else None, n, int(dim), _ptr(x), _ptr(vnp1), _ptr(p), _ptr(rho), _ptr(nu), float(t),
+              float(umax), out, dev))
     return tuple(out[:])
+
+
+def tgv_error(ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim=2):
+    """isph_tgv_error == the error of fix isph/tgv: (p_err, p_norm, u_err, u_norm).  x, vnp1 [>= nlocal, 3]; p, rho, nu
+    [>= nlocal]; all numpy or all device tensors."""
+    return _tgv_error_call(lib().isph_tgv_error, ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim)
+
+
+def tgv_error_dist(ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim=2):
+    """isph_tgv_error_dist: tgv_error over the owned rows of ALL ranks of ctx; the same bits on every rank.  COLLECTIVE."""
+    return _tgv_error_call(lib().isph_tgv_error_dist, ctx, nlocal, x, vnp1, p, rho, nu, t, umax, dim)
 
 
 # ---- the time step of incompressible Navier-Stokes, resident on the device ------------------------------------------
@@ -2285,26 +2354,44 @@ DIAG_FIELDS = ("p_err", "p_norm", "u_err", "u_norm") + STATUS_FIELDS + ("iters_h
 _INS_FIELDS = {"x": (3, np.float64), "v": (3, np.float64), "vstar": (3, np.float64), "f": (3, np.float64),
                "normal": (3, np.float64), "p": (1, np.float64), "dp": (1, np.float64), "rho": (1, np.float64),
                "nu": (1, np.float64), "vfrac": (1, np.float64), "pnd": (1, np.float64), "Gc": (None, np.float64),
-               "Lc": (None, np.float64), "type": (1, np.int32), "owner": (1, np.int32)}
+               "Lc": (None, np.float64), "type": (1, np.int32), "owner": (1, np.int32), "tag": (1, np.int32),
+               "owner_rank": (1, np.int32), "colmap": (1, np.int32)}
 
 
 class InsStep:
     """isph_ins: one rank's Navier-Stokes state on the device; the methods are the phases of the reference
-    (include/isph_hip.h).  Operands are numpy arrays or device tensors."""
+    (include/isph_hip.h).  Operands are numpy arrays or device tensors.  With decomp (a hip.Decomp) it is the distributed
+    driver (isph_ins_create_dist): the state is this rank's share, set_state takes the particles' global ids as tag, and
+    every method is COLLECTIVE over the ranks of ctx.  With decomp=None nothing changes."""
 
-    def __init__(self, ctx, params):
+    def __init__(self, ctx, params, decomp=None):
         L = lib()
-        self.ctx, self.params, self.dim = ctx, params, int(params.c.dim)
+        self.ctx, self.params, self.dim, self.decomp = ctx, params, int(params.c.dim), decomp
         self.h = C.c_void_p()
-        _check(L.isph_ins_create(ctx.h, C.byref(params.c), C.byref(self.h)))
+        if decomp is None:
+            _check(L.isph_ins_create(ctx.h, C.byref(params.c), C.byref(self.h)))
+        else:
+            cd = decomp.c_struct()
+            _check(L.isph_ins_create_dist(ctx.h, C.byref(params.c), C.byref(cd), C.byref(self.h)))
 
-    def set_state(self, x, v, p, type, rho, nu):
+    def set_state(self, x, v, p, type, rho, nu, tag=None):
         x, v, p, rho, nu, typ = _f64(x), _f64(v), _f64(p), _f64(rho), _f64(nu), _i32(type)
         dev = _on_device(x, v, p, rho, nu, typ)
         n = int(typ.numel()) if _is_torch(typ) else int(typ.size)
         _need(x, 3 * n, "x [nlocal][3]"); _need(v, 3 * n, "v [nlocal][3]"); _need(p, n, "p [nlocal]")
         _need(rho, n, "rho [nlocal]"); _need(nu, n, "nu [nlocal]")
-        _check(lib().isph_ins_set_state(self.h, n, _ptr(x), _ptr(v), _ptr(p), _ptr(typ), _ptr(rho), _ptr(nu), dev))
+        if self.decomp is None:
+            if tag is not None:
+                raise ValueError("set_state: tag belongs to the distributed driver (InsStep(ctx, params, decomp))")
+            _check(lib().isph_ins_set_state(self.h, n, _ptr(x), _ptr(v), _ptr(p), _ptr(typ), _ptr(rho), _ptr(nu), dev))
+            return
+        if tag is None:
+            raise ValueError("set_state: the distributed driver needs tag, the particles' global ids")
+        tag = _i32(tag)
+        _on_device(x, tag)
+        _need(tag, n, "tag [nlocal]")
+        args = [_ptr(a) if n else None for a in (x, v, p, typ, rho, nu, tag)]
+        _check(lib().isph_ins_set_state_dist(self.h, n, *args, dev))
 
     def set_list(self, x_all, owner, neigh_ptr, neigh_idx):
         """the caller's ghosts (x_all [nall, 3]), owners [nall] and full list (int32 or int64 offsets [nlocal + 1])"""
@@ -2324,10 +2411,17 @@ class InsStep:
         _check(lib().isph_ins_rebuild(self.h))
 
     def sizes(self):
+        """dict(nlocal, nall, entries, step, pre_done, solid_present); the distributed driver adds ncol, npeers, noffrank,
+        sent and received (by the last rebuild) and nglobal (the particles of all ranks)"""
         a = (C.c_longlong * 6)()
         _check(lib().isph_ins_sizes(self.h, a))
-        return dict(nlocal=int(a[0]), nall=int(a[1]), entries=int(a[2]), step=int(a[3]), pre_done=bool(a[4]),
-                    solid_present=bool(a[5]))
+        d = dict(nlocal=int(a[0]), nall=int(a[1]), entries=int(a[2]), step=int(a[3]), pre_done=bool(a[4]),
+                 solid_present=bool(a[5]))
+        if self.decomp is not None:
+            b = (C.c_longlong * 10)()
+            _check(lib().isph_ins_sizes_dist(self.h, b))
+            d.update(ncol=int(b[4]), npeers=int(b[5]), noffrank=int(b[6]), sent=int(b[7]), received=int(b[8]), nglobal=int(b[9]))
+        return d
 
     def get(self, name, ghosts=False, device=False):
         """a copy of a field: numpy array, or a device tensor with device=True"""

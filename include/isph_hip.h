@@ -1321,6 +1321,17 @@ int isph_nlist_dist_get(isph_ctx *ctx, const isph_nlist *nl, int *owner_rank, in
  * this rank (self-images) or through one exchange of the distinct ghost columns over the list's plan.  Collective. */
 int isph_nlist_forward(isph_ctx *ctx, const isph_nlist *nl, int ncomp, double *a, int on_device);
 int isph_nlist_forward_int(isph_ctx *ctx, const isph_nlist *nl, int ncomp, int *a, int on_device);
+/* The forward comm of up to 8 per-atom arrays in ONE exchange, as PairISPH::pack_forward_comm sends several fields per
+ * message: a record of sum(ncomp) doubles per listed atom, ints travelling as doubles.  arr[j].a is [nall][ncomp] doubles,
+ * or ints when is_int != 0, [h|d] per on_device, updated in place.  The result equals narrays single forwards bit for
+ * bit.  Collective: the arguments are checked before a consensus (one max all-reduce) that stands before the exchange,
+ * so a rank whose arguments are refused fails its peers with it ("... failed on another rank"). */
+typedef struct {
+  void *a;
+  int ncomp;
+  int is_int;
+} isph_fwd_array;
+int isph_nlist_forward_multi(isph_ctx *ctx, const isph_nlist *nl, int narrays, const isph_fwd_array *arr, int on_device);
 
 /* Comm::exchange: the positions x [nlocal][3] are wrapped; a particle whose wrapped position lies in another sub-box goes
  * to that rank with its nd doubles fd [nlocal][nd] and ni ints fi [nlocal][ni] (either may be 0 / NULL).  The target must
@@ -1337,8 +1348,9 @@ int isph_migrated_destroy(isph_ctx *ctx, isph_migrated *mg);
 
 /* ---- the glue of a time step: ghost rows, zero-mean pressure, observables ----------------------------------------- */
 
-/* What a time step needs between the neighbour sweeps, and the numbers the reference's scripts record, for ONE rank: every
- * entry point of this section refuses a context with a communicator (isph_ctx_create_dist / _hostcomm) by name.  All
+/* What a time step needs between the neighbour sweeps, and the numbers the reference's scripts record, for ONE rank: isph_ghost_fill,
+ * isph_zero_mean_pressure, isph_status and isph_tgv_error refuse a context with a communicator (isph_ctx_create_dist /
+ * _hostcomm) by name; the forms over several ranks are isph_nlist_forward and the three *_dist entry points below.  All
  * pointers [h|d] per on_device unless marked host; work buffers come from the library's pool; everything runs on the
  * context's stream.  The sums are two-stage reductions over a partition that depends on the row count alone, summed in a
  * fixed order, without floating-point atomics (the discipline of the solvers' multi-dot): the bits of a result do not
@@ -1379,6 +1391,30 @@ int isph_status(isph_ctx *ctx, const isph_particles *P, int type_mask, const dou
 int isph_tgv_error(isph_ctx *ctx, int nlocal, int dim, const double *x, const double *vnp1, const double *p,
                    const double *rho, const double *nu, double t, double umax, double out[4] /*host*/, int on_device);
 
+/* The same three over the ranks of the context's communicator.  COLLECTIVE: every rank calls, nlocal = 0 takes part; a
+ * context with RCCL, with the host-staged transport, or without a communicator is accepted.  A rank whose arguments are
+ * refused fails the others with it ("... failed on another rank") at a consensus that stands before the first all-reduce.
+ *   isph_zero_mean_pressure_dist  sum and count over the owned non-Solid rows of ALL ranks (one sum all-reduce); owned
+ *                                 Solid rows are zeroed; the mean is subtracted from all nall non-Solid entries of this
+ *                                 rank; a count of 0 over all ranks gives mean 0.
+ *   isph_status_dist              the seven sums (one sum all-reduce) and the maximum (one max all-reduce) over all ranks.
+ *   isph_tgv_error_dist           the pressure mean over the owned rows of all ranks first, then the four sums (two sum
+ *                                 all-reduces), then sqrt(sum / N) with N the rows of all ranks.
+ * The reduction: the two-stage fixed-order reduction per rank, whose result goes into the rank's slot of an nranks-wide
+ * device vector that is otherwise 0; the sum all-reduce adds the vectors -- adding zeros is exact, so every slot arrives
+ * with the bits its rank computed --; a small kernel adds the slots in rank order.  So the bits of a result are the same
+ * on every rank, from run to run and from transport to transport; they differ from the result of another rank count by
+ * round-off only; without a communicator they are the bits of the one-rank entry point. */
+int isph_zero_mean_pressure_dist(isph_ctx *ctx, int nlocal, int nall, const int *type /*[nall]*/, const int *kind /*[h]*/,
+                                 int ntypes, double *f /*[nall], in place*/, int update,
+                                 double *mean_out /*host, may be NULL*/, int on_device);
+int isph_status_dist(isph_ctx *ctx, const isph_particles *P, int type_mask, const double *v /*[nlocal][3]*/,
+                     const double *rho /*[nlocal]*/, const double centre[3] /*host*/, double radius,
+                     double out[8] /*host*/, int on_device);
+int isph_tgv_error_dist(isph_ctx *ctx, int nlocal, int dim, const double *x, const double *vnp1, const double *p,
+                        const double *rho, const double *nu, double t, double umax, double out[4] /*host*/,
+                        int on_device);
+
 /* ---- the time step of incompressible Navier-Stokes, resident on the device ------------------------------------------ */
 
 /* An isph_ins owns ONE rank's state on the device -- x, v, vstar, the force f and the wall normals [nall][3]; p, dp, rho,
@@ -1397,7 +1433,8 @@ int isph_tgv_error(isph_ctx *ctx, int nlocal, int dim, const double *x, const do
  * read back: the two counts of a list build, the solve infos, the shift's vmax; the owner map is validated once when a
  * list is taken; the zero-mean value stays on the device.
  *
- * Out of scope, refused by name: a context with a communicator (more than one rank); block Helmholtz
+ * Out of scope, refused by name: a context with a communicator (isph_ins_create is one rank; isph_ins_create_dist at the
+ * end of this section runs the same phases on a brick of ranks); block Helmholtz
  * (isph_assemble_block_helmholtz / isph_solve_block); the MorrisHolmes boundary; bd_coord and use_part wall normals; a
  * recycle handle; a context in hold-pattern mode (isph_ctx_hold_pattern).  Solid particles need antisym = 0 (the wall
  * normals read Gc).
@@ -1491,6 +1528,38 @@ int isph_ins_diagnostics(isph_ins *S, double t, double out[12] /*host*/);
  * t = step dt (steps count from 1 over the life of the state), then the Helmholtz and Poisson iteration counts and their
  * converged flags. */
 int isph_ins_run(isph_ins *S, int nsteps, double *diag);
+
+/* ---- the same driver on a brick of ranks ---------------------------------------------------------------------------- */
+
+/* An isph_ins made by isph_ins_create_dist owns ONE RANK's share of the particles and runs the same phases COLLECTIVELY
+ * over the decomposition: every rank makes every call.  The context has RCCL, the host-staged transport, or no
+ * communicator (a 1 x 1 (x 1) grid; the results then equal the one-rank driver's bit for bit).  The decomposition is
+ * copied, faces included.  Refused by name: prm->cut <= 0; a grid whose product differs from the context's rank count; a
+ * sub-box narrower than the cut; prm->lo / hi / periodic that are set (not all zero) and differ from the decomposition's;
+ * and what isph_ins_create refuses (block Helmholtz, MorrisHolmes, bd_coord / use_part, recycle, hold-pattern mode).
+ *
+ * isph_ins_set_state_dist: the particles this rank holds (nlocal = 0 allowed) with `tag`, the caller's global id, an int
+ * carried with the particle.  They must lie in the rank's sub-box or in a grid neighbour's: the first rebuild migrates
+ * them.  ONE sum all-reduce: the non-Solid rows of all ranks (the value of the SA-AMG null vector), the Solid rows, the
+ * particles, the failure flag -- a type outside [1, ntypes] on one rank fails ALL ranks, the others with "... failed on
+ * another rank".  isph_ins_set_state and isph_ins_set_list are refused on such a state by name.
+ *
+ * isph_ins_rebuild on such a state: v, p, rho, nu -> [nlocal][6] doubles, type, tag -> [nlocal][2] ints (one kernel);
+ * isph_migrate; unpack (one kernel); isph_nlist_build_dist with prune = 1; ONE isph_nlist_forward_multi of v, p, rho, nu,
+ * type, tag; the host null mask of isph_solve is remade from the types (a read-back of nlocal ints) only when a particle
+ * arrived or left.  Every other phase is the one-rank phase with: the forward through the list's plan for the ghost
+ * fills; the list's colmap and ncol, rank0 = (rank == 0) in the assemblers; isph_mat_set_halo from the list's plan on H
+ * and A; owned rows of vstar then its forward; the *_dist forms of the zero mean, the TGV error and the status; normals
+ * and pnd in ONE forward of 4 doubles per ghost.  A rank that fails in a phase carries its rc to the next consensus
+ * (before migration, before the list build, before the forward of the state, after each assembly), where all fail.
+ * isph_ins_get knows "tag", "owner_rank" and "colmap" on such a state; "owner" is the index on the owner's rank.
+ * The diag rows of isph_ins_run are the same bits on every rank. */
+int isph_ins_create_dist(isph_ctx *ctx, const isph_ins_params *prm, const isph_decomp *dc, isph_ins **S);
+int isph_ins_set_state_dist(isph_ins *S, int nlocal, const double *x, const double *v, const double *p, const int *type,
+                            const double *rho, const double *nu, const int *tag, int on_device);
+/* info: [0] nlocal [1] nall [2] list entries (-1: no list) [3] steps [4] ncol [5] npeers [6] off-rank ghosts
+ * [7] particles sent and [8] received by the last rebuild [9] the particle count over all ranks */
+int isph_ins_sizes_dist(const isph_ins *S, long long info[10]);
 
 #ifdef __cplusplus
 }
